@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: batched NMPC solves/sec on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...)
+
+A plain run sets up the headline workload, runs W untimed and K timed steps and prints the line; `ms_per_step` is the
+wall time of one timed step. `--dump-outputs DIR` then writes what the last timed step returned to its caller (U, cost,
+status, iters, info[:, :6] of rank 0's shard; under torch.distributed.run also the gathered U) as DIR/<name>.npy in float32 /
+float64, at most 64 MB in all (a fixed, seeded sample of rows beyond that). The inputs are seeded: the same arguments
+give the same inputs on every run, so two builds can be compared output for output. `--full` adds what the headline
+does not need (N = 1 only): `secondary_solves_per_s`, `cpu_baseline` and `accuracy_summary` below.
 
 A "step" is one pass of the hot path over one batch: every rank solves its own shard of B independent MPC
 problems (weak scaling: B per GPU is fixed) with the parameter batch already resident in HBM, then (N > 1) the
@@ -16,11 +23,11 @@ driver) with the driver's keys plus
                            VALU/latency bound, so the HBM fraction is tiny by construction; the fp32 vector-ALU figure
                            that actually bounds it sits next to it as roofline.valu_tflops / valu_frac / psi_evals_per_solve
   converged_frac         : share of the timed instances that end Converged
-  secondary_solves_per_s : (N = 1) flat {name: solves/s} of the other BASELINE configurations, the `passing` scenario
-                           family (where the solver converges), fp64, polish and dispatch-hint rows
-  cpu_baseline           : the CPU oracle (plain-C restatement of the reference's OpEn algorithm, kind "port") timed on
-                           this box's host cores on a bounded sample of the same batch (N = 1, rank 0 only)
-  accuracy_summary       : (N = 1) flat {name: number} digest of the SURVEY.md 8(d) accuracy protocol
+  secondary_solves_per_s : (--full, N = 1) flat {name: solves/s} of the other BASELINE configurations, the `passing`
+                           scenario family (where the solver converges), fp64, polish and dispatch-hint rows
+  cpu_baseline           : (--full) the CPU oracle (plain-C restatement of the reference's OpEn algorithm, kind "port")
+                           timed on this box's host cores on a bounded sample of the same batch (N = 1, rank 0 only)
+  accuracy_summary       : (--full, N = 1) flat {name: number} digest of the SURVEY.md 8(d) accuracy protocol
                            (tests/accuracy_protocol.py) on small seeded samples of the configs[1] / [2] / [4] generators
 and writes everything it measured, un-abridged (solver statistics, every secondary row, the whole accuracy table, the
 CPU-baseline notes), to `bench_detail.json` next to this file and to stderr.
@@ -266,8 +273,14 @@ def run_workload(env: Env, workload: str, family: str, dtype: str, steps: int, w
 
     status = dstatus.cpu().numpy()
     iters = diters.cpu().numpy()
-    info = dinfo.cpu().numpy().astype(np.float64)
+    info_t = dinfo.cpu().numpy()
+    info = info_t.astype(np.float64)
     U = dU.cpu().numpy()
+    # what the caller of the last timed step received (bench.py --dump-outputs). info[:, 6:8] say which kernel family solved
+    # an instance -- the tail hand-off picks its instances at run time -- so only the solver statistics info[:, :6] go along
+    outputs = {"U": U, "cost": dcost.cpu().numpy(), "status": status, "iters": iters, "info": info_t[:, :6]}
+    if gathered is not None:
+        outputs["U_gathered"] = gathered          # (a device tensor: copied to the host only when dumped)
     kinfo = h.kernel_info()
     launch = h.last_launch_info()
     h.close()
@@ -363,6 +376,7 @@ def run_workload(env: Env, workload: str, family: str, dtype: str, steps: int, w
                    "converged_solves_per_s": float(conv.mean() * env.world * B * steps / elapsed)},
         "_host": (layout, P_host, U, status),
         "_gathered": gathered,
+        "_outputs": outputs,
     }
 
 
@@ -377,9 +391,13 @@ def main(argv=None, env_factory=Env):
                          "parameter vectors harvested from the closed loop on the reference's scenarios / the corridor family")
     ap.add_argument("--batch", type=int, default=None, help="override the per-GPU batch (default: BASELINE's)")
     ap.add_argument("--dtype", choices=("f32", "f64"), default="f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (N = 1 only)")
-    ap.add_argument("--no-accuracy", action="store_true", help="skip the accuracy protocol (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary workloads, the CPU baseline and the accuracy protocol (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads")
+    ap.add_argument("--no-accuracy", action="store_true", help="with --full: skip the accuracy protocol")
     ap.add_argument("--latency-waves", type=int, default=0,
                     help="nmpc_config.latency_waves: 0 = automatic (library default), 1 = one wavefront per instance, "
                          "2..4 = latency mode")
@@ -400,8 +418,11 @@ def main(argv=None, env_factory=Env):
                      args.latency_waves, args.reg_table, args.coop_waves, axis_aligned=args.axis_aligned)
     layout, P_host, U, status = m.pop("_host")
     gathered = m.pop("_gathered")
+    outputs = m.pop("_outputs")
 
     if env.rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         detail = {
             "metric": f"MPC solves/sec (N={layout.N}, batched)",
             "value": m["value"],
@@ -425,12 +446,12 @@ def main(argv=None, env_factory=Env):
         }
         if m.get("scale"):      # launched under torch.distributed.run: ranks / per-rank times / gather time at the top level
             detail.update(m["scale"])
-        single = env.world == 1
-        if single and not args.no_secondary:
+        full = args.full and env.world == 1
+        if full and not args.no_secondary:
             detail["secondary"] = secondary_workloads(env, args)
-        if single and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             detail["cpu_baseline"] = cpu_baseline(layout, P_host)
-        if single and not args.no_accuracy:
+        if full and not args.no_accuracy:
             detail["accuracy"] = accuracy_table(env)
         line = compact_line(detail)
         try:                                       # the un-abridged record: a side file + stderr, never stdout
@@ -445,6 +466,31 @@ def main(argv=None, env_factory=Env):
     if env.use_dist:
         env.dist.destroy_process_group()
     return {"U": U, "gathered": gathered, "P_checksum": float(np.abs(P_host).sum())}
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> None:
+    """DIR/<name>.npy for every output of the last timed step: float arrays in their own precision, integer ones as
+    float64 (exact). Above DUMP_LIMIT_BYTES in all, every array keeps the same fixed share of its rows, chosen by a
+    seeded generator (the same rows on every run), and DIR/<name>_rows.npy holds the row indices kept."""
+    arrays = {}
+    for name, a in outputs.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    # (when sampled: 8 bytes of index per kept row, and room for the .npy headers)
+    keep = 1.0 if total <= 0.99 * DUMP_LIMIT_BYTES else \
+        0.95 * DUMP_LIMIT_BYTES / (total + 8 * sum(a.shape[0] for a in arrays.values()))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if keep < 1.0:
+            n = a.shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * keep)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 LINE_TARGET_BYTES, LINE_LIMIT_BYTES = 4096, 8192

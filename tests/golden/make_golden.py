@@ -380,6 +380,105 @@ def main(out_dir=None):
         json.dump(ww, fh)
     print("warehouse_world.json:", len(ww["nodes_world"]), "nodes,", len(ww["graph_edges"]), "edges,", len(ww["map_polygons_world"]), "polygons")
 
+    tc = tcp_consumer_fixture()
+    with open(os.path.join(OUT, "tcp_consumer.json"), "w") as fh:
+        json.dump(tc, fh, indent=1)
+    print("tcp_consumer.json:", {k: len(v["trace"]) for k, v in tc["runs"].items()}, "recorded accesses")
+
+
+# ---------------------------------------------------------------------------------------------------------
+class _Traced:
+    """Stand-in that forwards to `obj` and logs [role, member, value] for every attribute read / method call of the
+    caller; objects returned by method calls are traced in turn under `role` of their own."""
+
+    def __init__(self, obj, role, trace, roles):
+        self._obj, self._role, self._trace, self._roles = obj, role, trace, roles
+
+    def __getattr__(self, name):
+        v = getattr(self._obj, name)
+        if not callable(v):
+            self._trace.append([self._role, name, _jsonable(v)])
+            return v
+
+        def call(*args, **kwargs):
+            r = v(*args, **kwargs)
+            role = self._roles.get((self._role, name))
+            self._trace.append([self._role, name + "()", None if role else _jsonable(r),
+                                {"n_args": len(args), "len_arg0": len(args[0]) if args and hasattr(args[0], "__len__") else None,
+                                 "kwargs": sorted(kwargs)}])
+            return _Traced(r, role, self._trace, self._roles) if role else r
+        return call
+
+
+def _jsonable(v):
+    if isinstance(v, np.ndarray):
+        return v.tolist()
+    if isinstance(v, (list, tuple)):
+        return [_jsonable(x) for x in v]
+    if isinstance(v, (np.floating, np.integer)):
+        return v.item()
+    return v
+
+
+def tcp_consumer_fixture():
+    """Row f4, consumer side: the REFERENCE's TrajectoryTracker.run_solver_tcp (pkg_mpc_tracker/trajectory_tracker.py:385-416,
+    imported with stub `opengen` / `casadi` modules for its import lines) against this repository's OptimizerTcpManager +
+    server with the scripted solver of tests/test_tcp_cpu.py: every member of the manager / response / answer it touches,
+    in order, with the value it saw, and what it returned (or raised). tests/test_tcp_cpu.py replays the trace against the
+    current manager and checks the in-repo consumer returns the same."""
+    import importlib
+    root = os.path.dirname(os.path.dirname(HERE))
+    sys.path.insert(0, root)
+    sys.path.insert(0, os.path.join(root, "tests"))
+    import test_tcp_cpu as ttc
+    from dyobav_mpcnwta_warehouse_amd import tcp
+    og = types.ModuleType("opengen")
+    og.__path__ = []
+    sub = types.ModuleType("opengen.opengen")
+    sub.__path__ = []
+    tcpm = types.ModuleType("opengen.opengen.tcp")
+    tcpm.__path__ = []
+    ss = types.ModuleType("opengen.opengen.tcp.solver_status")
+    ss.SolverStatus = object
+    og.opengen, sub.tcp, tcpm.solver_status = sub, tcpm, ss
+    og.tcp = types.SimpleNamespace(OptimizerTcpManager=tcp.OptimizerTcpManager)
+    saved = {k: sys.modules.get(k) for k in ("opengen", "opengen.opengen", "opengen.opengen.tcp", "opengen.opengen.tcp.solver_status")}
+    sys.modules.update({"opengen": og, "opengen.opengen": sub, "opengen.opengen.tcp": tcpm, "opengen.opengen.tcp.solver_status": ss})
+    try:
+        ref_tt = importlib.import_module("pkg_mpc_tracker.trajectory_tracker")
+        ref_mm = importlib.import_module("basic_motion_model.motion_model")
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+    roles = {("manager", "call"): "response", ("response", "get"): "answer"}
+    p_ok, p_err, state = [1.5] + [0.0] * 2777, [0.0] * 5, [1.0, 2.0, 0.3]
+    out = {"source": "recorded by tests/golden/make_golden.py: the reference's TrajectoryTracker.run_solver_tcp "
+                     "(pkg_mpc_tracker/trajectory_tracker.py:385-416) against this repository's tcp.OptimizerTcpManager",
+           "nu": 2, "ts": 0.2, "state": state, "runs": {}}
+    for name, p in (("ok", p_ok), ("error", p_err)):
+        mng = tcp.OptimizerTcpManager("mpc_solver/navi_fast", solver_factory=ttc._Scripted)
+        mng.start()
+        trace = []
+        me = types.SimpleNamespace(mng=_Traced(mng, "manager", trace, roles), nu=2, ts=0.2,
+                                   motion_model=ref_mm.UnicycleModel(0.2, rk4=True))
+        run = {"parameters": {"head": p[:1], "len": len(p)}, "trace": trace}
+        try:
+            r = ref_tt.TrajectoryTracker.run_solver_tcp(me, p, np.array(state))
+            run["returned"] = {"taken_states": _jsonable(r[0]), "pred_states": _jsonable(r[1]), "actions": _jsonable(r[2]),
+                               "cost": r[3], "solve_time_ms": r[4], "exit_status": r[5]}
+        except RuntimeError as exc:
+            run["raised"] = str(exc)
+        finally:
+            try:
+                mng.kill()
+            except OSError:
+                pass
+        out["runs"][name] = run
+    return out
+
 
 # ---------------------------------------------------------------------------------------------------------
 def assemble_fixture(K=6, seed=77):

@@ -55,3 +55,25 @@ def test_bench_under_the_launcher_on_one_gpu_agrees_with_the_plain_run():
         plain = _run([sys.executable] + ARGS)
     assert abs(launched["value"] - plain["value"]) <= 0.05 * plain["value"], (launched["value"], plain["value"])
     assert launched["roofline"]["psi_evals_per_solve"] == plain["roofline"]["psi_evals_per_solve"]     # bit-identical solves
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run (no --full) prints the headline without the secondary rows, the CPU baseline or the accuracy digest;
+    --steps sets the timed steps; --dump-outputs writes the last step's outputs, float32 / float64 only, the same arrays
+    from two runs of the same arguments (seeded inputs; the number of steps does not change the results)."""
+    import numpy as np
+    base = [sys.executable, "bench.py", "--gpus", "1", "--warmup", "1", "--batch", "8192"]
+    recs = [_run(base + ["--steps", str(k), "--dump-outputs", str(tmp_path / str(k))]) for k in (2, 3)]
+    for k, rec in zip((2, 3), recs):
+        assert rec["steps"] == k and rec["ms_per_step"] > 0
+        assert abs(rec["value"] - 8192 / (rec["ms_per_step"] * 1e-3)) < 1e-3 * rec["value"]
+        assert not {"secondary_solves_per_s", "cpu_baseline", "accuracy_summary"} & set(rec)
+    names = {"U", "cost", "status", "iters", "info"}
+    for k in (2, 3):
+        assert sorted(os.listdir(tmp_path / str(k))) == sorted(n + ".npy" for n in names)
+    shapes = {"U": (8192, 40), "cost": (8192,), "status": (8192,), "iters": (8192, 2), "info": (8192, 6)}
+    for n in names:
+        a, b = np.load(tmp_path / "2" / (n + ".npy")), np.load(tmp_path / "3" / (n + ".npy"))
+        assert a.dtype == np.float32 if n in ("U", "cost", "info") else a.dtype == np.float64, (n, a.dtype)
+        assert a.shape == shapes[n] and np.array_equal(a, b), n
+    assert np.isfinite(np.load(tmp_path / "2" / "U.npy")).all()

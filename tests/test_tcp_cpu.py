@@ -4,7 +4,6 @@ is not pinned by anything in the reference ("wire format unpinned", see the modu
 import json
 import os
 import socket
-import types
 
 import numpy as np
 import pytest
@@ -174,65 +173,73 @@ def test_shift_solution():
     np.testing.assert_array_equal(shift_solution(U), [[2, 3, 4, 5, 4, 5], [8, 9, 10, 11, 10, 11]])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference tree is only in the authoring container")
+def _same(got, seen):
+    if isinstance(seen, list):
+        return np.array_equal(np.asarray(got, dtype=float), np.asarray(seen, dtype=float))
+    return got == seen
+
+
 def test_the_references_own_tcp_consumer_accepts_our_answers():
     """What CAN be pinned of row f4 without opengen: the consumer side. The REFERENCE's TrajectoryTracker.run_solver_tcp
-    (pkg_mpc_tracker/trajectory_tracker.py:385-416, imported from /root/reference with stub `opengen` / `casadi` modules
-    for its import lines) is run against this repo's OptimizerTcpManager + server -- `.call(parameters)`, `.is_ok()`,
-    `.get().solution / .cost / .exit_status / .solve_time_ms`, and on an error `.get().code / .message` + `.kill()` --
-    and must return exactly what its in-process twin run_solver returns for the same solver answers."""
-    import importlib
-    import sys
-    saved = {k: sys.modules.get(k) for k in ("opengen", "opengen.opengen", "opengen.opengen.tcp", "opengen.opengen.tcp.solver_status",
-                                             "casadi", "casadi.casadi", "configs", "pkg_mpc_tracker", "pkg_mpc_tracker.trajectory_tracker")}
-    og = types.ModuleType("opengen")
-    og.__path__ = []
-    sub = types.ModuleType("opengen.opengen")
-    sub.__path__ = []
-    tcpm = types.ModuleType("opengen.opengen.tcp")
-    tcpm.__path__ = []
-    ss = types.ModuleType("opengen.opengen.tcp.solver_status")
-    ss.SolverStatus = object
-    og.opengen, sub.tcp, tcpm.solver_status = sub, tcpm, ss
-    og.tcp = types.SimpleNamespace(OptimizerTcpManager=tcp.OptimizerTcpManager)
-    cs = types.ModuleType("casadi")
-    cs.__path__ = []
-    csc = types.ModuleType("casadi.casadi")
-    csc.SX = type("SX", (), {})
-    cs.casadi = csc
-    sys.modules.update({"opengen": og, "opengen.opengen": sub, "opengen.opengen.tcp": tcpm,
-                        "opengen.opengen.tcp.solver_status": ss, "casadi": cs, "casadi.casadi": csc})
-    sys.path.insert(0, "/root/reference/src")
-    try:
-        for k in ("configs", "pkg_mpc_tracker", "pkg_mpc_tracker.trajectory_tracker"):
-            sys.modules.pop(k, None)
-        ref_tt = importlib.import_module("pkg_mpc_tracker.trajectory_tracker")
-        ref_mm = importlib.import_module("basic_motion_model.motion_model")
+    (pkg_mpc_tracker/trajectory_tracker.py:385-416) was run against this repo's OptimizerTcpManager + server with the
+    scripted solver above, and every member of the manager / response / answer it touched was recorded in order with the
+    value it saw (`.call(parameters)`, `.is_ok()`, `.get().solution / .cost / .exit_status / .solve_time_ms`, and on an
+    error `.get().code / .message` + `.kill()`), together with what it returned or raised (tests/golden/tcp_consumer.json,
+    tests/golden/make_golden.py). Replayed against the current manager every member must answer as it did then, and this
+    repo's tracker over TCP must return what the reference's consumer returned."""
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "tcp_consumer.json")))
+    state = np.array(rec["state"])
+    for name, run in rec["runs"].items():
+        head, n = run["parameters"]["head"], run["parameters"]["len"]
+        p = head + [0.0] * (n - len(head))
         fake = _Scripted()
         mng = tcp.OptimizerTcpManager("mpc_solver/navi_fast", solver_factory=lambda: fake)
         mng.start()
-        me = types.SimpleNamespace(mng=mng, solver=_Scripted(), use_tcp=False, nu=2, ts=0.2,
-                                   motion_model=ref_mm.UnicycleModel(0.2, rk4=True))
-        p, state = [1.5] + [0.0] * 2777, np.array([1.0, 2.0, 0.3])
-        over_tcp = ref_tt.TrajectoryTracker.run_solver_tcp(me, p, state)
-        in_proc = ref_tt.TrajectoryTracker.run_solver(me, p, state)
-        for a, b in zip(over_tcp[:3], in_proc[:3]):                  # taken_states, pred_states, actions
-            np.testing.assert_array_equal(np.array(a), np.array(b))
-        assert over_tcp[3] == in_proc[3] and over_tcp[5] == in_proc[5] == "Converged"      # cost, exit status
-        assert over_tcp[4] == 1.25                                   # solve_time_ms as the server reported it
-        with pytest.raises(RuntimeError, match=r"MPC Solver error: \[1600\]"):
-            ref_tt.TrajectoryTracker.run_solver_tcp(me, [0.0] * 5, state)
-        with pytest.raises(OSError):
-            mng.ping()                                               # the reference killed the server (:396)
-    finally:
-        sys.path.remove("/root/reference/src")
-        for k in ("configs", "pkg_mpc_tracker", "pkg_mpc_tracker.trajectory_tracker", "basic_motion_model", "basic_motion_model.motion_model"):
-            sys.modules.pop(k, None)
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+        objs = {"manager": mng}
+        try:
+            for role, member, seen, *meta in run["trace"]:
+                obj = objs[role]
+                if member.endswith("()"):
+                    assert meta[0]["kwargs"] == [] and meta[0]["len_arg0"] in (None, len(p)), (name, member, meta)
+                    got = getattr(obj, member[:-2])(*((p,) if meta[0]["n_args"] == 1 else ()))
+                    nxt = {"call()": "response", "get()": "answer"}.get(member)
+                    if nxt:
+                        objs[nxt] = got
+                        continue
+                else:
+                    got = getattr(obj, member)
+                assert _same(got, seen), (name, role, member, got, seen)
+            if name == "error":
+                with pytest.raises(OSError):
+                    mng.ping()                                       # the reference killed the server (:396)
+        finally:
+            try:
+                mng.kill()
+            except OSError:
+                pass
+        # this repo's consumer over the socket returns what the reference's returned
+        mpc, rob = MpcConfiguration.from_yaml(CFG), CircularRobotSpecification.from_yaml(CFG)
+        assert rob.ts == rec["ts"]
+        tr = TrajectoryTracker(mpc, rob, use_tcp=True, verbose=False, solver_factory=_Scripted)
+        tr.load_motion_model(UnicycleModel(rob.ts))
+        if "raised" in run:
+            with pytest.raises(RuntimeError) as exc:
+                tr.run_solver(p, state)
+            assert run["raised"].startswith("MPC Solver error: [1600]") and "[1600]" in str(exc.value)
+            with pytest.raises(OSError):
+                tr.mng.ping()
+            continue
+        try:
+            out = tr.run_solver(p, state)
+        finally:
+            tr.mng.kill()
+        want = run["returned"]
+        # (the states are rolled out by this repo's motion model: same RK4, last-bit differences in the sums)
+        for got, key in zip(out[:2], ("taken_states", "pred_states")):
+            np.testing.assert_allclose(np.asarray(got), np.asarray(want[key]), rtol=1e-12, atol=1e-12, err_msg=key)
+        assert _same([np.asarray(a) for a in out[2]], want["actions"])                  # the controls themselves: exact
+        assert out[3] == want["cost"] and out[5] == want["exit_status"] == "Converged"
+        assert out[4] == want["solve_time_ms"] == 1.25                                    # solve_time_ms as the server reported it
 
 
 # ---- the RECALLED wire documents (tests/recalled/tcp_wire.json: not reference-backed, see tests/recalled/README.md) ----------------------------------------

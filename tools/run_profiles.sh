@@ -8,8 +8,8 @@ export TMPDIR=/tmp
 cd /tmp
 B="python3 $R/bench.py"
 LEAN="--no-cpu-baseline --no-secondary --no-accuracy"
-# 1. headline line (secondary workloads, CPU baseline, accuracy table), same command the driver runs
-$B > $OUT/cfg2_bench.json 2> $OUT/cfg2_bench.err
+# 1. headline line with everything --full adds (secondary workloads, CPU baseline, accuracy table)
+$B --full > $OUT/cfg2_bench.json 2> $OUT/cfg2_bench.err
 cp $R/bench_detail.json $OUT/cfg2_bench_detail.json 2>/dev/null
 # 2. kernel trace + stats of the headline workload (same kernel, same batch)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B $LEAN --steps 3 > $OUT/cfg2_bench_under_rocprof.json 2> $OUT/stats.err
