@@ -260,11 +260,13 @@ class Handle:
         return float(ms.value)
 
     def last_launch_info(self) -> dict:
-        """Which kernel family / variant the last solve or eval call launched (``nmpc_last_launch_info``)."""
+        """Which kernel family / variant the last solve or eval call launched (``nmpc_last_launch_info``). ``order_source``:
+        0 index order, 1 the caller's (``set_dispatch_order``), 2 one evaluation, 3 a pilot launch."""
         v = (C.c_int32 * 8)()
         _check(self._lib.nmpc_last_launch_info(self._h, C.byref(v)))
         return {"family": ("throughput", "latency", "cooperative")[v[0]], "axis_aligned": int(v[1]),
-                "staged_outer_iterations": int(v[2]), "polish_selected": int(v[3]), "tail_handed_off": int(v[4])}
+                "staged_outer_iterations": int(v[2]), "polish_selected": int(v[3]), "tail_handed_off": int(v[4]),
+                "deep_parked": int(v[5]), "order_source": int(v[6])}
 
     def kernel_info(self) -> dict:
         v = [C.c_int32() for _ in range(5)]

@@ -43,10 +43,14 @@ int fail(int code, const char* fmt, ...)
                         hipGetErrorString(e_));                                                              \
     } while (0)
 
-// grow-only device buffer
+// grow-only device buffer, freed when it goes out of scope (or with the handle that holds it)
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t bytes)
     {
         if (bytes <= cap) return 0;
@@ -239,6 +243,7 @@ struct nmpc_handle_s {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int last_tail = 0;              // tail hand-off of the last solve: the parking threshold it ran with (0 = none)
+    int last_order = 0;             // dispatch order of the last solve: 0 index order, 1 the caller's, 2 one evaluation, 3 a pilot launch
     bool timed = false;
     int ptr_mode = NMPC_PTR_DETECT;
     DevBuf dP, dU, dcost, dstatus, diters, du0, dy, dc0, dinfo, dY2, dC2, dpsi, dgrad, df2, dws;
@@ -364,8 +369,13 @@ __device__ __forceinline__ void eval_instance(const nmpc::KParams<T>& kp, const 
     const int inst = blockIdx.x, N = kp.N;
     nmpc::Instance<T, LPS, GLB, RS, false, false, AXIS> I(kp, kp.P + (size_t)inst * kp.np, lds,
                                                         GLB ? kp.ws + (long long)inst * kp.ws_stride : nullptr);
-    if (I.load()) {
-        if (I.lane == 0) ep.psi[inst] = __builtin_nanf("");
+    if (I.load()) { // (not evaluated: every output of the instance is NaN)
+        if (I.lane == 0) {
+            ep.psi[inst] = __builtin_nanf("");
+            if (ep.f2sq) ep.f2sq[inst] = __builtin_nanf("");
+        }
+        if (ep.grad)
+            for (int j = threadIdx.x; j < 2 * N; j += blockDim.x) ep.grad[(size_t)inst * 2 * N + j] = __builtin_nanf("");
         return;
     }
     const int kk = I.act ? I.k : 0;
@@ -707,8 +717,13 @@ void eval_coop_kernel(nmpc::KParams<T> kp, nmpc::EvalParams<T> ep)
     I.cw_ = wave;
     I.CW_ = (int)(blockDim.x >> 6);
     I.coop_x = lds + kp.lds_xch;
-    if (I.load()) {
-        if (threadIdx.x == 0) ep.psi[inst] = __builtin_nanf("");
+    if (I.load()) { // (not evaluated: every output of the instance is NaN)
+        if (threadIdx.x == 0) {
+            ep.psi[inst] = __builtin_nanf("");
+            if (ep.f2sq) ep.f2sq[inst] = __builtin_nanf("");
+        }
+        if (ep.grad)
+            for (int j = threadIdx.x; j < 2 * N; j += blockDim.x) ep.grad[(size_t)inst * 2 * N + j] = __builtin_nanf("");
         return;
     }
     const int kk = I.act ? I.k : 0;
@@ -1122,6 +1137,7 @@ int run_solve(nmpc_handle_s* h, nmpc::KParams<T>& k, int B, bool allow_staging)
     if (int rc = prepare_axis<T>(h, pl.has_axis, k, B)) return rc;
     h->last_mode = pl.mode;
     h->last_axis = pl.has_axis ? k.axis_mode : -1;
+    h->last_order = k.order ? 1 : 0;
     // Resumable solve: up to two stage boundaries (outer-iteration count, ranking key of the launch that follows).
     //  * first (nmpc_config.staged, ranked by ||F2||) -- the instances whose hard constraints are still violated after the
     //    first inner solve are the ones that will run into the iteration caps. Automatic (one outer iteration) for
@@ -1177,6 +1193,8 @@ int run_solve(nmpc_handle_s* h, nmpc::KParams<T>& k, int B, bool allow_staging)
         }
     h->last_staged = n_stage == 0 ? 0 : n_stage == 1 ? stage_cap[0] : 100 * stage_cap[0] + stage_cap[1];
     h->last_tail = 0;
+    if (proxy) h->last_order = 2;
+    else if (n_stage > 0) h->last_order = 3;
     // (the evaluation order below goes into k.order for the rest of this function only: the caller's k gets its own back)
     struct OrderGuard {
         nmpc::KParams<T>& kk;
@@ -1429,9 +1447,11 @@ int polish_batch(nmpc_handle_s* h, const nmpc::KParams<T>& k, int B, bool y_user
     q.status = static_cast<int*>(h->pstatus.p);
     q.iters = static_cast<int*>(h->piters.p);
     q.info = static_cast<double*>(h->pinfo.p);
-    const int keep_mode = h->last_mode, keep_axis = h->last_axis, keep_staged = h->last_staged, keep_tail = h->last_tail;
+    const int keep_mode = h->last_mode, keep_axis = h->last_axis, keep_staged = h->last_staged, keep_tail = h->last_tail,
+              keep_order = h->last_order;
     rc = run_solve<double>(h, q, ns, false);
-    h->last_mode = keep_mode, h->last_axis = keep_axis, h->last_staged = keep_staged, h->last_tail = keep_tail;
+    h->last_mode = keep_mode, h->last_axis = keep_axis, h->last_staged = keep_staged, h->last_tail = keep_tail,
+    h->last_order = keep_order;
     if (rc) return rc;
     hipLaunchKernelGGL(polish_scatter_kernel<T>, dim3(ns), dim3(128), 0, h->stream, sel, (const double*)q.U, (const double*)q.y,
                        (const double*)q.cost, (const int*)q.status, (const int*)q.iters, (const double*)q.info, n2, k.U, k.y,
@@ -1455,9 +1475,7 @@ int solve_trace(nmpc_handle_s* h, const double* p, const double* u0, const doubl
     fill_kparams(h, k);
     k.B = 1;
     int rc;
-    struct Scoped : DevBuf { // (local buffers: freed on every path out of this function)
-        ~Scoped() { release(); }
-    } dtrace, dc0;
+    DevBuf dtrace, dc0; // (local buffers: freed on every path out of this function)
     if ((rc = dtrace.reserve(tlen * sizeof(double)))) return rc;
     if ((rc = h->dP.reserve(np * sizeof(double)))) return rc;
     if ((rc = h->dU.reserve(n * sizeof(double)))) return rc;
@@ -1586,6 +1604,8 @@ int eval_batch(nmpc_handle_s* h, const T* P, const T* U, const T* Y, const T* C,
     h->last_axis = has_axis ? k.axis_mode : -1;
     h->last_staged = 0;
     h->last_polish_selected = 0;
+    h->last_tail = 0;
+    h->last_order = 0;
     if (!fn2 || k.axis_mode != 0) {
         hipLaunchKernelGGL(fn, dim3(B), dim3(64 * waves), lds_bytes, h->stream, k, ep);
         HIP_TRY(hipGetLastError());
@@ -1998,15 +2018,10 @@ int nmpc_destroy(nmpc_handle h)
     if (!h) return 0;
     (void)hipSetDevice(h->cfg.device_id);
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
-    for (DevBuf* b : {&h->dP, &h->dU, &h->dcost, &h->dstatus, &h->diters, &h->du0, &h->dy, &h->dc0, &h->dinfo,
-                      &h->dY2, &h->dC2, &h->dpsi, &h->dgrad, &h->df2, &h->dws, &h->dorder, &h->dflag, &h->dresume,
-                      &h->dorder2, &h->dhist, &h->ddeep, &h->psel, &h->pP, &h->pU0, &h->pY, &h->pC, &h->pU, &h->pcost, &h->pstatus,
-                      &h->piters, &h->pinfo})
-        b->release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h; // (the device buffers: DevBuf's destructor)
     return 0;
 }
 
@@ -2145,6 +2160,15 @@ int nmpc_last_launch_info(nmpc_handle h, int32_t out[8])
     out[2] = h->last_staged;
     out[3] = h->last_polish_selected;
     out[4] = h->last_tail;
+    if (h->last_tail > 0) { // instances the tail launch took over inside an inner solve: KParams::dyn_ctr[3], capped at the slots
+        int parked = 0;
+        HIP_TRY(hipSetDevice(h->cfg.device_id));
+        HIP_TRY(hipMemcpyAsync(&parked, static_cast<const int*>(h->dhist.p) + 2 * kRankBuckets + 3, sizeof(int),
+                               hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        out[5] = std::min(parked, h->last_tail);
+    }
+    out[6] = h->last_order;
     return 0;
 }
 

@@ -93,9 +93,9 @@ __device__ __forceinline__ void solve_instance_spec(const KParams<T>& kp, const 
             uv = kc->u0[(size_t)inst * 2 * N + 2 * kk];
             uw = kc->u0[(size_t)inst * 2 * N + 2 * kk + 1];
         }
-        if (kc->y && kc->y_is_input) {
-            yv = kc->y[(size_t)inst * 2 * N + kk];
-            yw = kc->y[(size_t)inst * 2 * N + N + kk];
+        if (kc->y && kc->y_is_input) { // (projected on Y = [-1e12, 1e12] like at the head of every outer iteration)
+            yv = tclamp(kc->y[(size_t)inst * 2 * N + kk], T(-1e12), T(1e12));
+            yw = tclamp(kc->y[(size_t)inst * 2 * N + N + kk], T(-1e12), T(1e12));
         }
         c = kc->c0v ? kc->c0v[inst] : kc->c_init;
     }

@@ -128,3 +128,39 @@ def test_layout_bookkeeping_without_a_device():
     cfg.N_hor = 0
     with pytest.raises(nm.NmpcError):
         nm.layout_info(cfg)
+
+
+def _capi_source():
+    return open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_capi.hip")).read()
+
+
+def _block(text, head):
+    """The brace-balanced body that follows the first match of the regex `head`."""
+    m = re.search(head, text)
+    assert m, head
+    i = text.index("{", m.end() - 1)
+    depth = 0
+    for j in range(i, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[j], 0)
+        if depth == 0:
+            return text[i + 1:j]
+    raise AssertionError(head)
+
+
+def test_handle_teardown_releases_every_device_buffer():
+    """nmpc_destroy must give back every device buffer of the handle -- either DevBuf frees itself in its destructor (and
+    cannot be copied, so no buffer is freed twice), or every DevBuf member of nmpc_handle_s is on nmpc_destroy's release
+    list. A buffer that is neither leaks its device memory with every handle (one per BatchEvaluator / bench run)."""
+    src = re.sub(r"//[^\n]*", "", _capi_source())
+    devbuf = _block(src, r"\bstruct\s+DevBuf\s*\{")
+    if re.search(r"~DevBuf\s*\(\s*\)\s*\{[^}]*\brelease\s*\(\s*\)", devbuf):
+        assert re.search(r"DevBuf\s*\(\s*const\s+DevBuf\s*&\s*\)\s*=\s*delete", devbuf), "DevBuf frees itself: its copies must be deleted"
+        assert re.search(r"operator\s*=\s*\(\s*const\s+DevBuf\s*&\s*\)\s*=\s*delete", devbuf), "DevBuf frees itself: its copies must be deleted"
+        return
+    members = []
+    for decl in re.findall(r"^\s*DevBuf\s+([^;]+);", _block(src, r"\bstruct\s+nmpc_handle_s\s*\{"), flags=re.M):
+        members += [m.strip() for m in decl.split(",")]
+    assert len(members) > 20, members
+    destroy = _block(src, r"\bint\s+nmpc_destroy\s*\(\s*nmpc_handle\s+h\s*\)\s*\{")
+    missing = [m for m in members if not re.search(r"&\s*h->" + m + r"\b", destroy) and not re.search(r"h->" + m + r"\.release\s*\(", destroy)]
+    assert not missing, f"nmpc_destroy does not release {missing}"

@@ -12,7 +12,7 @@ import dyobav_mpcnwta_warehouse_amd as nm
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("U", "cost", "status", "iters")
+KEYS = ("U", "y", "cost", "status", "iters")
 
 
 def _cfg(lay, hint, **ov):
@@ -106,3 +106,42 @@ def test_tail_handoff_on_the_general_member_and_in_small_or_other_launches():
         assert h.last_launch_info()["family"] == "latency" and h.last_launch_info()["tail_handed_off"] == 0
     with pytest.raises(nm.NmpcError):
         nm.Handle(_cfg(lay, 40, tail_latency=-2))
+
+
+@pytest.mark.parametrize("dims,hint,slots", [((20, 10, 10, 40), 40, 14), ((20, 10, 10, 15), 10, 4)], ids=["cfg2-14slot", "cfg1-4slot"])
+def test_deep_parks_return_the_plain_launch_bits(dims, hint, slots):
+    """Cap-bound solves (the contract family at the default 500 inner iterations) are still inside an inner solve when the
+    launch drains, so the hand-off parks them there (KParams::deep: iterate, gradient, L-BFGS ring, multipliers, penalty)
+    and the tail member resumes that very iteration. nmpc_last_launch_info reports how many did (`deep_parked`); every
+    result array -- the multipliers y included -- must equal one plain launch (index order, no hand-off), on both members
+    of the kernel pair and with an evaluation budget that truncates parked solves."""
+    lay = nm.scenarios.ParamLayout(*dims)
+    n_ped, n_hyp = (4, 10) if dims[3] == 40 else (2, 5)
+    B = 8192
+    P = nm.scenarios.make_batch_chunked(B, lay, seed=44, n_ped=n_ped, n_hyp=n_hyp, ped_mode="toward_robot", dtype=np.float32)
+    assert nm.layout_info(_cfg(lay, hint)).reg_slots_f32 == slots
+    Pg = P.copy()                                    # rotated ellipses: the general member of the pair
+    rows = Pg[:, lay.od:lay.od + lay.Ndyn * 21 * 6].reshape(B, lay.Ndyn, 21, 6)
+    rows[::7, 3, :, 4] = 0.4
+    rows[::7, 3, :, 2] *= 1.3
+    deep_total = 0
+    for name, Q, thresholds, ov in (("axis-aligned", P, (64, 512, 0), {}), ("general", Pg, (512,), {}),
+                                    ("budget", P, (512,), dict(max_evaluations=300))):
+        with nm.Handle(_cfg(lay, hint, tail_latency=-1, staged=-1, **ov)) as h:
+            ref = h.solve(Q)
+            li = h.last_launch_info()
+            assert li["tail_handed_off"] == 0 and li["deep_parked"] == 0 and li["order_source"] == 0, li
+        if ov:
+            assert (ref["status"] == 2).sum() > 100
+        for thr in thresholds:
+            with nm.Handle(_cfg(lay, hint, tail_latency=thr, **ov)) as h:
+                r = h.solve(Q)
+                li = h.last_launch_info()
+            print("deep parks:", dims, name, thr, li)
+            assert li["family"] == "throughput" and li["axis_aligned"] == 2 and li["order_source"] in (2, 3), li
+            assert li["tail_handed_off"] == (thr or li["tail_handed_off"]) > 0, li
+            assert 0 < li["deep_parked"] <= li["tail_handed_off"], li
+            _same(r, ref, (name, thr))
+            assert (r["info"][:, 7] > 0).sum() >= li["deep_parked"]
+            deep_total += li["deep_parked"]
+    assert deep_total > 0
