@@ -152,9 +152,11 @@ MARGIN_KINDS = {0: "-", 1: "lipschitz", 2: "linesearch", 3: "pair", 4: "exit", 5
 def _suffix(dtype, reassoc: bool = False) -> str:
     dtype = np.dtype(dtype)
     if reassoc:
-        if dtype != np.float64:
-            raise TypeError("the re-associated variant exists in double precision only")
-        return "r64"
+        if dtype == np.float64:
+            return "r64"
+        if dtype == np.float32:
+            return "r32"
+        raise TypeError(dtype)
     if dtype == np.float64:
         return "f64"
     if dtype == np.float32:
@@ -194,8 +196,8 @@ def psi(pr: Problem, u, c, y, p, grad=True, dtype=np.float64, reassoc=False):
 
 
 def solve(pr: Problem, op: Options, p, u0=None, y0=None, dtype=np.float64, reassoc=False):
-    """One ALM/PANOC solve. Returns (u, y, result-record). `reassoc`: the same fp64 algorithm with its sums associated
-    differently (nmpc_oracle_impl.h, ORC_REASSOC)."""
+    """One ALM/PANOC solve. Returns (u, y, result-record). `reassoc`: the same algorithm in the same precision with its
+    sums associated differently (nmpc_oracle_impl.h, ORC_REASSOC; fp64 and fp32)."""
     p = np.ascontiguousarray(p, dtype=dtype)
     assert p.size == pr.np_
     u = np.zeros(2 * pr.N, dtype=dtype) if u0 is None else np.array(u0, dtype=dtype)

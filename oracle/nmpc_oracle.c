@@ -1,7 +1,7 @@
 /*
  * nmpc_oracle.c -- CPU ORACLE (TEST INFRASTRUCTURE, NOT PRODUCT CODE). See nmpc_oracle.h.
- * Instantiates nmpc_oracle_impl.h for double (the checker) and float (to study fp32 behaviour of the
- * same algorithm on the CPU).
+ * Instantiates nmpc_oracle_impl.h for double (the checker) and float (the checker of the fp32 kernels), and each
+ * of them once more with its sums re-associated (the noise floor of that precision).
  */
 #include "nmpc_oracle.h"
 
@@ -95,6 +95,25 @@ static inline double rsqrt_r64(double x) { return sqrt(x); }
 static inline double rabs_r64(double x) { return fabs(x); }
 static inline double rpow_r64(double x, double y) { return pow(x, y); }
 static inline int risfinite_r64(double x) { return isfinite(x); }
+#include "nmpc_oracle_impl.h"
+#undef REAL
+#undef SUF
+#undef REAL_MIN_POS
+#undef REAL_EPS
+#undef ORC_REASSOC
+
+/* ---------------- float, sums re-associated: the fp32 twin (the noise floor of fp32 solves) ---------------- */
+#define ORC_REASSOC 1
+#define REAL float
+#define SUF(x) x##_r32
+#define REAL_MIN_POS FLT_MIN
+#define REAL_EPS FLT_EPSILON
+static inline float rcos_r32(float x) { return cosf(x); }
+static inline float rsin_r32(float x) { return sinf(x); }
+static inline float rsqrt_r32(float x) { return sqrtf(x); }
+static inline float rabs_r32(float x) { return fabsf(x); }
+static inline float rpow_r32(float x, float y) { return powf(x, y); }
+static inline int risfinite_r32(float x) { return isfinite(x); }
 #include "nmpc_oracle_impl.h"
 #undef REAL
 #undef SUF

@@ -127,6 +127,14 @@ int orc_solve_r64(const orc_problem *pr, const orc_options *op, const double *p,
                   orc_result *res);
 int orc_solve_batch_r64(const orc_problem *pr, const orc_options *op, const double *P, int B, double *U,
                         orc_result *res, int nthreads);
+/* ... and the float solver re-associated the same way (the fp32 noise floor: tests/test_oracle_solver.py,
+ * tests/test_gpu_fp32_paths.py). */
+void orc_psi_r32(const orc_problem *pr, const float *u, float c, const float *y, const float *p,
+                 float *psi, float *grad);
+int orc_solve_r32(const orc_problem *pr, const orc_options *op, const float *p, float *u, float *y,
+                  orc_result *res);
+int orc_solve_batch_r32(const orc_problem *pr, const orc_options *op, const float *P, int B, float *U,
+                        orc_result *res, int nthreads);
 
 /* Iteration trace of one solve (first-divergence audit, tests/accuracy_protocol.py): like orc_solve_*, plus one record
  * of ORC_TRACE_HEAD + 2N doubles per completed inner iteration, up to max_rec records:
@@ -141,6 +149,8 @@ int orc_solve_batch_r64(const orc_problem *pr, const orc_options *op, const doub
 int orc_solve_trace_f64(const orc_problem *pr, const orc_options *op, const double *p, double *u, double *y,
                         orc_result *res, double *trace, int max_rec, int *n_rec);
 int orc_solve_trace_r64(const orc_problem *pr, const orc_options *op, const double *p, double *u, double *y,
+                        orc_result *res, double *trace, int max_rec, int *n_rec);
+int orc_solve_trace_r32(const orc_problem *pr, const orc_options *op, const float *p, float *u, float *y,
                         orc_result *res, double *trace, int max_rec, int *n_rec);
 int orc_solve_trace_f32(const orc_problem *pr, const orc_options *op, const float *p, float *u, float *y,
                         orc_result *res, double *trace, int max_rec, int *n_rec);

@@ -13,12 +13,13 @@
 #error "include from nmpc_oracle.c"
 #endif
 
-/* ORC_REASSOC (third instantiation, suffix _r64): THE SAME ALGORITHM IN THE SAME PRECISION WITH ITS SUMS ASSOCIATED
+/* ORC_REASSOC (instantiations with suffix _r64 and _r32): THE SAME ALGORITHM IN THE SAME PRECISION WITH ITS SUMS ASSOCIATED
  * DIFFERENTLY -- inner products and the accumulations over obstacles / polygons / robots run in reverse index order, the
  * two obstacle snapshots swap places, the rollout positions are X0 + (running sum of the increments) instead of a chain
  * of additions onto X. No decision rule, constant or tie-break differs (the segment minimum keeps "first wins"). It
- * exists to measure how far two correct fp64 implementations of this solver end up from each other (the oracle's own
- * noise floor under re-association: tests/accuracy_protocol.py). */
+ * exists to measure how far two correct implementations of this solver in one precision end up from each other (the
+ * oracle's own noise floor under re-association: tests/accuracy_protocol.py; in fp32 the bar of
+ * tests/test_gpu_fp32_paths.py). */
 #ifdef ORC_REASSOC
 #define ORC_IDX(i, n) ((n) - 1 - (i))
 #else

@@ -25,7 +25,7 @@ def make_case(rng, axis_aligned=None):
         axis_aligned = rng.random() < 0.34
     N = int(rng.choice([rng.integers(3, 65), 20, 21, 22, 32, 33, 40, 42, 43, 64]))
     Nother, Nstc = int(rng.integers(1, 13)), int(rng.integers(1, 15))
-    Ndyn = int(rng.choice([rng.integers(1, 30), rng.integers(30, 220), 12, 13, 42, 43, 96, 97, 144, 145, 160]))
+    Ndyn = int(rng.choice([rng.integers(1, 30), rng.integers(30, 220), 12, 13, 18, 19, 42, 43, 96, 97, 144, 145, 160]))
     rows = int(rng.choice([0, 1, 2, 3, Ndyn, rng.integers(0, Ndyn + 1)]))
     lay = ParamLayout(N=N, Nother=Nother, Nstc=Nstc, Ndyn=Ndyn)
     B = 4

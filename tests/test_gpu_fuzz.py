@@ -31,6 +31,17 @@ def test_fuzz_solve(seed, outer, inner, cases):
     assert rc == 0, lines[-1]
 
 
+@pytest.mark.parametrize("seed", [24, 25])
+def test_fuzz_solve_fp32(seed):
+    """fp32 short solves, the fp32-only kernels included, against the fp32 oracle at the wide Lipschitz step."""
+    import numpy as np
+    import fuzz_solve
+    lines, out = _collect()
+    rc = fuzz_solve.run(cases=200, seed=seed, n_outer=1, n_inner=4, out=out, dtype=np.float32)
+    print("\n".join(lines))
+    assert rc == 0, lines[-1]
+
+
 def test_fuzz_assemble():
     import fuzz_assemble
     lines, out = _collect()
