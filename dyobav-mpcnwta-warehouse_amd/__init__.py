@@ -15,17 +15,20 @@ Host side (Python, mirrors the reference's interface for the solve path only):
                                 scenarios in lock-step on the device (row f3)
 * :mod:`.tcp`                -- OpEn's TCP/JSON wire format in front of the solver + the ``OptimizerTcpManager`` surface
                                 used by ``TrajectoryTracker(use_tcp=True)`` (row f4)
+* :mod:`.snap`               -- ``WorldTransform`` and ``edge_map`` for ``Handle.set_map`` / ``Handle.snap_hypotheses``: the
+                                predictor's pixel hypotheses -> world points, on the device (``mmp_interface.py:60``,
+                                ``utils_np.py:102-140``, ``main_base.py:196``)
 * :mod:`.scenarios`          -- synthetic parameter batches of BASELINE.json's configurations
 * :mod:`.sharding`           -- one process per GPU, contiguous batch shards, RCCL gather of the results
 
 Device side: ``csrc/`` (hand-written HIP for gfx950) behind the C ABI of ``include/nmpc_hip.h``.
 Import of this package never touches the GPU; the library is loaded on first use.
 """
-from . import scenarios  # noqa: F401
+from . import scenarios, snap  # noqa: F401
 from ._capi import (EXIT_STATUS_NAMES, EXPORTED_SYMBOLS, Handle, NmpcConfigStruct, NmpcError,  # noqa: F401
                     default_config_struct, layout_info, library_path, load_library)
 from .build import build as build_library  # noqa: F401
 from .solver import BatchSolver, OptimizerSolution, Solver, make_config, solver  # noqa: F401
 
-__all__ = ["BatchSolver", "OptimizerSolution", "Solver", "make_config", "solver", "scenarios", "Handle", "NmpcConfigStruct", "NmpcError", "default_config_struct", "layout_info", "load_library",
+__all__ = ["BatchSolver", "OptimizerSolution", "Solver", "make_config", "solver", "scenarios", "snap", "Handle", "NmpcConfigStruct", "NmpcError", "default_config_struct", "layout_info", "load_library",
            "library_path", "build_library", "EXIT_STATUS_NAMES", "EXPORTED_SYMBOLS"]

@@ -80,6 +80,13 @@ class NmpcLoopArgs(C.Structure):
                 [(n, C.c_double) for n in ("hyp_fan_rad", "hyp_radius0", "hyp_radius_growth")])
 
 
+class NmpcSnapArgs(C.Structure):
+    """Mirror of ``struct nmpc_snap_args`` (device pointers)."""
+    _fields_ = ([(n, C.c_int32) for n in ("n_ped", "n_hyp", "x_reverse", "y_reverse")] +
+                [(n, C.c_double) for n in ("rescale", "scale", "offset_x", "offset_y", "x_max", "y_max")] +
+                [("n_snapped", C.c_void_p), ("n_outside", C.c_void_p)])
+
+
 # every symbol include/nmpc_hip.h declares (checked by the CPU test-suite against the built library)
 EXPORTED_SYMBOLS = (
     "nmpc_default_config", "nmpc_layout", "nmpc_create", "nmpc_destroy", "nmpc_param_len", "nmpc_set_stream", "nmpc_use_own_stream", "nmpc_set_pointer_mode",
@@ -87,6 +94,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_solve_batch_f32", "nmpc_solve_batch_f64", "nmpc_solve_trace_f64", "nmpc_eval_batch_f32", "nmpc_eval_batch_f64",
     "nmpc_assemble_params_f32", "nmpc_assemble_params_f64",
     "nmpc_hypotheses_to_ellipses_f32", "nmpc_hypotheses_to_ellipses_f64",
+    "nmpc_set_map", "nmpc_snap_hypotheses_f32", "nmpc_snap_hypotheses_f64",
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_last_error",
 )
@@ -128,12 +136,14 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     lib.nmpc_use_own_stream.argtypes = [vp]
     lib.nmpc_set_pointer_mode.argtypes = [vp, i32]
     lib.nmpc_set_dispatch_order.argtypes = [vp, vp, i32]
+    lib.nmpc_set_map.argtypes = [vp, vp, vp, i32, i32]
     for sfx in ("f32", "f64"):
         getattr(lib, "nmpc_solve_batch_" + sfx).argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32]
         getattr(lib, "nmpc_eval_batch_" + sfx).argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
         getattr(lib, "nmpc_assemble_params_" + sfx).argtypes = [vp, C.POINTER(NmpcAssembleArgs), i32, vp]
         getattr(lib, "nmpc_hypotheses_to_ellipses_" + sfx).argtypes = [vp, vp, i32, vp, i32, C.c_double, C.c_double,
                                                                        C.c_double, C.c_double, i32, vp, vp]
+        getattr(lib, "nmpc_snap_hypotheses_" + sfx).argtypes = [vp, vp, C.POINTER(NmpcSnapArgs), i32, vp]
         getattr(lib, "nmpc_loop_pre_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
         getattr(lib, "nmpc_loop_post_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
@@ -314,6 +324,48 @@ class Handle:
         p = _Arg.ptr
         _check(fn(self._h, p(hypos), P, p(cur), H, float(human_size), float(eps), float(enlarge), float(extra_margin),
                   B, p(dyn_out), p(n_obs_out)))
+
+    def set_map(self, occupied, edge=None):
+        """``nmpc_set_map``: host arrays ``occupied[H, W]`` (non-zero = occupied; for the reference: ``255 - label > 0``)
+        and ``edge[H, W]``; ``edge=None`` computes it with :func:`.snap.edge_map` from ``occupied`` (pass the grey-level
+        occupancy itself then if it has more than one level: the edges between levels count). ``occupied=None`` clears
+        the map."""
+        if occupied is None:
+            _check(self._lib.nmpc_set_map(self._h, None, None, 0, 0))
+            return
+        occ = np.asarray(occupied)
+        if occ.ndim != 2:
+            raise ValueError(f"occupied must be [H, W], got {occ.shape}")
+        if edge is None:
+            from .snap import edge_map
+            edge = edge_map(occ)
+        edge = np.asarray(edge)
+        if edge.shape != occ.shape:
+            raise ValueError(f"edge {edge.shape} and occupied {occ.shape} differ in shape")
+        occ8 = np.ascontiguousarray(occ != 0, dtype=np.uint8)
+        edge8 = np.ascontiguousarray(edge != 0, dtype=np.uint8)
+        _check(self._lib.nmpc_set_map(self._h, occ8.ctypes.data, edge8.ctypes.data, int(occ.shape[0]), int(occ.shape[1])))
+
+    def snap_hypotheses(self, dtype, raw, out, n_ped, n_hyp, transform, rescale=1.0, n_snapped=None, n_outside=None):
+        """``nmpc_snap_hypotheses_*``: device tensors ``raw[B, N_hor, n_ped * n_hyp, 2]`` (network pixel coordinates) ->
+        ``out`` of the same shape (world coordinates, snapped points first in every segment; ``out`` may be ``raw``),
+        enqueued on the handle's stream. ``transform``: a :class:`.snap.WorldTransform`. Optional int32 device outputs
+        ``n_snapped[B, N_hor, n_ped]`` and ``n_outside[B]``."""
+        B, N, P = int(raw.shape[0]), int(raw.shape[1]), int(raw.shape[2])
+        if N != self.cfg.N_hor or P != int(n_ped) * int(n_hyp) or int(raw.shape[3]) != 2:
+            raise ValueError(f"raw must be [B, {self.cfg.N_hor}, {int(n_ped) * int(n_hyp)}, 2], got {tuple(raw.shape)}")
+        if tuple(out.shape) != tuple(raw.shape):
+            raise ValueError(f"out {tuple(out.shape)} and raw {tuple(raw.shape)} differ in shape")
+        a = NmpcSnapArgs()
+        a.n_ped, a.n_hyp = int(n_ped), int(n_hyp)
+        a.x_reverse, a.y_reverse = int(bool(transform.x_reverse)), int(bool(transform.y_reverse))
+        a.rescale, a.scale = float(rescale), float(transform.scale)
+        a.offset_x, a.offset_y = float(transform.offsetx_after), float(transform.offsety_after)
+        a.x_max, a.y_max = float(transform.x_max_before), float(transform.y_max_before)
+        p = _Arg.ptr
+        a.n_snapped, a.n_outside = p(n_snapped), p(n_outside)
+        fn = getattr(self._lib, "nmpc_snap_hypotheses_" + _suffix(dtype))
+        _check(fn(self._h, p(raw), C.byref(a), B, p(out)))
 
     def solve(self, P: np.ndarray, u0=None, y0=None, c0=None, dtype=None, want_info=True) -> dict:
         """Solve a batch held in host memory; returns numpy arrays."""

@@ -19,6 +19,7 @@
 #include "nmpc_spec.h"
 #include "nmpc_hypotheses.h"
 #include "nmpc_step.h"
+#include "nmpc_snap.h"
 
 namespace {
 
@@ -257,6 +258,9 @@ struct nmpc_handle_s {
     // polish: compact fp64 copies of the selected instances and their results
     DevBuf psel, pP, pU0, pY, pC, pU, pcost, pstatus, piters, pinfo;
     std::vector<int32_t> host_status, host_sel;
+    // nmpc_set_map: occupancy mask [map_h][map_w] and the row-major list of edge pixels (col | row << 16), zero-padded
+    DevBuf dmap_occ, dmap_edge;
+    int map_h = 0, map_w = 0, map_n_edge = 0, map_n_edge_pad = 0;
 };
 
 namespace {
@@ -1732,6 +1736,105 @@ int hypotheses_to_ellipses(nmpc_handle_s* h, const T* hypos, int32_t P, const T*
     return 0;
 }
 
+int set_map(nmpc_handle_s* h, const uint8_t* occupied, const uint8_t* edge, int32_t height, int32_t width)
+{
+    if (!h) return fail(NMPC_ERR_INVALID_ARGUMENT, "null handle");
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // a snap that is still running reads the previous map
+    if (!occupied) {
+        h->dmap_occ.release();
+        h->dmap_edge.release();
+        h->map_h = h->map_w = h->map_n_edge = h->map_n_edge_pad = 0;
+        return 0;
+    }
+    if (!edge) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_set_map: edge mask is NULL");
+    if (height < 1 || width < 1 || height > 32767 || width > 32767)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_set_map: map %d x %d outside [1, 32767]", height, width);
+    std::vector<uint32_t> list;
+    for (int r = 0; r < height; ++r)
+        for (int c = 0; c < width; ++c)
+            if (edge[(size_t)r * width + c]) list.push_back((uint32_t)c | ((uint32_t)r << 16));
+    const int n_edge = (int)list.size();
+    list.resize(((size_t)n_edge + 63) / 64 * 64 + 64, 0u); // (never empty: a map without edge pixels is legal)
+    const size_t occ_bytes = (size_t)height * width;
+    if (int rc = h->dmap_occ.reserve(occ_bytes)) return rc;
+    if (int rc = h->dmap_edge.reserve(list.size() * sizeof(uint32_t))) return rc;
+    h->map_h = 0; // (no map while the copies can still fail)
+    HIP_TRY(hipMemcpy(h->dmap_occ.p, occupied, occ_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->dmap_edge.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    h->map_h = height;
+    h->map_w = width;
+    h->map_n_edge = n_edge;
+    h->map_n_edge_pad = (n_edge + 63) / 64 * 64;
+    return 0;
+}
+
+template <typename T, int PPL>
+void launch_snap(nmpc_handle_s* h, const nmpc::SnapParams& a, const T* raw, T* hypos, unsigned grid)
+{
+    if (a.n_edge_pad <= nmpc::kSnapLdsPixels)
+        hipLaunchKernelGGL((nmpc::snap_kernel<T, PPL, true>), dim3(grid), dim3(nmpc::kSnapThreads),
+                           (size_t)a.n_edge_pad * sizeof(unsigned), h->stream, a, raw, hypos);
+    else
+        hipLaunchKernelGGL((nmpc::snap_kernel<T, PPL, false>), dim3(grid), dim3(nmpc::kSnapThreads), 0, h->stream, a, raw, hypos);
+}
+
+template <typename T>
+int snap_hypotheses(nmpc_handle_s* h, const T* raw, const nmpc_snap_args* g, int32_t B, T* hypos)
+{
+    if (!h || !raw || !g || !hypos) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if (B <= 0) return B == 0 ? 0 : fail(NMPC_ERR_INVALID_ARGUMENT, "B = %d < 0", B);
+    if (h->map_h == 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_snap_hypotheses: no map set (nmpc_set_map)");
+    if (g->n_ped < 1 || g->n_hyp < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_snap_hypotheses: n_ped = %d, n_hyp = %d", g->n_ped, g->n_hyp);
+    if ((long long)g->n_ped * g->n_hyp > 256)
+        return fail(NMPC_ERR_UNSUPPORTED, "nmpc_snap_hypotheses: n_ped * n_hyp = %lld points per time offset > 256", (long long)g->n_ped * g->n_hyp);
+    if (!(g->rescale != 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_snap_hypotheses: rescale = %g", g->rescale);
+    if ((long long)B * h->cfg.N_hor > 0x7fffffffLL / 256) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_snap_hypotheses: B = %d too large", B);
+    if (!is_device_ptr(raw) || !is_device_ptr(hypos) || (g->n_snapped && !is_device_ptr(g->n_snapped)) ||
+        (g->n_outside && !is_device_ptr(g->n_outside)))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_snap_hypotheses: every array must be a device pointer");
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    nmpc::SnapParams a;
+    a.items = B * h->cfg.N_hor;
+    a.N = h->cfg.N_hor;
+    a.K = g->n_hyp;
+    a.P = g->n_ped * g->n_hyp;
+    a.H = h->map_h;
+    a.W = h->map_w;
+    a.n_edge = h->map_n_edge;
+    a.n_edge_pad = h->map_n_edge_pad;
+    a.xr = g->x_reverse != 0;
+    a.yr = g->y_reverse != 0;
+    a.rescale = g->rescale;
+    a.scale = g->scale;
+    a.offx = g->offset_x;
+    a.offy = g->offset_y;
+    a.xmax = g->x_max;
+    a.ymax = g->y_max;
+    a.occ = static_cast<const unsigned char*>(h->dmap_occ.p);
+    a.edge = static_cast<const unsigned*>(h->dmap_edge.p);
+    a.n_snapped = g->n_snapped;
+    a.n_outside = g->n_outside;
+    if (a.n_outside) HIP_TRY(hipMemsetAsync(a.n_outside, 0, (size_t)B * sizeof(int32_t), h->stream));
+    // four items per workgroup pass; at most 8 workgroups per CU, so that the edge list is staged a few times per CU only
+    const int wpg = nmpc::kSnapThreads / 64;
+    const long long want = ((long long)a.items + wpg - 1) / wpg, cap = 8LL * std::max(1, h->n_simd / 4);
+    const unsigned grid = (unsigned)std::min(want, cap);
+    HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    if (a.P <= 64)
+        launch_snap<T, 1>(h, a, raw, hypos, grid);
+    else if (a.P <= 128)
+        launch_snap<T, 2>(h, a, raw, hypos, grid);
+    else if (a.P <= 192)
+        launch_snap<T, 3>(h, a, raw, hypos, grid);
+    else
+        launch_snap<T, 4>(h, a, raw, hypos, grid);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return 0;
+}
+
 template <typename T>
 int loop_step(nmpc_handle_s* h, const nmpc_loop_args* g, bool post)
 {
@@ -2135,6 +2238,21 @@ int nmpc_hypotheses_to_ellipses_f64(nmpc_handle h, const double* hypos, int32_t 
                                     double* dyn, int32_t* n_obs)
 {
     return hypotheses_to_ellipses<double>(h, hypos, P, cur, H, human_size, eps, enlarge, extra_margin, B, dyn, n_obs);
+}
+
+int nmpc_set_map(nmpc_handle h, const uint8_t* occupied, const uint8_t* edge, int32_t height, int32_t width)
+{
+    return set_map(h, occupied, edge, height, width);
+}
+
+int nmpc_snap_hypotheses_f32(nmpc_handle h, const float* raw, const nmpc_snap_args* a, int32_t B, float* hypos)
+{
+    return snap_hypotheses<float>(h, raw, a, B, hypos);
+}
+
+int nmpc_snap_hypotheses_f64(nmpc_handle h, const double* raw, const nmpc_snap_args* a, int32_t B, double* hypos)
+{
+    return snap_hypotheses<double>(h, raw, a, B, hypos);
 }
 
 int nmpc_loop_pre_f32(nmpc_handle h, const nmpc_loop_args* a) { return loop_step<float>(h, a, false); }
