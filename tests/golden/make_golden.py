@@ -20,8 +20,10 @@ Fixtures written:
                        (interfaces/mpc_interface.py:52-100: closest-N polygons -> half-spaces, obstacle flattening).
   hypotheses_cases.json hypothesis sets and the obstacle list produced by utils_test.fit_DBSCAN /
                        fit_cluster2gaussian (utils_test.py:133-151) + main_base.py:293-302.
+  hypotheses_edge_cases.json  the same functions on the edge families of tests/hypotheses_cases.py (exact ties, duplicate
+                       points, all-noise offsets, more clusters than slots) with non-default parameters.
 
-Usage:  python tests/golden/make_golden.py
+Usage:  python tests/golden/make_golden.py [out_dir [hypotheses]]     (``hypotheses``: only the two f2 recordings)
 """
 from __future__ import annotations
 
@@ -318,10 +320,24 @@ def tracker_harness():
     return rec
 
 
-def main(out_dir=None):
+def write_hypotheses():
+    hc = hypotheses_fixture()
+    with open(os.path.join(OUT, "hypotheses_cases.json"), "w") as fh:
+        json.dump(hc, fh)
+    print("hypotheses_cases.json:", len(hc), "cases, n_obs =", [c["n_obs"] for c in hc])
+    he = hypotheses_edge_fixture()
+    with open(os.path.join(OUT, "hypotheses_edge_cases.json"), "w") as fh:
+        json.dump(he, fh, separators=(",", ":"))
+    print("hypotheses_edge_cases.json:", len(he), "cases:", [(c["name"], c["n_obs"]) for c in he])
+
+
+def main(out_dir=None, only=None):
     global OUT
     OUT = out_dir or HERE
     os.makedirs(OUT, exist_ok=True)
+    if only == "hypotheses":
+        write_hypotheses()
+        return
     ka = known_answers()
     with open(os.path.join(OUT, "known_answers.json"), "w") as fh:
         json.dump(ka, fh, indent=1)
@@ -357,10 +373,7 @@ def main(out_dir=None):
         json.dump(ac, fh)
     print("assemble_cases.json:", len(ac), "cases")
 
-    hc = hypotheses_fixture()
-    with open(os.path.join(OUT, "hypotheses_cases.json"), "w") as fh:
-        json.dump(hc, fh)
-    print("hypotheses_cases.json:", len(hc), "cases, n_obs =", [c["n_obs"] for c in hc])
+    write_hypotheses()
 
     ec = evaluate_fixture()
     with open(os.path.join(OUT, "evaluate_cases.json"), "w") as fh:
@@ -590,6 +603,49 @@ def hypotheses_fixture(K=8, seed=123):
     return cases
 
 
+def hypotheses_edge_fixture():
+    """f2 at the edges: the inputs of tests/hypotheses_cases.py (coordinates rounded to multiples of 1/64, which are exact
+    in float32 and keep the squared distances near eps^2 exact) through the reference's ``utils_test.fit_DBSCAN`` /
+    ``fit_cluster2gaussian`` and the list assembly of main_base.py:293-302, with the parameters stored in each case: exact
+    ties at eps 1 and 5 (one case with 70 points per offset), duplicate points, offsets where every point is noise, more
+    clusters than ``Ndynobs`` (the recording keeps all n_obs rows; the kernels keep the first Ndynobs), two non-default
+    (enlarge, extra_margin) pairs."""
+    with contextlib.redirect_stdout(io.StringIO()):
+        import utils_test
+    sys.path.insert(0, os.path.dirname(HERE))
+    import hypotheses_cases as hcs
+    A, B_ = dict(enlarge=1.5, extra_margin=0.25), dict(enlarge=1.0, extra_margin=0.125)
+    spec = [("lattice_eps1", "lattice", 4, 12, 2, 1.0, {}), ("lattice_eps1_wide", "lattice", 2, 70, 1, 1.0, A),
+            ("lattice_eps5", "lattice", 4, 14, 1, 5.0, {}), ("lattice_eps5_margin", "lattice", 3, 20, 0, 5.0, B_),
+            ("lattice_half", "lattice", 3, 16, 2, 0.5, A),
+            ("duplicates", "duplicates", 5, 12, 1, 1.0, {}), ("duplicates_margin", "duplicates", 4, 16, 2, 1.0, A),
+            ("duplicates_enlarge1", "duplicates", 3, 10, 0, 2.0, B_),
+            ("all_noise_offsets", "holes", 6, 8, 1, 1.0, {}), ("all_noise_offsets_margin", "holes", 5, 9, 3, 0.5, B_),
+            ("overflow", "duplicates", 3, 24, 1, 1.0, {}), ("overflow_margin", "slots", 2, 30, 2, 1.0, A)]
+    cases = []
+    for k, (name, fam, N, P, H, eps, par) in enumerate(spec):
+        Ndyn = 3 if name.startswith("overflow") else 8
+        par = dict(dict(human_size=0.2, eps=eps, enlarge=2.0, extra_margin=0.0), **par)
+        hyp, cur = hcs.generate(fam, 1, N, P, H, eps, 500 + k, np.float32, Ndyn=Ndyn)
+        hyp, cur = np.round(hyp[0] * 64.0) / 64.0, np.round(cur[0] * 64.0) / 64.0
+        mu_list_list = [[c.tolist() for c in cur]]
+        std_list_list = [[[par["human_size"], par["human_size"]] for _ in range(H)]]
+        for t in range(N):
+            clusters = utils_test.fit_DBSCAN(hyp[t], eps=eps, min_sample=2)
+            mu_list, std_list = utils_test.fit_cluster2gaussian(clusters, enlarge=par["enlarge"], extra_margin=par["extra_margin"])
+            mu_list_list.append([m.tolist() for m in mu_list])
+            std_list_list.append([s.tolist() for s in std_list])
+        n_obs = max(len(m) for m in mu_list_list)                                   # main_base.py:293-302
+        dyn_obs_list = [[[0, 0, 0, 0, 0, 1]] * (N + 1) for _ in range(n_obs)]
+        for Tt, (mu_list, std_list) in enumerate(zip(mu_list_list, std_list_list)):
+            for Nn, (mu, std) in enumerate(zip(mu_list, std_list)):
+                dyn_obs_list[Nn][Tt] = [mu[0], mu[1], std[0], std[1], 0, 1]
+        cases.append(dict(name=name, N=N, Ndyn=Ndyn, params=par, cur=cur.tolist(), hypos=hyp.tolist(), n_obs=n_obs,
+                          dyn_obs_list=dyn_obs_list, counts=[len(m) for m in mu_list_list]))
+    assert any(c["n_obs"] > c["Ndyn"] for c in cases) and any(0 in c["counts"][1:] for c in cases)
+    return cases
+
+
 # ---------------------------------------------------------------------------------------------------------
 def scenario0_static_map(g, ct):
     """BASELINE configs[0]'s static obstacles: the reference's own map pipeline (main_base.py:123-127) on its own PGM.
@@ -782,4 +838,4 @@ def evaluate_fixture(seed=2024):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else None)
+    main(sys.argv[1] if len(sys.argv) > 1 else None, sys.argv[2] if len(sys.argv) > 2 else None)

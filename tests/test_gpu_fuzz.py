@@ -1,8 +1,9 @@
-"""Reduced runs of the randomised differential checks (tests/fuzz_eval.py, fuzz_solve.py, fuzz_assemble.py) with fixed
+"""Reduced runs of the randomised differential checks (tests/fuzz_eval.py, fuzz_solve.py, fuzz_assemble.py, fuzz_hypotheses.py) with fixed
 seeds, so that the driver-run GPU suite -- not a text file under profiles/ -- covers every lane-map / table boundary with
 obstacles ON the path: random dimensions with the table boundaries over-represented, every evaluation code path
 (register / LDS / global table, axis-aligned and general variants, cooperative with 2-4 wavefronts, on-chip cooperative
-with and without helper lanes), short solves with every solver kernel, the assembly kernel; all against the oracle."""
+with and without helper lanes), short solves with every solver kernel, the assembly kernel, the hypothesis-clustering
+kernels; all against the oracle."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -46,5 +47,13 @@ def test_fuzz_assemble():
     import fuzz_assemble
     lines, out = _collect()
     rc = fuzz_assemble.run(cases=600, seed=31, out=out)
+    print("\n".join(lines))
+    assert rc == 0, lines[-1]
+
+
+def test_fuzz_hypotheses():
+    import fuzz_hypotheses
+    lines, out = _collect()
+    rc = fuzz_hypotheses.run(cases=30, seed=41, out=out)
     print("\n".join(lines))
     assert rc == 0, lines[-1]
