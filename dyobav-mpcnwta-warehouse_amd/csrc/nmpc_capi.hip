@@ -11,15 +11,19 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nmpc_hip.h"
 #include "nmpc_assemble.h"
 #include "nmpc_device.h"
+#include "nmpc_plan.h"
 #include "nmpc_spec.h"
 #include "nmpc_hypotheses.h"
 #include "nmpc_step.h"
 #include "nmpc_snap.h"
+
+using namespace nmpc_plan;
 
 namespace {
 
@@ -83,151 +87,11 @@ bool is_device_ptr(const void* ptr)
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-struct Layout {
-    int np, off_rs, off_rv, off_c0, off_c, off_os, off_od, off_qstc, off_qdyn;
-    int lds_alpha, lds_poly, lds_seg, lds_seginv, lds_fl0, lds_fl, lds_iflag, lds_hist, lds_rho, lds_total;
-    int lds_xch, lds_total_spec; // latency mode: exchange area + the other wavefronts' parking areas behind lds_total
-    int lds_park, lds_deepsc;
-    int coop_lanes, lds_t0c; // cooperative kernels: lanes per plane of the exchange area; t = 0 rows of the compressed global table
-    int lds_xch_coop, lds_total_coop; // cooperative mode: two shared parking areas, then the partial-sum exchange area
-    int lds_left, lds_left_alpha;     // LDS table of the rows beyond the register-resident ones (cooperative register kernel)
-    int dyn_cap;          // obstacle rows provisioned per instance
-    int table_entries;    // entries of the obstacle table the kernels index in LDS / the workspace
-    int rs;               // > 0: register-resident obstacle table with this many slots per lane (LDS keeps t = 0 only)
-    bool glb;             // obstacle table streamed from a global workspace instead of LDS
-    long long ws_stride;  // workspace elements per instance (glb only)
-};
-
-#ifndef NMPC_MID_SLOTS
-#define NMPC_MID_SLOTS 1 // offer the 6-slot register-table kernels (13..18 provisioned rows)
-#endif
-#ifndef NMPC_SPEC_WPE_F32
-#define NMPC_SPEC_WPE_F32 3 // wavefronts per SIMD the fp32 latency kernel is compiled for (caps VGPRs at 168)
-#endif
-constexpr int kSpecWaves = 4; // wavefronts per instance in latency mode (nmpc_spec.h): automatic choice for batches up to one
-                              // workgroup per SIMD; wavefronts of the cooperative kernels
-constexpr int kSpecWavesWide = 6; // ... for batches of at most one workgroup per CU (the master + five workers: LIP + 5 candidates a round)
-constexpr int kSpecWavesMax = 8;  // most that nmpc_config.latency_waves may ask for
-constexpr size_t kLdsLimit = 160 * 1024; // bytes of LDS one workgroup may use on gfx950
-
-int round4(int x) { return (x + 3) & ~3; }
-// exchange area of a latency-kernel workgroup of W wavefronts (nmpc_spec.h: xch + command area)
-int spec_xch_elems(int W) { return round4(W * (2 * 64 + 4) + 2 * 64 * W + 8); } // (+ 8 command scalars: c, 1/max(c,1), flags, exit, gamma, 1/gamma)
-
-constexpr int kRegSlotsSmall = 4, kRegSlotsMid = 6, kRegSlotsLarge = 14; // compiled register-table sizes (rows = 3 x slots)
-// (Mid, round 5: 13..18 provisioned rows -- the reference's shipped yaml provisions 15 -- at the 168-register budget of the 4-slot
-//  kernels, three wavefronts per SIMD / four per instance in latency mode, instead of the 256-register 14-slot kernels)
-constexpr int kRegSlotsCoop = 12; // one lane per step: 8 cooperating wavefronts (2 per SIMD, 256 registers each) x 12 slots in
-                                  // registers (96 rows; 144 with helper lanes, below); the rows beyond those in LDS
-constexpr int kCoopRegWaves = 8;
-// Horizons of 33..42 steps leave 22..31 lanes of every wavefront without a step: there the kernel is compiled with helper
-// lanes (nmpc_device.h, HLP) that take a third row in each pass of two slots -- 8 x 18 = 144 rows in registers.
-bool coop_helper_lanes(int N) { return N >= 33 && N <= 42; }
-int coop_reg_rows(int N) { return kCoopRegWaves * (coop_helper_lanes(N) ? 3 * (kRegSlotsCoop / 2) : kRegSlotsCoop); }
-
-// coop_rs: layout of the cooperative register-table kernel (fp32, one lane per step): 4 x kRegSlotsCoop rows in the
-// registers of the four wavefronts, the t = 0 snapshot of all rows and the full table of the remaining rows in LDS --
-// nothing is streamed from global memory. L.rs = 0 on return if the configuration does not qualify.
-// reg64: layout of the fp64 register-table kernel (one wavefront per SIMD, 512 registers: 14 slots of 9 doubles = 252 of
-// them) -- offered for 13..42 provisioned rows and N <= 21; used for large batches where the 72-byte entries of the fp64
-// LDS table leave room for fewer than four instances per CU (nmpc_create decides).
-Layout make_layout(const nmpc_config& c, size_t elem_size, bool coop_rs = false, bool reg64 = false)
-{
-    Layout L;
-    const int N = c.N_hor;
-    L.off_rs = 18;
-    L.off_rv = L.off_rs + 3 * N;
-    L.off_c0 = L.off_rv + N;
-    L.off_c = L.off_c0 + 3 * c.Nother;
-    L.off_os = L.off_c + 3 * N * c.Nother;
-    L.off_od = L.off_os + 12 * c.Nstcobs;
-    L.off_qstc = L.off_od + 6 * (N + 1) * c.Ndynobs;
-    L.off_qdyn = L.off_qstc + N;
-    L.np = L.off_qdyn + N;
-    const int cap = c.max_active_dynobs > 0 && c.max_active_dynobs < c.Ndynobs ? c.max_active_dynobs : c.Ndynobs;
-    // fp32, three lanes per horizon step: the table entries of t >= 1 live in the registers of the one lane that reads
-    // them (nmpc_device.h, RS > 0) when the provisioned rows fit 3 x 4 or 3 x 14
-    L.rs = 0;
-    if (elem_size == 4 && c.reg_table >= 0 && N <= 21 && 64 / N >= 3 && cap > 0) {
-        if (cap <= 3 * kRegSlotsSmall) L.rs = kRegSlotsSmall;
-        else if (cap <= 3 * kRegSlotsMid && NMPC_MID_SLOTS) L.rs = kRegSlotsMid;
-        else if (cap <= 3 * kRegSlotsLarge) L.rs = kRegSlotsLarge;
-    }
-    if (elem_size == 8 && reg64 && c.reg_table >= 0 && N <= 21 && 64 / N >= 3 && cap > 3 * kRegSlotsSmall && cap <= 3 * kRegSlotsLarge)
-        L.rs = kRegSlotsLarge;
-    int left_ne = 0; // entries of the LDS table of the rows beyond the register-resident ones (cooperative register kernel)
-    if (coop_rs) {
-        L.rs = 0;
-        if (elem_size == 4 && c.reg_table >= 0 && 64 / N == 1 && cap > 0) {
-            L.rs = kRegSlotsCoop;
-            left_ne = std::max(0, cap - coop_reg_rows(N)) * (N + 1);
-        }
-    }
-    // table entries provisioned in LDS / the workspace. Register table: the t = 0 rows + the dummy row(s) -- three lanes per
-    // step: every row a pass can address (3 x slots), so that the passes read at fixed offsets without a clamp
-    int ne = L.rs ? std::max(cap + 1, coop_rs ? 0 : 3 * L.rs) : cap * (N + 1);
-    // three lanes per step, register table: the table of groups of rows with identical t = 0 snapshots (nmpc_device.h,
-    // load()) takes the place of the cooperative kernel's left-over table
-    if (L.rs && !coop_rs) left_ne = 3 * L.rs;
-    L.dyn_cap = cap;
-    L.glb = false;
-    L.ws_stride = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-    L.lds_alpha = L.glb ? 0 : nmpc::kEllStride * ne;
-    L.lds_left = L.lds_alpha + (L.glb ? 0 : round4(ne));
-    L.lds_left_alpha = L.lds_left + nmpc::kEllStride * left_ne;
-    L.lds_poly = L.lds_left_alpha + round4(left_ne);
-    L.lds_seg = L.lds_poly + 12 * (c.Nstcobs + 3); // (+3: dummy polygons behind the stored ones, nmpc_device.h load())
-    // path segments: N real ones + far-away dummies up to 2 N + 4, so that every lane can run the same number of loop trips
-    // over `first segment + 3 j` without a bound (nmpc_device.h, eval(): the segment loop)
-    const int nseg = nmpc::seg_table_len(N);
-    L.lds_seginv = L.lds_seg + 4 * nseg;
-    L.lds_fl0 = L.lds_seginv + round4(nseg);
-    L.lds_fl = L.lds_fl0 + round4(c.Nother);          // int list: robots with a non-zero t=0 position
-    L.lds_iflag = L.lds_fl + round4(c.Nother);         // int list: robots with a non-zero predicted position
-    L.lds_hist = L.lds_iflag + round4(c.Ndynobs);  // int flags / compaction map (an int fits in a T)
-    L.lds_rho = L.lds_hist + 4 * nmpc::kMem * nmpc::lbfgs_slot_stride(N); // L-BFGS ring: kMem slots x (N | 1) x (s_v, s_w, y_v, y_w)
-    L.lds_park = L.lds_rho + round4(2 * nmpc::kMem);   // rho[kMem], alpha[kMem]; then the parking area(s) (16-B aligned)
-    const int park_one = nmpc::kParkQuads * 4 * 64;    // elements per wavefront
-    L.lds_deepsc = L.lds_park + park_one;              // scalar block of a deep park (tail hand-off), throughput kernels only
-    L.lds_total = L.lds_deepsc + nmpc::kDeepScalars;
-    // latency kernel: the exchange area of W wavefronts (nmpc_spec.h) in place of the parking area (its solver vectors stay
-    // in registers): W result rows of 64 x 2 gradient entries + psi (padded to 132), the master's command area of
-    // 2 x 64 x W + 4 scalars
-    L.lds_xch = L.lds_park;
-    L.lds_total_spec = L.lds_xch + spec_xch_elems(kSpecWavesMax);
-    const int cw = coop_rs ? kCoopRegWaves : kSpecWaves;
-    L.lds_xch_coop = L.lds_park + 2 * park_one; // cooperative kernels: two shared parking areas, used alternately
-    // exchange area: 2 buffers x cw wavefronts x 2 planes x coop_lanes Quads. Global-table kernels with one lane per step keep
-    // only the lanes that carry a step (nmpc_device.h) and put the t = 0 rows of the compressed table behind it
-    L.coop_lanes = (L.glb && 64 / N == 1) ? std::min(64, round4(N)) : 64;
-    L.lds_t0c = L.lds_xch_coop + 2 * cw * 2 * 4 * L.coop_lanes;
-    L.lds_total_coop = L.lds_t0c + (L.glb ? round4((nmpc::kEllStride + 1) * cap) : 0);
-    if (coop_rs) { // no global fallback for this variant: it either fits LDS or is not offered
-        if ((size_t)L.lds_total_coop * elem_size > kLdsLimit) L.rs = 0;
-        break;
-    }
-    if (L.glb || (size_t)L.lds_total * elem_size <= kLdsLimit) break;
-    L.glb = true; // second attempt: everything but the ellipse table in LDS
-    L.rs = 0;     // (the GLB kernels index the full [row][t] table: the register-table layout does not apply)
-    left_ne = 0;
-    ne = cap * (N + 1);
-    // (room for the general table, 9 values per entry, and for the compressed one: 5 per entry + the expanded t = 0 rows)
-    L.ws_stride = (long long)(nmpc::kEllStride + 1) * ne; // (the compressed table -- 5 values per entry -- uses a prefix of it)
-    }
-    L.table_entries = ne;
-    return L;
-}
-
 } // namespace
 
 struct nmpc_handle_s {
     nmpc_config cfg;
-    Layout lay32, lay64;
-    Layout lay32c; // cooperative register-table kernel (fp32, one lane per step); rs = 0 if not available
-    Layout lay64r; // fp64 register-table kernel (three lanes per step, one wavefront per SIMD); rs = 0 if not available
-    bool use64r_auto = false; // ... chosen automatically for large batches (the LDS table allows < 4 instances per CU)
-    int lps;
+    Layouts lays;  // the four layouts and lanes per step (nmpc_plan.h)
     int n_simd = 0; // SIMDs of the device (4 per CU): latency_waves = 0 picks the wavefront count from B / n_simd
     bool spec_ok[2] = {true, true}; // [f32, f64]
     bool coop_ok[2] = {true, true};
@@ -238,7 +102,7 @@ struct nmpc_handle_s {
     template <typename T>
     const Layout& lay() const
     {
-        return sizeof(T) == 4 ? lay32 : lay64;
+        return lays.main(sizeof(T));
     }
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -265,13 +129,6 @@ struct nmpc_handle_s {
 
 namespace {
 
-// second launch-bound argument = minimum waves per SIMD; it caps the register allocation (512 / waves)
-#ifndef NMPC_WPE_F32
-#define NMPC_WPE_F32 3 // throughput kernel, table in LDS / global memory (133 VGPRs; one spill short of fitting 128)
-#endif
-#ifndef NMPC_WPE_F64
-#define NMPC_WPE_F64 2
-#endif
 // waves per SIMD a kernel variant is compiled for: the large register table needs the 256-register budget
 template <typename T, int RS>
 constexpr int wpe(int f32_default)
@@ -283,7 +140,7 @@ template <typename T, int LPS, int RS>
 constexpr bool kHasAxisVariant = LPS == 3 && RS > 0;
 
 // ONLY: 1 / 2 = the axis-aligned / the general path alone, returning at once when the launch takes the other one -- how every
-// register-table kernel is built and launched since round 4 (pick_solve below). (0 = both paths inlined into one kernel,
+// register-table kernel is built and launched since round 4 (solve_kernel_of below). (0 = both paths inlined into one kernel,
 // chosen per workgroup: round 3's fp32 form, no longer instantiated. In fp64 that form never worked: the 512-register
 // kernel computed garbage on the general path, nondeterministically, while each path compiled alone is right -- it was
 // 142 KB of code, beyond the +-128 KB reach of s_cbranch, its far branches relaxed into s_getpc / s_setpc sequences;
@@ -757,102 +614,85 @@ using SolveFn = void (*)(nmpc::KParams<T>);
 template <typename T>
 using EvalFn = void (*)(nmpc::KParams<T>, nmpc::EvalParams<T>);
 
-// the register-table variants exist for float with three lanes per step only
-void (*pick_solve_coop_reg(int N))(nmpc::KParams<float>)
+// ---- variant -> kernel: the one place that names the instantiations -------------------------------------------------------
+// f(lanes per step) / f(register-table slots) with the run-time value as a compile-time constant
+template <int I>
+using IC = std::integral_constant<int, I>;
+template <typename F>
+auto with_lps(int lps, F f)
 {
-    return coop_helper_lanes(N) ? solve_coop_reg_kernel<true> : solve_coop_reg_kernel<false>;
+    return lps == 3 ? f(IC<3>{}) : lps == 2 ? f(IC<2>{}) : f(IC<1>{});
 }
-
-// (the register-table variants exist for float with three lanes per step only)
-// The register-table kernels come as PAIRS since round 4 -- <.., 1> = the axis-aligned path alone, <.., 2> = the general
-// (rotated-ellipse) path alone, launched one behind the other, each workgroup of the twin that the device-side flag does
-// not pick returning before it touches anything. One kernel with both paths inlined (round 3) reported its resources as
-// the maximum over both -- 19-22 spilled VGPRs and 52-88 B of scratch that only the general path has -- and had grown to
-// 125 KB of code, against the 128 KB reach of s_cbranch. `only` = 1 / 2 picks the member.
-template <typename T>
-SolveFn<T> pick_solve(int lps, bool glb, int rs = 0, int only = 1)
-{
-    if constexpr (sizeof(T) == 4)
-    {
-        if (rs == kRegSlotsSmall && lps == 3 && !glb)
-            return only == 2 ? solve_kernel<T, 3, false, kRegSlotsSmall, 2> : solve_kernel<T, 3, false, kRegSlotsSmall, 1>;
-        if (rs == kRegSlotsMid && lps == 3 && !glb)
-            return only == 2 ? solve_kernel<T, 3, false, kRegSlotsMid, 2> : solve_kernel<T, 3, false, kRegSlotsMid, 1>;
-    }
-    if (rs == kRegSlotsLarge && lps == 3 && !glb)
-        return only == 2 ? solve_kernel<T, 3, false, kRegSlotsLarge, 2> : solve_kernel<T, 3, false, kRegSlotsLarge, 1>;
-    if (glb) return lps == 3 ? solve_kernel<T, 3, true> : lps == 2 ? solve_kernel<T, 2, true> : solve_kernel<T, 1, true>;
-    return lps == 3 ? solve_kernel<T, 3, false> : lps == 2 ? solve_kernel<T, 2, false> : solve_kernel<T, 1, false>;
-}
-template <typename T>
-SolveFn<T> pick_solve_spec(int lps, bool glb, int rs = 0, int only = 1)
+template <typename T, typename F>
+auto with_reg_slots(int rs, F f) // (fp64 has the 14-slot table only)
 {
     if constexpr (sizeof(T) == 4) {
-        if (rs == kRegSlotsSmall && lps == 3 && !glb)
-            return only == 2 ? solve_spec_kernel<T, 3, false, kRegSlotsSmall, 2> : solve_spec_kernel<T, 3, false, kRegSlotsSmall, 1>;
-        if (rs == kRegSlotsMid && lps == 3 && !glb)
-            return only == 2 ? solve_spec_kernel<T, 3, false, kRegSlotsMid, 2> : solve_spec_kernel<T, 3, false, kRegSlotsMid, 1>;
-        if (rs == kRegSlotsLarge && lps == 3 && !glb)
-            return only == 2 ? solve_spec_kernel<T, 3, false, kRegSlotsLarge, 2> : solve_spec_kernel<T, 3, false, kRegSlotsLarge, 1>;
+        if (rs == kRegSlotsSmall) return f(IC<kRegSlotsSmall>{});
+        if (rs == kRegSlotsMid) return f(IC<kRegSlotsMid>{});
     }
-    if (glb) return lps == 3 ? solve_spec_kernel<T, 3, true> : lps == 2 ? solve_spec_kernel<T, 2, true> : solve_spec_kernel<T, 1, true>;
-    return lps == 3 ? solve_spec_kernel<T, 3, false> : lps == 2 ? solve_spec_kernel<T, 2, false> : solve_spec_kernel<T, 1, false>;
+    return f(IC<kRegSlotsLarge>{});
 }
 
-// The tail member of the fp32 register-table kernels (nmpc_config.tail_latency): the latency kernel with the throughput
-// kernels' evaluation; nullptr where there is none.
+// The kernel of a variant (nmpc_plan.h); member = 1 / 2 of a pair -- nullptr for the second member of a variant that is
+// not one, and for a family of the other signature.
 template <typename T>
-SolveFn<T> pick_solve_tail(int lps, bool glb, int rs, int only)
+SolveFn<T> solve_kernel_of(const Variant& v, int member = 1)
 {
-    if constexpr (sizeof(T) == 4) {
-        if (lps != 3 || glb) return nullptr;
-        if (rs == kRegSlotsSmall)
-            return only == 2 ? solve_spec_kernel<T, 3, false, kRegSlotsSmall, 2, false> : solve_spec_kernel<T, 3, false, kRegSlotsSmall, 1, false>;
-        if (rs == kRegSlotsMid)
-            return only == 2 ? solve_spec_kernel<T, 3, false, kRegSlotsMid, 2, false> : solve_spec_kernel<T, 3, false, kRegSlotsMid, 1, false>;
-        if (rs == kRegSlotsLarge)
-            return only == 2 ? solve_spec_kernel<T, 3, false, kRegSlotsLarge, 2, false> : solve_spec_kernel<T, 3, false, kRegSlotsLarge, 1, false>;
+    using Fn = SolveFn<T>;
+    const bool second = member == 2, tail = v.family == kLatencyTail;
+    if (second && !v.pair) return nullptr;
+    switch (v.family) {
+    case kThroughput:
+        if (v.pair) return with_reg_slots<T>(v.rs, [&](auto r) -> Fn { return second ? solve_kernel<T, 3, false, r(), 2> : solve_kernel<T, 3, false, r(), 1>; });
+        return with_lps(v.lps, [&](auto l) -> Fn { return v.glb ? solve_kernel<T, l(), true> : solve_kernel<T, l(), false>; });
+    case kLatencyFlat:
+    case kLatencyTail: // (the register-table members, and with them the tail members, exist in fp32 only)
+        if constexpr (sizeof(T) == 4)
+            if (v.pair)
+                return with_reg_slots<T>(v.rs, [&](auto r) -> Fn {
+                    if (tail) return second ? solve_spec_kernel<T, 3, false, r(), 2, false> : solve_spec_kernel<T, 3, false, r(), 1, false>;
+                    return second ? solve_spec_kernel<T, 3, false, r(), 2> : solve_spec_kernel<T, 3, false, r(), 1>;
+                });
+        if (tail) return nullptr;
+        return with_lps(v.lps, [&](auto l) -> Fn { return v.glb ? solve_spec_kernel<T, l(), true> : solve_spec_kernel<T, l(), false>; });
+    case kCoop:
+        return with_lps(v.lps, [&](auto l) -> Fn {
+            return !v.glb ? solve_coop_kernel<T, l(), false> : second ? solve_coop_kernel<T, l(), true, 2> : solve_coop_kernel<T, l(), true, 1>;
+        });
+    case kCoopOnChip:
+        if constexpr (sizeof(T) == 4) return v.hlp ? solve_coop_reg_kernel<true> : solve_coop_reg_kernel<false>;
+        return nullptr;
+    default:
+        return nullptr;
     }
-    return nullptr;
 }
-
-// (global table: `only` = 1 the compressed-table member of the pair, 2 the general one)
 template <typename T>
-SolveFn<T> pick_solve_coop(int lps, bool glb, int only = 2)
+EvalFn<T> eval_kernel_of(const Variant& v, int member = 1)
 {
-    if (glb && only == 1) return lps == 3 ? solve_coop_kernel<T, 3, true, 1> : lps == 2 ? solve_coop_kernel<T, 2, true, 1> : solve_coop_kernel<T, 1, true, 1>;
-    if (glb) return lps == 3 ? solve_coop_kernel<T, 3, true, 2> : lps == 2 ? solve_coop_kernel<T, 2, true, 2> : solve_coop_kernel<T, 1, true, 2>;
-    return lps == 3 ? solve_coop_kernel<T, 3, false> : lps == 2 ? solve_coop_kernel<T, 2, false> : solve_coop_kernel<T, 1, false>;
-}
-
-template <typename T>
-EvalFn<T> pick_eval(int lps, bool glb, int rs = 0, int only = 1)
-{
-    if constexpr (sizeof(T) == 4)
-    {
-        if (rs == kRegSlotsSmall && lps == 3 && !glb)
-            return only == 2 ? eval_kernel<T, 3, false, kRegSlotsSmall, 2> : eval_kernel<T, 3, false, kRegSlotsSmall, 1>;
-        if (rs == kRegSlotsMid && lps == 3 && !glb)
-            return only == 2 ? eval_kernel<T, 3, false, kRegSlotsMid, 2> : eval_kernel<T, 3, false, kRegSlotsMid, 1>;
-    }
-    if (rs == kRegSlotsLarge && lps == 3 && !glb)
-        return only == 2 ? eval_kernel<T, 3, false, kRegSlotsLarge, 2> : eval_kernel<T, 3, false, kRegSlotsLarge, 1>;
-    if (glb) return lps == 3 ? eval_kernel<T, 3, true> : lps == 2 ? eval_kernel<T, 2, true> : eval_kernel<T, 1, true>;
-    return lps == 3 ? eval_kernel<T, 3, false> : lps == 2 ? eval_kernel<T, 2, false> : eval_kernel<T, 1, false>;
-}
-
-template <typename T>
-EvalFn<T> pick_eval_coop(int lps, bool glb, int only = 2)
-{
+    using Fn = EvalFn<T>;
     constexpr int W = kSpecWaves;
-    if (glb && only == 1) return lps == 3 ? eval_coop_kernel<T, 3, true, 0, false, W, 1> : lps == 2 ? eval_coop_kernel<T, 2, true, 0, false, W, 1> : eval_coop_kernel<T, 1, true, 0, false, W, 1>;
-    if (glb) return lps == 3 ? eval_coop_kernel<T, 3, true, 0, false, W, 2> : lps == 2 ? eval_coop_kernel<T, 2, true, 0, false, W, 2> : eval_coop_kernel<T, 1, true, 0, false, W, 2>;
-    return lps == 3 ? eval_coop_kernel<T, 3, false, 0, false, W> : lps == 2 ? eval_coop_kernel<T, 2, false, 0, false, W> : eval_coop_kernel<T, 1, false, 0, false, W>;
+    const bool second = member == 2;
+    if (second && !v.pair) return nullptr;
+    switch (v.family) {
+    case kEval:
+        if (v.pair) return with_reg_slots<T>(v.rs, [&](auto r) -> Fn { return second ? eval_kernel<T, 3, false, r(), 2> : eval_kernel<T, 3, false, r(), 1>; });
+        return with_lps(v.lps, [&](auto l) -> Fn { return v.glb ? eval_kernel<T, l(), true> : eval_kernel<T, l(), false>; });
+    case kEvalCoop:
+        return with_lps(v.lps, [&](auto l) -> Fn {
+            return !v.glb ? eval_coop_kernel<T, l(), false, 0, false, W> : second ? eval_coop_kernel<T, l(), true, 0, false, W, 2> : eval_coop_kernel<T, l(), true, 0, false, W, 1>;
+        });
+    case kEvalCoopOnChip:
+        if constexpr (sizeof(T) == 4)
+            return v.hlp ? eval_coop_kernel<float, 1, false, kRegSlotsCoop, true, kCoopRegWaves> : eval_coop_kernel<float, 1, false, kRegSlotsCoop, false, kCoopRegWaves>;
+        return nullptr;
+    default:
+        return nullptr;
+    }
 }
-EvalFn<float> pick_eval_coop_reg(int N)
+// diagnostic kernel of nmpc_solve_trace_f64
+SolveFn<double> trace_kernel_of(int lps, bool glb)
 {
-    return coop_helper_lanes(N) ? eval_coop_kernel<float, 1, false, kRegSlotsCoop, true, kCoopRegWaves>
-                                : eval_coop_kernel<float, 1, false, kRegSlotsCoop, false, kCoopRegWaves>;
+    return with_lps(lps, [&](auto l) -> SolveFn<double> { return glb ? trace_kernel<l(), true> : trace_kernel<l(), false>; });
 }
 
 // stage `count` elements: returns the device pointer to use (src itself if already on the device)
@@ -890,212 +730,60 @@ int stage_out(nmpc_handle_s* h, DevBuf& buf, T* dst, size_t count, T** dev, bool
     return 0;
 }
 
-// ---- kernel choice and launch ---------------------------------------------------------------------------------------
-// (development builds, -DNMPC_DEV_ENV: the batch-size thresholds of the resumable solve / the tail hand-off, in device fills, from
-//  the environment -- tools/exp_mid_batches.py; the shipped library has the constants)
+// ---- the solve plan (nmpc_plan.h) and its execution ---------------------------------------------------------------------
+// (development builds, -DNMPC_DEV_ENV: the thresholds of PlanTuning from the environment -- tools/exp_mid_batches.py,
+//  tools/exp_cfg1_proxy_order.py; the shipped library has the constants)
 #ifdef NMPC_DEV_ENV
-static double dev_factor(const char* name, double dflt)
+static double dev_env(const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; }
+static PlanTuning plan_tuning()
 {
-    const char* s = getenv(name);
-    return s ? atof(s) : dflt;
+    const PlanTuning d;
+    return {dev_env("NMPC_PROXY_ORDER", d.proxy_order), dev_env("NMPC_PROXY_FILLS", d.proxy_fills), dev_env("NMPC_PROXY_VNOM", d.proxy_vnom),
+            dev_env("NMPC_STAGE_FILLS", d.stage_fills), dev_env("NMPC_TAIL_FILLS", d.tail_fills), dev_env("NMPC_TAIL_WAVES", d.tail_waves),
+            dev_env("NMPC_TAIL_MINB", d.tail_min_parks)};
 }
 #else
-static constexpr double dev_factor(const char*, double dflt) { return dflt; }
+static PlanTuning plan_tuning() { return PlanTuning(); }
 #endif
-// Batch size, in device fills of the planned kernel, from which the resumable solve (pilot + ranking) and the tail hand-off are
-// used. fp32 register-table kernels: ONE fill -- measured at configs[1]'s and configs[2]'s dimensions on three families
-// (tools/exp_mid_batches.py, profiles/r06_exp_mid_batches.txt: batches of 1-4 fills, what a closed-loop evaluation sends once
-// most scenarios have finished, -15..-35 %; until round 6 both started at four fills). Everything else: four, as measured
-// in rounds 3-4 (fp64 and the LDS-table kernels have no tail member and were not re-measured).
-constexpr double kStageFills = 4, kTailFills = 4, kStageFillsReg = 1, kTailFillsReg = 1;
-// 14-slot kernels (2 048 resident wavefronts): already from 0.7 fills on -- B = 1 500 at configs[2]'s dimensions: `passing` 42.0 ->
-// 27.2 ms, reference scenarios 31.0 -> 32.5, contract family 62.2 -> 50.5; at 1 024 the contract family still loses 20 % to two
-// wavefronts per instance, and at configs[1]'s dimensions (4-slot kernels) it does so up to a full fill (same record).
-constexpr double kFillsLarge = 0.7;
-constexpr double kProxyFills = 8;     // throughput plans below this many fills: dispatch order from one evaluation instead of a pilot launch
-constexpr double kTailMinParks = 5;   // the hand-off needs a batch of at least this many parking thresholds (8 until the above)
 
 template <typename T>
-struct Plan {
-    SolveFn<T> fn = nullptr, fn2 = nullptr; // fn2: the general-path member of a register-table kernel pair (fn = the axis-aligned one)
-    bool has_axis = false; // the kernel contains the axis-aligned variant (KParams::axis_mode)
-    int threads = 64;
-    size_t lds_bytes = 0;
-    int mode = 0;          // 0 throughput, 1 latency (speculative), 2 cooperative
-    bool uses_ws = false;  // the variant reads the global obstacle workspace
-    bool stageable = false;
-    int resident = 0;      // cooperative kernels: workgroups resident at once (0 = derived from the one-wavefront layout)
-};
-
-// Which solve kernel runs a batch of B instances (measured crossovers). May re-fill `k` with the layout of the
-// on-chip cooperative kernel (the batch buffers are kept).
-template <typename T>
-Plan<T> plan_solve(nmpc_handle_s* h, int B, nmpc::KParams<T>& k)
+PlanStatic plan_static(const nmpc_handle_s* h)
 {
-    const Layout& L = h->lay<T>();
-    Plan<T> pl;
-    // wavefronts per instance: 0 = throughput kernel; > 0 = latency kernel (pays off while the batch leaves SIMDs idle)
-    int lw = h->cfg.latency_waves;
-    // fp64 runs 2 wavefronts per SIMD (256 VGPRs) against 3 in fp32, so fewer 4-wavefront workgroups are resident
-    const int cap = sizeof(T) == 4 ? h->n_simd : h->n_simd / 2;
-    if (lw == 0) {
-        // one workgroup per SIMD or less: four wavefronts per instance. (Round 2 measured W = 3 -- what stays resident
-        // together at 168 registers -- ahead of W = 4, 28.5 k against 25.1 k solves/s on configs[1]; since the resumable
-        // solve starts the long instances first, the quarter of the workgroups that has to wait for a slot is the short
-        // ones and the faster line search of the long ones wins: 41.8 k (W = 4) against 40.0 k (W = 3) and 35.4 k (W = 2),
-        // `passing` 46.6 / 41.8 / 34.7 k -- profiles/r04_exp_cfg1_waves.txt. Results do not depend on W, bit for bit.)
-        lw = B <= cap ? (sizeof(T) == 4 ? (L.rs >= kRegSlotsLarge ? (4 * B <= 3 * h->n_simd ? kSpecWaves : 2) : kSpecWaves) : kSpecWaves) : B <= 4 * cap ? 2 : 1;
-        // (14-slot kernels, 2 048 resident wavefronts: until round 6 two wavefronts per instance at every size. Measured at
-        //  configs[2]'s dimensions on three families, W = 2 / 3 / 4 / 6 -- profiles/r06_exp_mid_batches.txt: B = 64 / 256 six
-        //  wavefronts -32..-35 %; B = 512 / 768 four -25..-30 % on `passing` and the reference scenarios, -31 % / +3 % on the
-        //  contract family; at B = 1 024 four still win 27-30 % on the first two but lose 14 % on the contract family: two.)
-        // (14-slot kernels, two wavefronts per SIMD: from 0.7 device fills on -- 1 434 instances, kFillsLarge -- the throughput kernels with
-        //  the resumable solve and the tail hand-off are ahead of two wavefronts per instance: configs[2]'s dimensions,
-        //  B = 2 100 / 3 200 / 4 096: `passing` 34.5 / 50.7 / 43.8 -> 22.3 / 30.3 / 28.3 ms, reference scenarios 40.0 / 49.7 /
-        //  50.3 -> 37.4 / 38.6 / 39.5, contract family 73.6 / 94.2 / ~100 -> 56.2 / 70.2 / 87.1; below a fill the two are
-        //  level. The 4- and 6-slot kernels keep the latency plan up to 4 096: level or ahead there. tools/exp_mid_batches.py)
-        if (sizeof(T) == 4 && L.rs >= kRegSlotsLarge && !L.glb && B >= kFillsLarge * 2 * cap) lw = 1;
-        // At most one workgroup per CU (what a fleet's real-time loop sends: a handful of robots): six wavefronts -- the master
-        // and five workers, the Lipschitz evaluation + five candidates in the first round of an iteration (1.3 instead of 1.6-1.8
-        // rounds per iteration on the long instances). B = 64 / 256: 23.4 -> 21.8 / 18.5 -> 17.3 ms; from two workgroups per CU
-        // on (B = 512) six or eight wavefronts cost more than they bring
-        // (profiles/r04_exp_cfg1_batch_size_and_up_to_8_wavefronts.txt). Same results, bit for bit.
-        // (the 4-slot register table only: what was measured, and what nmpc_hip.h documents -- ADVICE r4)
-        // (the 6-slot table, same register budget: measured too -- B = 64 / 256: 22.98 -> 21.37 / 18.12 -> 16.96 ms, tools/exp_mid_w6.py;
-        //  the 14-slot table: round 6, below)
-        if (sizeof(T) == 4 && L.rs > 0 && !L.glb && 4 * B <= h->n_simd) lw = kSpecWavesWide;
-        // Large batches whose LDS tables allow only a few workgroups per CU (e.g. 40 active obstacle rows: 35 KB,
-        // 4 per CU = one wavefront per SIMD): the wavefronts of a latency-kernel workgroup SHARE the instance's
-        // tables, so W of them fill the SIMDs that the throughput kernel leaves empty (measured on configs[2]:
-        // 16.4 k -> 24.0 k solves/s with W = 3). Smallest W that reaches the resident-wavefront limit, if that is
-        // at least 1.5x what the throughput kernel gets.
-        // Obstacle table streamed from the global workspace (GLB): the wavefronts of a workgroup read the same
-        // 236 KB at about the same time, so speculation rides on cache hits (configs[4]: 1.31 k -> 1.58 k solves/s)
-        if (L.glb) lw = kSpecWaves;
-        // resident wavefronts per CU: register budget of the kernel variant (wpe<>) x 4 SIMDs, capped by LDS
-        const bool f32 = sizeof(T) == 4;
-        const int wpe_tp = !f32 ? NMPC_WPE_F64 : L.rs >= kRegSlotsLarge ? 2 : L.rs > 0 ? 3 : NMPC_WPE_F32;
-        const int wpe_sp = !f32 ? NMPC_WPE_F64 : L.rs >= kRegSlotsLarge ? 2 : NMPC_SPEC_WPE_F32;
-        const size_t elem = sizeof(T);
-        const int tp = std::min<int>(4 * wpe_tp, (int)(kLdsLimit / ((size_t)L.lds_total * elem)));
-        const int wg_spec = (int)(kLdsLimit / ((size_t)(L.lds_xch + spec_xch_elems(kSpecWaves)) * elem));
-        int best = tp;
-        for (int w = std::max(lw, 2); w <= kSpecWaves; ++w) {
-            const int res = std::min(4 * wpe_sp / w, wg_spec) * w;
-            if (2 * res >= 3 * tp && res > best) {
-                best = res;
-                lw = w;
-            }
-        }
-    }
-    int waves = lw == 1 ? 0 : lw < 0 ? 1 : lw > kSpecWavesMax ? kSpecWavesMax : lw;
-    if (!h->spec_ok[sizeof(T) == 4 ? 0 : 1]) waves = 0;
-    // cooperative evaluation (nmpc_config.coop_waves): explicit request, or automatic where the obstacle table is streamed
-    // from global memory (configs[4]: the obstacle loop is 94 % of the time and its rows split cleanly over the
-    // wavefronts). Needs the LDS / global table (not the register table), room for the exchange area and no wall-clock
-    // budget (each wavefront would read its own clock).
-    int coop = h->cfg.coop_waves > kSpecWaves ? kSpecWaves : h->cfg.coop_waves;
-    if (coop == 0) coop = (L.glb && h->cfg.latency_waves == 0) ? kSpecWaves : 1;
-    if (L.rs > 0 || h->cfg.max_solver_time_us > 0 || !h->coop_ok[sizeof(T) == 4 ? 0 : 1]) coop = 1;
-    // (latency kernel: the exchange area by the W actually launched -- about half of the 8-wavefront maximum at W = 4)
-    pl.lds_bytes = (size_t)(waves ? L.lds_xch + spec_xch_elems(waves) : L.lds_total) * sizeof(T);
-    pl.fn = waves ? pick_solve_spec<T>(h->lps, L.glb, L.rs) : pick_solve<T>(h->lps, L.glb, L.rs);
-    pl.has_axis = L.rs > 0 && h->lps == 3 && !L.glb;
-    if (pl.has_axis) pl.fn2 = waves ? pick_solve_spec<T>(h->lps, L.glb, L.rs, 2) : pick_solve<T>(h->lps, L.glb, L.rs, 2);
-    // nmpc_config.batch_invariant: the latency plan on the TAIL members -- the throughput kernels' evaluation, hence their bits.
-    // Automatic (0): the 14-slot kernels. There the gated form is also the faster one on everything but the contract family
-    // (configs[2]'s dimensions, B = 1 .. 1 300: `passing` -8..-20 %, the reference scenarios -26..+1 %, the corridor family
-    // -18..+19 %, one instance alone -7..-17 % on all four families; the contract family -15..+20 % --
-    // profiles/r06_exp_mid_batches.txt); the 4- / 6-slot kernels keep the flat form configs[1] is quoted on.
-    if (waves && (h->cfg.batch_invariant > 0 || (h->cfg.batch_invariant == 0 && L.rs >= kRegSlotsLarge)))
-        if (SolveFn<T> tf = pick_solve_tail<T>(h->lps, L.glb, L.rs, 1)) {
-            pl.fn = tf;
-            if (pl.has_axis) pl.fn2 = pick_solve_tail<T>(h->lps, L.glb, L.rs, 2);
-        }
-    pl.uses_ws = L.glb;
-    if (coop > 1) {
-        // global table: the pair (compressed table of axis-aligned ellipses / general table); LDS table: one kernel
-        pl.fn = pick_solve_coop<T>(h->lps, L.glb, L.glb ? 1 : 2);
-        pl.fn2 = L.glb ? pick_solve_coop<T>(h->lps, true, 2) : nullptr;
-        pl.has_axis = L.glb;
-        pl.lds_bytes = (size_t)L.lds_total_coop * sizeof(T);
-        k.lds_xch = L.lds_xch_coop;
-        waves = coop;
-        if constexpr (sizeof(T) == 4) {
-            // the register-table variant is available (automatic / 4-wavefront request): eight wavefronts hold the table,
-            // nothing is streamed from global memory
-            if (coop == kSpecWaves && h->lay32c.rs > 0 && h->lps == 1) {
-                waves = kCoopRegWaves;
-                const Layout& C = h->lay32c;
-                fill_layout(k, C);
-                k.lds_xch = C.lds_xch_coop;
-                pl.fn = pick_solve_coop_reg(h->cfg.N_hor);
-                pl.fn2 = nullptr;
-                pl.has_axis = false;
-                pl.lds_bytes = (size_t)C.lds_total_coop * sizeof(T);
-                pl.uses_ws = false;
-            }
-        }
-    }
-    if constexpr (sizeof(T) == 8) {
-        // fp64, three lanes per step, 13..42 rows: the register-table kernel (one wavefront per SIMD, four instances per CU)
-        // where the LDS table leaves room for fewer -- measured on configs[2]'s dimensions: ahead of the latency kernel
-        // from B = 1024 on (97 vs 122 ms; 500 vs 696 ms at 8192), behind it below; never ahead for <= 12 rows, whose LDS
-        // table is small. reg_table = 1 forces it (tests), -1 switches it off.
-        const bool wanted = h->cfg.reg_table > 0 || (h->use64r_auto && B >= 2 * cap && h->cfg.latency_waves <= 1);
-        if (h->lay64r.rs > 0 && coop <= 1 && h->cfg.latency_waves <= 1 && wanted) {
-            const Layout& R = h->lay64r;
-            fill_layout(k, R);
-            waves = 0;
-            pl.fn = pick_solve<T>(h->lps, false, R.rs);
-            pl.fn2 = pick_solve<T>(h->lps, false, R.rs, 2);
-            pl.lds_bytes = (size_t)R.lds_total * sizeof(T);
-            pl.has_axis = true;
-            pl.uses_ws = false;
-            pl.resident = h->n_simd;
-        }
-    }
-    pl.threads = waves ? 64 * waves : 64;
-    pl.mode = coop > 1 ? 2 : waves ? 1 : 0;
-    pl.stageable = h->cfg.max_solver_time_us <= 0; // (every kernel family parks / resumes; a wall-clock budget does not survive it)
-    if (pl.mode == 2) { // cooperative kernels: workgroups resident on the device (LDS-bound; one per CU for the on-chip variant)
-        const int per_cu = std::max<int>(1, (int)(kLdsLimit / std::max<size_t>(pl.lds_bytes, 1)));
-        pl.resident = std::min(per_cu, std::max(1, 8 / (pl.threads / 64))) * (h->n_simd / 4);
-    }
-    return pl;
+    const int i = sizeof(T) == 4 ? 0 : 1;
+    return {&h->cfg, &h->lays, sizeof(T), h->n_simd, h->spec_ok[i], h->coop_ok[i]};
 }
 
-// one launch of the planned kernel over `grid` workgroups
+// point `k` at the layout and the global workspace of a kernel choice (the batch buffers and solver options are kept)
 template <typename T>
-int launch_plan(nmpc_handle_s* h, const Plan<T>& pl, const nmpc::KParams<T>& k, int grid, hipStream_t stream = nullptr, bool own = true)
+int bind_choice(nmpc_handle_s* h, const KernelChoice& kc, nmpc::KParams<T>& k, int B)
 {
-    if (own) stream = h->stream;
-    if (grid <= 0) return 0;
-    if (!pl.fn2 || k.axis_mode != 0) { // (axis_mode 0 = the general path only: the axis-only kernel of a pair has nothing to do)
-        hipLaunchKernelGGL(pl.fn, dim3(grid), dim3(pl.threads), pl.lds_bytes, stream, k);
-        HIP_TRY(hipGetLastError());
-    }
-    if (pl.fn2 && k.axis_mode != 1) {
-        hipLaunchKernelGGL(pl.fn2, dim3(grid), dim3(pl.threads), pl.lds_bytes, stream, k);
-        HIP_TRY(hipGetLastError());
+    if (kc.use != kLayMain) fill_layout(k, *kc.L);
+    if (kc.coop) k.lds_xch = kc.L->lds_xch_coop;
+    k.ws = nullptr;
+    k.ws_stride = 0;
+    if (kc.uses_ws) { // (only the variants that stream the obstacle table reserve the global workspace)
+        if (int rc = h->dws.reserve((size_t)B * kc.L->ws_stride * sizeof(T))) return rc;
+        k.ws = static_cast<T*>(h->dws.p);
+        k.ws_stride = kc.L->ws_stride;
     }
     return 0;
 }
 
-// the tail member that goes with a throughput plan (fn == nullptr: none -- other kernel family, fp64, LDS / global table)
-template <typename T>
-Plan<T> plan_tail(nmpc_handle_s* h, const Plan<T>& pl, const Layout& L, int waves)
+// one launch of a kernel choice over `grid` workgroups (solve kernels: no `ep`; evaluation kernels: one). Of a pair, the
+// member whose path KParams::axis_mode rules out -- 0: the general path only, 1: the axis-aligned only -- is not launched.
+template <typename T, typename... Ep>
+int launch_choice(nmpc_handle_s* h, const KernelChoice& kc, int grid, const nmpc::KParams<T>& k, const Ep&... ep)
 {
-    Plan<T> t;
-    if (pl.mode != 0 || pl.uses_ws || !h->spec_ok[sizeof(T) == 4 ? 0 : 1]) return t;
-    t.fn = pick_solve_tail<T>(h->lps, L.glb, L.rs, 1);
-    if (!t.fn) return t;
-    t.fn2 = pl.has_axis ? pick_solve_tail<T>(h->lps, L.glb, L.rs, 2) : nullptr;
-    t.has_axis = pl.has_axis;
-    t.threads = 64 * waves;
-    t.lds_bytes = (size_t)(L.lds_xch + spec_xch_elems(waves)) * sizeof(T);
-    t.mode = 1;
-    return t;
+    if (grid <= 0) return 0;
+    for (int member = 1; member <= (kc.variant.pair ? 2 : 1); ++member) {
+        if (kc.variant.pair && k.axis_mode == member - 1) continue;
+        if constexpr (sizeof...(Ep) == 0)
+            hipLaunchKernelGGL(solve_kernel_of<T>(kc.variant, member), dim3(grid), dim3(kc.threads), kc.lds_bytes, h->stream, k);
+        else
+            hipLaunchKernelGGL(eval_kernel_of<T>(kc.variant, member), dim3(grid), dim3(kc.threads), kc.lds_bytes, h->stream, k, ep...);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
 }
 
 // How the axis-aligned variant takes part in a call over B instances at P (device): sets k.axis_mode to 0 (general only),
@@ -1123,89 +811,43 @@ int prepare_axis(nmpc_handle_s* h, bool has_axis, nmpc::KParams<T>& k, int B)
     return 0;
 }
 
-// Solve B instances whose buffers (all on the device) are in `k`: kernel choice, the axis-aligned twin, the two-launch
-// resumable solve. `allow_staging`: the caller's status array may be used for the in-progress marker.
+// Solve B instances whose buffers (all on the device) are in `k`: asks nmpc_plan.h for the plan and carries it out -- the
+// axis scan, the dispatch order from one evaluation, the stages of the resumable solve with the ranking behind each, the
+// tail hand-off. `allow_staging`: the caller's status array may be used for the in-progress marker.
 template <typename T>
 int run_solve(nmpc_handle_s* h, nmpc::KParams<T>& k, int B, bool allow_staging)
 {
-    const Layout& L = h->lay<T>();
-    Plan<T> pl = plan_solve<T>(h, B, k);
-    if (pl.uses_ws) {
-        if (int rc_ = h->dws.reserve((size_t)B * L.ws_stride * sizeof(T))) return rc_;
-        k.ws = static_cast<T*>(h->dws.p);
-        k.ws_stride = L.ws_stride;
-    } else {
-        k.ws = nullptr;
-        k.ws_stride = 0;
-    }
-    if (int rc = prepare_axis<T>(h, pl.has_axis, k, B)) return rc;
-    h->last_mode = pl.mode;
-    h->last_axis = pl.has_axis ? k.axis_mode : -1;
-    h->last_order = k.order ? 1 : 0;
-    // Resumable solve: up to two stage boundaries (outer-iteration count, ranking key of the launch that follows).
-    //  * first (nmpc_config.staged, ranked by ||F2||) -- the instances whose hard constraints are still violated after the
-    //    first inner solve are the ones that will run into the iteration caps. Automatic (one outer iteration) for
-    //    batches that fill the device at least four times over with the one-wavefront kernel: started first, the long
-    //    solves no longer end the launch alone (configs[2] `passing`: 156 -> 121 ms); and for the latency kernel with
-    //    about one workgroup per SIMD, where every workgroup is resident at once and the order decides which long solves
-    //    share a SIMD to the end (configs[1]: 32.6 -> 28.5 ms; costs ~1.5 ms where most instances converge early).
-    //  * second (nmpc_config.staged_evals, ranked by the evaluations used so far) -- explicit only: every boundary is a
-    //    barrier (each stage ends with ITS longest instance), and late boundaries lost more to that than the better
-    //    ranking returned in every measurement (tools/exp_cfg1_order2.py, tools/sim_stages.py).
-    int caps[2] = {h->cfg.staged, h->cfg.staged_evals};
-    const int wpe_tp = sizeof(T) == 8 ? NMPC_WPE_F64 : L.rs >= kRegSlotsLarge ? 2 : L.rs > 0 ? 3 : NMPC_WPE_F32;
-    const int resident = std::max(1, std::min<int>(wpe_tp * h->n_simd,
-                                                   (int)(kLdsLimit / ((size_t)L.lds_total * sizeof(T))) * (h->n_simd / 4)));
-    const int lat_cap = sizeof(T) == 4 ? h->n_simd : h->n_simd / 2;
-    const bool reg32 = sizeof(T) == 4 && L.rs > 0 && !L.glb;
-    // Latency plan at about one workgroup per SIMD (configs[1]): the order decides which long solves share a SIMD to the end.
-    // Until round 6 a pilot launch ranked them (32.6 -> 28.5 ms then); the barrier and the second launch cost ~1.3 ms of
-    // 20, and an order from ONE evaluation -- ||F2||^2 at the nominal controls (2/3 v_max, 0), ~20 us -- does as well on the
-    // contract family below full oversubscription (B = 600 / 800: 21.5 -> 20.1 / 20.4 ms) and needs no barrier: `passing` -5..-7 %,
-    // the reference scenarios -6.5 %, configs[2]'s dimensions at 1 024: -2..-9 % (tools/exp_cfg1_proxy_order.py,
-    // profiles/r06_exp_proxy_order.txt; at 65 536 instances the pilot stays ahead).
-    // One measured exception keeps the pilot: the 4- / 6-slot kernels at full oversubscription (B > 7/8 of the SIMD count, four
-    // wavefronts per instance on three slots per SIMD -- configs[1] itself), where the order decides which quarter of the
-    // workgroups waits for a slot and the pilot's better key is worth its barrier on the contract family (21.1 against 21.6 ms;
-    // `passing` would gain 7 % there too: 20.6 -> 19.2).
-    // The two-wavefront plans of the 4- / 6-slot kernels (1 024 < B <= 4 096, up to 2.7x oversubscribed) had no ranking at all: the
-    // same evaluation order there -- B = 2 500 / 4 096: contract family -10 / -12 %, corridor -9 %, `passing` -4 / -6 %, the
-    // reference scenarios +-2 %; a pilot launch loses or ties everywhere (same record). 14-slot kernels, 769..1 433: neutral, none.
-    const double fills_ = !reg32 ? kStageFills : L.rs >= kRegSlotsLarge ? kFillsLarge : kStageFillsReg;
-    const int res_ = pl.resident ? pl.resident : resident;
-    // ... and the throughput plans up to eight device fills (tools/exp_cfg1_proxy_order.py at 3 000 .. 40 000 instances, both
-    // dimensions, same record): one launch in the evaluation order + the tail hand-off against pilot + ranking + hand-off --
-    // `passing` / the reference scenarios -8..-11 % up to six fills, the contract family -3..+1 %; level at eight fills; from ten
-    // on the pilot's key wins (65 536: `passing` 85.7 against 91.3 ms) and stays.
-    const bool proxy = reg32 && caps[0] == 0 && allow_staging && pl.stageable && !k.order && k.status && dev_factor("NMPC_PROXY_ORDER", 1) > 0 &&
-                       (pl.mode == 1 ? (B > lat_cap / 2 && (B <= lat_cap ? (L.rs >= kRegSlotsLarge || 8 * B <= 7 * lat_cap)
-                                                                         : (L.rs < kRegSlotsLarge && B <= 4 * lat_cap)))
-                                     : (pl.mode == 0 && B >= fills_ * res_ && B < dev_factor("NMPC_PROXY_FILLS", kProxyFills) * res_));
-    if (proxy) caps[0] = -1;
-    if (caps[0] == 0)
-        caps[0] = ((pl.mode == 0 && B >= dev_factor("NMPC_STAGE_FILLS", !reg32 ? kStageFills : L.rs >= kRegSlotsLarge ? kFillsLarge : kStageFillsReg) * (pl.resident ? pl.resident : resident)) || (pl.mode == 1 && B > lat_cap / 2 && B <= lat_cap) ||
-                   (pl.mode == 2 && !pl.uses_ws && B >= 4 * pl.resident)) ? 1 : -1; // (configs[4] fp32: 2 116 -> 2 087 ms;
-                                                                                   //  streamed table, fp64: -2 %, off)
-    if (caps[1] == 0) caps[1] = -1;
-    const bool stageable = allow_staging && pl.stageable && !k.order && k.status;
-    int n_stage = 0, stage_cap[2], stage_key[2];
-    for (int i = 0; i < 2; ++i)
-        if (stageable && caps[i] > 0 && caps[i] < h->cfg.max_outer_iterations && (n_stage == 0 || caps[i] > stage_cap[n_stage - 1])) {
-            stage_cap[n_stage] = caps[i];
-            stage_key[n_stage] = i;
-            ++n_stage;
-        }
-    h->last_staged = n_stage == 0 ? 0 : n_stage == 1 ? stage_cap[0] : 100 * stage_cap[0] + stage_cap[1];
+    const PlanStatic s = plan_static<T>(h);
+    const PlanTuning tune = plan_tuning();
+    const SolvePlan pl = plan_solve(s, {B, k.order != nullptr, allow_staging, k.status != nullptr}, tune);
+    if (int rc = bind_choice<T>(h, pl.main, k, B)) return rc;
+    if (int rc = prepare_axis<T>(h, pl.main.has_axis, k, B)) return rc;
+    h->last_mode = pl.last_mode;
+    h->last_axis = pl.main.has_axis ? k.axis_mode : -1;
+    h->last_staged = pl.last_staged;
+    h->last_order = pl.last_order;
     h->last_tail = 0;
-    if (proxy) h->last_order = 2;
-    else if (n_stage > 0) h->last_order = 3;
     // (the evaluation order below goes into k.order for the rest of this function only: the caller's k gets its own back)
     struct OrderGuard {
         nmpc::KParams<T>& kk;
         decltype(nmpc::KParams<T>::order) saved;
         ~OrderGuard() { kk.order = saved; }
     } order_guard{k, k.order};
-    if (proxy) {
+    int* const hist = static_cast<int*>(h->dhist.p);
+    int* const offs = hist + kRankBuckets;
+    int* const dctr = offs + kRankBuckets;       // (KParams::dyn_ctr: four counters behind the bucket tables)
+    const int nb = (B + 255) / 256;
+    // counting sort of the instances by `key` of their parked state (rank_bucket) into dorder2; publish: the number of
+    // unfinished ones goes to the hand-off's counters
+    const auto rank = [&](const T* resume, int key, bool publish) {
+        int* const order2 = static_cast<int*>(h->dorder2.p);
+        hipLaunchKernelGGL(rank_hist_kernel<T>, dim3(nb), dim3(256), 0, h->stream, resume, k.status, B, hist, key);
+        hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(kRankBuckets), 0, h->stream, hist, offs, publish ? dctr : nullptr);
+        hipLaunchKernelGGL(rank_scatter_kernel<T>, dim3(nb), dim3(256), 0, h->stream, resume, k.status, B, offs, order2, key);
+        return hipGetLastError();
+    };
+    if (pl.eval_order) {
+        // one evaluation at the nominal controls (v_nom, 0), zero multipliers, the initial penalty; its ||F2||^2 is the key
         const size_t n = 2 * (size_t)h->cfg.N_hor;
         if (int rc = h->dresume.reserve((size_t)B * nmpc::kResumeStride * sizeof(T))) return rc;
         if (int rc = h->dorder2.reserve((size_t)B * sizeof(int))) return rc;
@@ -1214,93 +856,53 @@ int run_solve(nmpc_handle_s* h, nmpc::KParams<T>& k, int B, bool allow_staging)
         nmpc::EvalParams<T> ep;
         ep.U = Un, ep.Y = Un + (size_t)B * n, ep.C = Un + 2 * (size_t)B * n;
         ep.psi = Un + 2 * (size_t)B * n + B, ep.grad = nullptr, ep.f2sq = Un + 2 * (size_t)B * n + 2 * (size_t)B;
-        const int nbf = (int)(((size_t)B * n + 255) / 256), nb = (B + 255) / 256;
+        const int nbf = (int)(((size_t)B * n + 255) / 256);
         hipLaunchKernelGGL(proxy_fill_kernel<T>, dim3(nbf), dim3(256), 0, h->stream, Un, Un + (size_t)B * n, Un + 2 * (size_t)B * n, B, (int)n,
-                           T(dev_factor("NMPC_PROXY_VNOM", 2.0 / 3.0)) * k.vmax, k.c_init);
-        const size_t lds_eval = (size_t)L.lds_total * sizeof(T);
-        if (k.axis_mode != 0) hipLaunchKernelGGL(pick_eval<T>(h->lps, L.glb, L.rs, 1), dim3(B), dim3(64), lds_eval, h->stream, k, ep);
-        if (k.axis_mode != 1) hipLaunchKernelGGL(pick_eval<T>(h->lps, L.glb, L.rs, 2), dim3(B), dim3(64), lds_eval, h->stream, k, ep);
+                           T(tune.proxy_vnom) * k.vmax, k.c_init);
+        if (int rc = launch_choice<T>(h, choose_single(s, kEval), B, k, ep)) return rc;
         T* const resume = static_cast<T*>(h->dresume.p);
-        int* const hist = static_cast<int*>(h->dhist.p);
-        int* const order2 = static_cast<int*>(h->dorder2.p);
         hipLaunchKernelGGL(proxy_key_kernel<T>, dim3(nb), dim3(256), 0, h->stream, ep.f2sq, resume, k.status, B);
-        hipLaunchKernelGGL(rank_hist_kernel<T>, dim3(nb), dim3(256), 0, h->stream, resume, k.status, B, hist, 0);
-        hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(kRankBuckets), 0, h->stream, hist, hist + kRankBuckets, (int*)nullptr);
-        hipLaunchKernelGGL(rank_scatter_kernel<T>, dim3(nb), dim3(256), 0, h->stream, resume, k.status, B, hist + kRankBuckets, order2, 0);
-        HIP_TRY(hipGetLastError());
-        k.order = order2;   // (from here on as under a caller's order: one launch, the tail hand-off where the batch is big enough)
-        if (pl.mode == 1) return launch_plan<T>(h, pl, k, B);
+        HIP_TRY(rank(resume, 0, false));
+        k.order = static_cast<const int*>(h->dorder2.p); // (from here on as under a caller's order)
     }
-    // Tail hand-off (nmpc_config.tail_latency; round 6). A launch of the throughput kernel ends with
-    // whatever long solves are still running -- one wavefront each, alone on its SIMD -- while the rest of the chip idles: on
-    // batches with a skewed distribution of solve lengths the launch IS its longest instance
-    // (profiles/r05_cfg2_passing_kernel_timeline.txt). The latency family's TAIL member (solve_spec_kernel<.., FLAT = false>:
-    // speculative line search over six wavefronts, the throughput kernels' own evaluation) computes the throughput kernels'
-    // bits and solves a long instance ~1.8x faster on an idle chip (tools/exp_tail_solo.py). So the LAST throughput launch
-    // of a solve parks whatever is still running once it is in its drain phase -- every workgroup dispatched, at most
-    // `park` instances left (KParams::dyn_ctr) -- at the instance's next outer-iteration boundary, and one more launch
-    // -- the tail member over the parked instances, found by the same ranking kernels -- finishes them. Who solves which
-    // part of an instance depends on timing; the results do not (tests/test_gpu_tail.py). (Running the two families side by
-    // side on two streams does not work: with tens of thousands of one-wavefront workgroups pending, a four-wavefront
-    // workgroup never finds its four slots on one CU and runs after the throughput launch -- profiles/r06_ab_tail_handoff.jsonl.)
-    h->last_tail = 0;
-    int park = h->cfg.tail_latency;
-    if (park == 0) park = std::max(32, h->n_simd / 4);      // automatic: one tail workgroup per CU
-    // (six wavefronts per parked instance while they are all resident at two per SIMD, else four: `passing` 87.0 -> 84.4 ms per
-    //  call, batches of 3 000 / 6 000: -8 / -6 %; eight bring nothing more -- profiles/r06_exp_mid_batches.txt)
-    const int tail_waves = (int)dev_factor("NMPC_TAIL_WAVES", park * kSpecWavesWide <= 2 * h->n_simd ? kSpecWavesWide : kSpecWaves);
-    const bool big = B >= dev_factor("NMPC_TAIL_FILLS", !reg32 ? kTailFills : L.rs >= kRegSlotsLarge ? kFillsLarge : kTailFillsReg) * (pl.resident ? pl.resident : resident);
-    const Plan<T> tail = (park > 0 && allow_staging && k.status && pl.stageable && (n_stage > 0 || (k.order && big)) && B >= dev_factor("NMPC_TAIL_MINB", kTailMinParks) * park)
-                             ? plan_tail<T>(h, pl, L, tail_waves) : Plan<T>();
-    if (n_stage == 0 && !tail.fn) return launch_plan<T>(h, pl, k, B);
-    if (tail.fn) {
-        if (int rc = h->ddeep.reserve((size_t)park * nmpc::deep_park_stride(h->cfg.N_hor) * sizeof(T))) return rc;
+    if (pl.n_stage == 0 && !pl.tail) return launch_choice<T>(h, pl.main, B, k);
+    if (pl.tail) {
+        if (int rc = h->ddeep.reserve((size_t)pl.park * nmpc::deep_park_stride(h->cfg.N_hor) * sizeof(T))) return rc;
         k.deep = static_cast<T*>(h->ddeep.p);   // (read by the tail launch; handed to the LAST throughput launch only)
     }
-
     if (int rc = h->dresume.reserve((size_t)B * nmpc::kResumeStride * sizeof(T))) return rc;
     if (int rc = h->dorder2.reserve((size_t)B * sizeof(int))) return rc;
     k.resume = static_cast<T*>(h->dresume.p);
-    int* hist = static_cast<int*>(h->dhist.p);
-    int* offs = hist + kRankBuckets;
-    int* dctr = offs + kRankBuckets;             // (KParams::dyn_ctr: four counters behind the bucket tables)
-    int* order2 = static_cast<int*>(h->dorder2.p);
-    const int nb = (B + 255) / 256;
-    auto rank = [&](int key, bool publish) {
-        hipLaunchKernelGGL(rank_hist_kernel<T>, dim3(nb), dim3(256), 0, h->stream, k.resume, k.status, B, hist, key);
-        hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(kRankBuckets), 0, h->stream, hist, offs, publish ? dctr : nullptr);
-        hipLaunchKernelGGL(rank_scatter_kernel<T>, dim3(nb), dim3(256), 0, h->stream, k.resume, k.status, B, offs, order2, key);
-        return hipGetLastError();
-    };
-    for (int i = 0; i <= n_stage; ++i) {
+    const int* const order2 = static_cast<const int*>(h->dorder2.p);
+    for (int i = 0; i <= pl.n_stage; ++i) {
         nmpc::KParams<T> ki = k;
         ki.deep = nullptr;
         ki.stage_in = i > 0;
-        ki.stage_outer_cap = i < n_stage ? stage_cap[i] : 0;
+        ki.stage_outer_cap = i < pl.n_stage ? pl.stage_cap[i] : 0;
         if (i > 0) ki.order = order2;
-        if (i == n_stage && tail.fn) { // the last throughput launch parks its drain phase (the counters: set by the ranking before it)
-            if (n_stage == 0) {        // (one launch under the caller's order: all B instances are to be solved)
+        if (i == pl.n_stage && pl.tail) { // the last throughput launch parks its drain phase (the counters: set by the ranking before it)
+            if (pl.n_stage == 0) {        // (one launch under the caller's order: all B instances are to be solved)
                 hipLaunchKernelGGL(dyn_init_kernel, dim3(1), dim3(1), 0, h->stream, dctr, B);
                 HIP_TRY(hipGetLastError());
             }
             ki.dyn_ctr = dctr;
-            ki.dyn_park = park;
-            ki.deep = k.deep;       // (parking inside an inner solve: the slots reserved below)
-            ki.deep_slots = park;
+            ki.dyn_park = pl.park;
+            ki.deep = k.deep;       // (parking inside an inner solve: the slots reserved above)
+            ki.deep_slots = pl.park;
         }
-        if (int rc = launch_plan<T>(h, pl, ki, B)) return rc;
-        if (i == n_stage) break;
-        HIP_TRY(rank(stage_key[i], i + 1 == n_stage && tail.fn != nullptr));
+        if (int rc = launch_choice<T>(h, pl.main, B, ki)) return rc;
+        if (i == pl.n_stage) break;
+        HIP_TRY(rank(k.resume, pl.stage_key[i], i + 1 == pl.n_stage && pl.tail));
     }
-    if (tail.fn) {
+    if (pl.tail) {
         // the parked instances (status -1) first in order2 -- at most `park` of them by construction -- and the tail member over them
-        HIP_TRY(rank(0, false));
+        HIP_TRY(rank(k.resume, 0, false));
         nmpc::KParams<T> kt = k;
         kt.stage_in = 1;
         kt.stage_outer_cap = 0;
         kt.order = order2;
-        if (int rc = launch_plan<T>(h, tail, kt, std::min(B, park))) return rc;
-        h->last_tail = park;
+        if (int rc = launch_choice<T>(h, pl.tail_kernel, std::min(B, pl.park), kt)) return rc;
+        h->last_tail = pl.park;
     }
     return 0;
 }
@@ -1396,7 +998,7 @@ int polish_batch(nmpc_handle_s* h, const nmpc::KParams<T>& k, int B, bool y_user
         HIP_TRY(hipGetLastError());
     }
     if (ns == 0) return 0;
-    const Layout& L64 = h->lay64;
+    const Layout& L64 = h->lays.lay64;
     const size_t np = (size_t)L64.np;
     int rc;
     if ((rc = h->psel.reserve((size_t)ns * sizeof(int)))) return rc;
@@ -1472,7 +1074,7 @@ int solve_trace(nmpc_handle_s* h, const double* p, const double* u0, const doubl
     if (!p || !U || !trace || !n_records || max_records < 1)
         return fail(NMPC_ERR_INVALID_ARGUMENT, "p, U, trace, n_records must not be NULL and max_records >= 1");
     HIP_TRY(hipSetDevice(h->cfg.device_id));
-    const Layout& L = h->lay64;
+    const Layout& L = h->lays.lay64;
     const size_t n = 2 * (size_t)h->cfg.N_hor, np = L.np;
     const size_t rec = (size_t)nmpc::kTraceHead + n, tlen = (size_t)nmpc::kTraceHead + (size_t)max_records * rec;
     nmpc::KParams<double> k;
@@ -1516,9 +1118,7 @@ int solve_trace(nmpc_handle_s* h, const double* p, const double* u0, const doubl
         k.ws = static_cast<double*>(h->dws.p);
         k.ws_stride = L.ws_stride;
     }
-    using Fn = void (*)(nmpc::KParams<double>);
-    const Fn fn = L.glb ? (h->lps == 3 ? (Fn)trace_kernel<3, true> : h->lps == 2 ? (Fn)trace_kernel<2, true> : (Fn)trace_kernel<1, true>)
-                        : (h->lps == 3 ? (Fn)trace_kernel<3, false> : h->lps == 2 ? (Fn)trace_kernel<2, false> : (Fn)trace_kernel<1, false>);
+    const SolveFn<double> fn = trace_kernel_of(h->lays.lps, L.glb);
     const size_t lds_bytes = (size_t)L.lds_total * sizeof(double);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(fn, dim3(1), dim3(64), lds_bytes, h->stream, k);
@@ -1560,64 +1160,16 @@ int eval_batch(nmpc_handle_s* h, const T* P, const T* U, const T* Y, const T* C,
     if ((rc = stage_out(h, h->dpsi, psi, (size_t)B, &ep.psi, &hpsi))) return rc;
     if ((rc = stage_out(h, h->dgrad, grad, (size_t)B * n, &ep.grad, &hgrad))) return rc;
     if ((rc = stage_out(h, h->df2, f2sq, (size_t)B, &ep.f2sq, &hf2))) return rc;
-    size_t lds_bytes = (size_t)L.lds_total * sizeof(T);
-    EvalFn<T> fn = pick_eval<T>(h->lps, L.glb, L.rs), fn2 = nullptr;
-    bool has_axis = L.rs > 0 && h->lps == 3 && !L.glb;
-    if (has_axis) fn2 = pick_eval<T>(h->lps, L.glb, L.rs, 2); // (register-table kernels are pairs: the general-path member)
-    if constexpr (sizeof(T) == 8) { // (what solves of large fp64 batches run: the register-table kernel where it is offered)
-        if (h->lay64r.rs > 0 && h->cfg.coop_waves <= 1 && h->cfg.latency_waves <= 1 && (h->cfg.reg_table > 0 || h->use64r_auto)) {
-            const Layout& R = h->lay64r;
-            fill_layout(k, R);
-            fn = pick_eval<T>(h->lps, false, R.rs);
-            fn2 = eval_kernel<T, 3, false, kRegSlotsLarge, 2>;
-            lds_bytes = (size_t)R.lds_total * sizeof(T);
-            has_axis = true;
-        }
-    }
-    bool uses_ws = L.glb;
-    int waves = 1;
-    // coop_waves > 1: evaluate through the cooperative kernels' code path (same variant choice as solve_batch)
-    if (h->cfg.coop_waves > 1 && L.rs == 0 && h->coop_ok[sizeof(T) == 4 ? 0 : 1]) {
-        waves = std::min<int>(h->cfg.coop_waves, kSpecWaves);
-        fn = pick_eval_coop<T>(h->lps, L.glb, L.glb ? 1 : 2);
-        fn2 = L.glb ? pick_eval_coop<T>(h->lps, true, 2) : nullptr;
-        has_axis = L.glb;
-        lds_bytes = (size_t)L.lds_total_coop * sizeof(T);
-        k.lds_xch = L.lds_xch_coop;
-        if constexpr (sizeof(T) == 4) {
-            if (waves == kSpecWaves && h->lay32c.rs > 0 && h->lps == 1) {
-                const Layout& C = h->lay32c;
-                fill_layout(k, C);
-                k.lds_xch = C.lds_xch_coop;
-                waves = kCoopRegWaves;
-                fn = pick_eval_coop_reg(h->cfg.N_hor);
-                fn2 = nullptr;
-                has_axis = false;
-                lds_bytes = (size_t)C.lds_total_coop * sizeof(T);
-                uses_ws = false;
-            }
-        }
-    }
-    if (uses_ws) { // (only the variants that stream the obstacle table reserve the global workspace)
-        if (int rc_ = h->dws.reserve((size_t)B * L.ws_stride * sizeof(T))) return rc_;
-        k.ws = static_cast<T*>(h->dws.p);
-        k.ws_stride = L.ws_stride;
-    }
-    if ((rc = prepare_axis<T>(h, has_axis, k, B))) return rc;
-    h->last_mode = waves > 1 ? 2 : 0;
-    h->last_axis = has_axis ? k.axis_mode : -1;
+    const KernelChoice kc = plan_eval(plan_static<T>(h));
+    if ((rc = bind_choice<T>(h, kc, k, B))) return rc;
+    if ((rc = prepare_axis<T>(h, kc.has_axis, k, B))) return rc;
+    h->last_mode = kc.coop ? 2 : 0;
+    h->last_axis = kc.has_axis ? k.axis_mode : -1;
     h->last_staged = 0;
     h->last_polish_selected = 0;
     h->last_tail = 0;
     h->last_order = 0;
-    if (!fn2 || k.axis_mode != 0) {
-        hipLaunchKernelGGL(fn, dim3(B), dim3(64 * waves), lds_bytes, h->stream, k, ep);
-        HIP_TRY(hipGetLastError());
-    }
-    if (fn2 && k.axis_mode != 1) {
-        hipLaunchKernelGGL(fn2, dim3(B), dim3(64 * waves), lds_bytes, h->stream, k, ep);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = launch_choice<T>(h, kc, B, k, ep))) return rc;
     if (hpsi) HIP_TRY(hipMemcpyAsync(psi, ep.psi, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, h->stream));
     if (hgrad) HIP_TRY(hipMemcpyAsync(grad, ep.grad, (size_t)B * n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
     if (hf2) HIP_TRY(hipMemcpyAsync(f2sq, ep.f2sq, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, h->stream));
@@ -1889,49 +1441,39 @@ int loop_step(nmpc_handle_s* h, const nmpc_loop_args* g, bool post)
     return 0;
 }
 
+// the kernel(s) of a variant may use `bytes` of dynamic LDS (beyond 48 KB a kernel has to be told)
+template <typename T>
+int allow_lds(const Variant& v, size_t bytes)
+{
+    if (bytes <= kLdsOptIn) return 0;
+    for (int member = 1; member <= (v.pair ? 2 : 1); ++member) {
+        const void* fn = v.family >= kEval ? reinterpret_cast<const void*>(eval_kernel_of<T>(v, member))
+                                           : reinterpret_cast<const void*>(solve_kernel_of<T>(v, member));
+        if (fn) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    }
+    return 0;
+}
+
+// every variant the plans of this handle can name, by family; families whose LDS does not fit are switched off
 template <typename T>
 int set_lds_limit(nmpc_handle_s* h)
 {
     const Layout& L = h->lay<T>();
-    const size_t lds_bytes = (size_t)L.lds_total * sizeof(T);
-    if (lds_bytes > 48 * 1024)
-        for (int only = 1; only <= 2; ++only) { // (register-table kernels: both members of the pair; else the same kernel twice)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_solve<T>(h->lps, L.glb, L.rs, only)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_eval<T>(h->lps, L.glb, L.rs, only)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        }
-    if (sizeof(T) == 4 && h->lay32c.rs > 0) {
-        const size_t cb = (size_t)h->lay32c.lds_total_coop * sizeof(float);
-        if (cb > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_solve_coop_reg(h->cfg.N_hor)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)cb));
-        if (cb > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_eval_coop_reg(h->cfg.N_hor)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)cb));
-    }
-    const size_t coop_bytes = (size_t)L.lds_total_coop * sizeof(T);
-    if (coop_bytes > kLdsLimit) {
-        h->coop_ok[sizeof(T) == 4 ? 0 : 1] = false;
-    } else if (coop_bytes > 48 * 1024) {
-        for (int only = 1; only <= 2; ++only) { // (global table: both members of the pair; else the same kernel twice)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_solve_coop<T>(h->lps, L.glb, only)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)coop_bytes));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_eval_coop<T>(h->lps, L.glb, only)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)coop_bytes));
-        }
-    }
-    const size_t spec_bytes = (size_t)L.lds_total_spec * sizeof(T);
-    if (spec_bytes > kLdsLimit) {
-        h->spec_ok[sizeof(T) == 4 ? 0 : 1] = false; // no room for the exchange area: latency mode unavailable
-    } else if (spec_bytes > 48 * 1024) {
-        for (int only = 1; only <= 2; ++only) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_solve_spec<T>(h->lps, L.glb, L.rs, only)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)spec_bytes));
-            if (auto* tf = pick_solve_tail<T>(h->lps, L.glb, L.rs, only))
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)spec_bytes));
-        }
-    }
+    const int lps = h->lays.lps, prec = sizeof(T) == 4 ? 0 : 1;
+    int rc = 0;
+    for (Family f : {kThroughput, kEval})
+        if ((rc = allow_lds<T>(single_variant(f, L, lps), (size_t)L.lds_total * sizeof(T)))) return rc;
+    if (sizeof(T) == 4 && h->lays.lay32c.rs > 0)
+        for (bool eval : {false, true})
+            if ((rc = allow_lds<T>(coop_onchip_variant(eval, h->cfg.N_hor), (size_t)h->lays.lay32c.lds_total_coop * sizeof(T)))) return rc;
+    h->coop_ok[prec] = coop_fits(L, sizeof(T));
+    if (h->coop_ok[prec])
+        for (bool eval : {false, true})
+            if ((rc = allow_lds<T>(coop_variant(eval, L, lps), (size_t)L.lds_total_coop * sizeof(T)))) return rc;
+    h->spec_ok[prec] = latency_fits(L, sizeof(T)); // (no room for the exchange area: latency mode unavailable)
+    if (h->spec_ok[prec])
+        for (Family f : {kLatencyFlat, kLatencyTail}) // (allow_lds skips the tail member where there is none)
+            if ((rc = allow_lds<T>(single_variant(f, L, lps), (size_t)L.lds_total_spec * sizeof(T)))) return rc;
     return 0;
 }
 
@@ -2073,17 +1615,9 @@ int nmpc_create(const nmpc_config* cfg, nmpc_handle* out)
     nmpc_handle_s* h = new (std::nothrow) nmpc_handle_s();
     if (!h) return fail(NMPC_ERR_OUT_OF_MEMORY, "host allocation failed");
     h->cfg = *cfg;
-    h->lay32 = make_layout(*cfg, sizeof(float));
-    h->lay64 = make_layout(*cfg, sizeof(double));
-    h->lay32c = make_layout(*cfg, sizeof(float), true);
-    h->lay64r = make_layout(*cfg, sizeof(double), false, true);
-    h->use64r_auto = h->lay64r.rs > 0 && !h->lay64.glb &&
-                     std::min<size_t>(4 * NMPC_WPE_F64, kLdsLimit / ((size_t)h->lay64.lds_total * sizeof(double))) < 4;
-    h->lps = 64 / cfg->N_hor;
-    if (h->lps > 3) h->lps = 3;
-    if (h->lps < 1) h->lps = 1;
-    if ((size_t)h->lay64.lds_total * sizeof(double) > kLdsLimit || (size_t)h->lay32.lds_total * sizeof(float) > kLdsLimit) {
-        const size_t need = (size_t)h->lay64.lds_total * sizeof(double);
+    h->lays = make_layouts(*cfg);
+    if ((size_t)h->lays.lay64.lds_total * sizeof(double) > kLdsLimit || (size_t)h->lays.lay32.lds_total * sizeof(float) > kLdsLimit) {
+        const size_t need = (size_t)h->lays.lay64.lds_total * sizeof(double);
         delete h;
         return fail(NMPC_ERR_UNSUPPORTED,
                     "polygon / robot / path tables alone need %zu B of LDS per instance (> 160 KiB)", need);
@@ -2131,7 +1665,7 @@ int nmpc_destroy(nmpc_handle h)
 int nmpc_param_len(nmpc_handle h)
 {
     if (!h) return fail(NMPC_ERR_INVALID_ARGUMENT, "null handle");
-    return h->lay32.np;
+    return h->lays.lay32.np;
 }
 
 int nmpc_set_stream(nmpc_handle h, void* s)
@@ -2295,20 +1829,20 @@ int nmpc_kernel_info(nmpc_handle h, int32_t* lds_bytes_f32, int32_t* lds_bytes_f
 {
     if (!h) return fail(NMPC_ERR_INVALID_ARGUMENT, "null handle");
     HIP_TRY(hipSetDevice(h->cfg.device_id));
-    const size_t l32 = (size_t)h->lay32.lds_total * 4, l64 = (size_t)h->lay64.lds_total * 8;
+    const size_t l32 = (size_t)h->lays.lay32.lds_total * 4, l64 = (size_t)h->lays.lay64.lds_total * 8;
     if (lds_bytes_f32) *lds_bytes_f32 = (int32_t)l32;
     if (lds_bytes_f64) *lds_bytes_f64 = (int32_t)l64;
-    if (lanes_per_step) *lanes_per_step = h->lps;
+    if (lanes_per_step) *lanes_per_step = h->lays.lps;
     if (waves_per_cu_f32) {
         int nb = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &nb, reinterpret_cast<const void*>(pick_solve<float>(h->lps, h->lay32.glb, h->lay32.rs)), 64, l32));
+            &nb, reinterpret_cast<const void*>(solve_kernel_of<float>(single_variant(kThroughput, h->lays.lay32, h->lays.lps))), 64, l32));
         *waves_per_cu_f32 = nb;
     }
     if (waves_per_cu_f64) {
         int nb = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &nb, reinterpret_cast<const void*>(pick_solve<double>(h->lps, h->lay64.glb, h->lay64.rs)), 64, l64));
+            &nb, reinterpret_cast<const void*>(solve_kernel_of<double>(single_variant(kThroughput, h->lays.lay64, h->lays.lps))), 64, l64));
         *waves_per_cu_f64 = nb;
     }
     return 0;

@@ -40,7 +40,7 @@ enum SpecPhase : int { SP_INIT_A, SP_INIT_B, SP_LIP, SP_SPEC0, SP_NOLS, SP_LSN, 
 // numerical difference between the two families: with it this kernel returns the throughput kernels' bits (every row of
 // profiles/r06_family_bits.txt, fp32 and fp64), which is what lets a launch of the throughput kernel hand its longest
 // instances -- parked in its drain phase -- to the speculative line search without an instance's result depending on what
-// else is in its batch (nmpc_config.tail_latency; nmpc_capi.hip, run_solve).
+// else is in its batch (nmpc_config.tail_latency; nmpc_plan.h, plan_solve).
 template <typename T, int LPS, bool GLB, int RS = 0, bool AXIS = false, bool FLAT = true>
 __device__ __forceinline__ void solve_instance_spec(const KParams<T>& kp, const int inst, T* lds)
 {

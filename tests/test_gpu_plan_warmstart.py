@@ -3,7 +3,7 @@ sends the previous solution shifted by one step as u0, the previous multipliers 
 penalty as c0. The plans of run_solve -- dispatch order from one evaluation or from a pilot launch, the resumable solve,
 the tail hand-off with its deep parks -- restore those inputs by paths of their own, so each plan is checked against one
 plain launch (index order, no hand-off) of the same warm-started batch: every result array identical, bit for bit. The
-batch sizes follow the device's SIMD count and the plan thresholds of run_solve; nmpc_last_launch_info shows that the
+batch sizes follow the device's SIMD count and the plan thresholds of csrc/nmpc_plan.h; nmpc_last_launch_info shows that the
 intended plan ran.
 
 Edge warm starts (multipliers outside the box Y = [-1e12, 1e12], zero multipliers passed as input, penalties below 1,
@@ -28,8 +28,8 @@ def n_simd():
 
 
 def plans():
-    """(name, dtype, B, expected launch info, two-wavefront plan) per plan of run_solve (nmpc_capi.hip: plan_solve, the
-    `proxy` / `caps` decisions), for S SIMDs. fp32 throughput kernels of the 4-slot tables: at most 3 S resident, so one
+    """(name, dtype, B, expected launch info, two-wavefront plan) per plan of run_solve (csrc/nmpc_plan.h: plan_solve, the
+    dispatch-order / stage decisions; tests/test_plan_cpu.py checks them without a device), for S SIMDs. fp32 throughput kernels of the 4-slot tables: at most 3 S resident, so one
     device fill <= 3 S instances."""
     S = n_simd()
     park = max(32, S // 4)                          # tail_latency = 0: one tail workgroup per CU
