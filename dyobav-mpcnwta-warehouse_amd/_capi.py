@@ -80,6 +80,22 @@ class NmpcLoopArgs(C.Structure):
                 [(n, C.c_double) for n in ("hyp_fan_rad", "hyp_radius0", "hyp_radius_growth")])
 
 
+class NmpcKfArgs(C.Structure):
+    """Mirror of ``struct nmpc_kf_args`` (device pointers; ``A`` [4,4], ``C`` [2,4], ``Q`` [4,4], ``R`` [2,2] row-major)."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "n_run", "H", "cap")] +
+                [(n, C.c_void_p) for n in ("run", "humans", "hcount", "kf_traj", "kf_len", "kf_P")] +
+                [("A", C.c_double * 16), ("C", C.c_double * 8), ("Q", C.c_double * 16), ("R", C.c_double * 4),
+                 ("human_size", C.c_double), ("dyn_c", C.c_void_p)])
+
+    def set_matrices(self, A, Cm, Q, R):
+        for name, m, shape in (("A", A, (4, 4)), ("C", Cm, (2, 4)), ("Q", Q, (4, 4)), ("R", R, (2, 2))):
+            m = np.asarray(m, dtype=np.float64)
+            if m.shape != shape:
+                raise ValueError(f"{name} must be {shape}, got {m.shape}")
+            getattr(self, name)[:] = m.ravel().tolist()
+        return self
+
+
 class NmpcSnapArgs(C.Structure):
     """Mirror of ``struct nmpc_snap_args`` (device pointers)."""
     _fields_ = ([(n, C.c_int32) for n in ("n_ped", "n_hyp", "x_reverse", "y_reverse")] +
@@ -96,6 +112,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_hypotheses_to_ellipses_f32", "nmpc_hypotheses_to_ellipses_f64",
     "nmpc_set_map", "nmpc_snap_hypotheses_f32", "nmpc_snap_hypotheses_f64",
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
+    "nmpc_kf_predict_f32", "nmpc_kf_predict_f64",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_last_error",
 )
 
@@ -146,6 +163,7 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
         getattr(lib, "nmpc_snap_hypotheses_" + sfx).argtypes = [vp, vp, C.POINTER(NmpcSnapArgs), i32, vp]
         getattr(lib, "nmpc_loop_pre_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
         getattr(lib, "nmpc_loop_post_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
+        getattr(lib, "nmpc_kf_predict_" + sfx).argtypes = [vp, C.POINTER(NmpcKfArgs)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     lib.nmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.nmpc_kernel_info.argtypes = [vp] + [C.POINTER(i32)] * 5
@@ -313,6 +331,13 @@ class Handle:
         """``nmpc_loop_pre_*`` / ``nmpc_loop_post_*``: one half of a closed-loop time step (row f3), enqueued on the
         handle's stream."""
         fn = getattr(self._lib, ("nmpc_loop_post_" if post else "nmpc_loop_pre_") + _suffix(dtype))
+        _check(fn(self._h, C.byref(args)))
+
+    def kf_predict(self, dtype, args: "NmpcKfArgs"):
+        """``nmpc_kf_predict_*``: the Kalman-filter pedestrian predictor for the running scenarios (append the new position,
+        filter the stored trajectories with the carried covariance, write the obstacle rows), enqueued on the handle's
+        stream."""
+        fn = getattr(self._lib, "nmpc_kf_predict_" + _suffix(dtype))
         _check(fn(self._h, C.byref(args)))
 
     def hypotheses_to_ellipses(self, dtype, hypos, cur, dyn_out, n_obs_out=None, human_size=0.2, eps=1.0, enlarge=2.0,

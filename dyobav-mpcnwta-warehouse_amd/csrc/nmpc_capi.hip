@@ -21,6 +21,7 @@
 #include "nmpc_spec.h"
 #include "nmpc_hypotheses.h"
 #include "nmpc_step.h"
+#include "nmpc_kf.h"
 #include "nmpc_snap.h"
 
 using namespace nmpc_plan;
@@ -1441,6 +1442,37 @@ int loop_step(nmpc_handle_s* h, const nmpc_loop_args* g, bool post)
     return 0;
 }
 
+template <typename T>
+int kf_predict(nmpc_handle_s* h, const nmpc_kf_args* g)
+{
+    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if (g->n_run <= 0) return g->n_run == 0 ? 0 : fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_kf_predict: n_run < 0");
+    if (g->B < g->n_run || g->H < 1 || g->cap < 1)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_kf_predict: bad dimensions (B %d, n_run %d, H %d, cap %d)", g->B, g->n_run, g->H, g->cap);
+    if (g->H > h->cfg.Ndynobs) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_kf_predict: H = %d rows exceed Ndynobs = %d", g->H, h->cfg.Ndynobs);
+    if (!g->run && g->n_run != g->B) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_kf_predict: run = NULL needs n_run = B");
+    if (!g->humans || !g->hcount || !g->kf_traj || !g->kf_len || !g->kf_P || !g->dyn_c)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_kf_predict: a required array is NULL");
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    // (a host pointer here would fault inside the kernel: three samples of the argument block are looked up)
+    if (h->ptr_mode != NMPC_PTR_DEVICE && (!is_device_ptr(g->humans) || !is_device_ptr(g->kf_traj) || !is_device_ptr(g->dyn_c)))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_kf_predict: every array must be a device pointer");
+    nmpc::KfParams<T> p;
+    std::memset(&p, 0, sizeof p);
+    p.B = g->B, p.n_run = g->n_run, p.N = h->cfg.N_hor, p.H = g->H, p.cap = g->cap;
+    p.run = reinterpret_cast<const long long*>(g->run);
+    p.humans = static_cast<const T*>(g->humans), p.hcount = reinterpret_cast<const long long*>(g->hcount);
+    p.kf_traj = static_cast<T*>(g->kf_traj), p.kf_len = reinterpret_cast<long long*>(g->kf_len);
+    p.kf_P = static_cast<T*>(g->kf_P), p.dyn_c = static_cast<T*>(g->dyn_c);
+    for (int i = 0; i < 16; ++i) p.A[i] = (T)g->A[i], p.Q[i] = (T)g->Q[i];
+    for (int i = 0; i < 8; ++i) p.C[i] = (T)g->C[i];
+    for (int i = 0; i < 4; ++i) p.R[i] = (T)g->R[i];
+    p.human_size = (T)g->human_size;
+    hipLaunchKernelGGL(nmpc::kf_predict_kernel<T>, dim3(g->n_run), dim3(64), 0, h->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // the kernel(s) of a variant may use `bytes` of dynamic LDS (beyond 48 KB a kernel has to be told)
 template <typename T>
 int allow_lds(const Variant& v, size_t bytes)
@@ -1793,6 +1825,9 @@ int nmpc_loop_pre_f32(nmpc_handle h, const nmpc_loop_args* a) { return loop_step
 int nmpc_loop_pre_f64(nmpc_handle h, const nmpc_loop_args* a) { return loop_step<double>(h, a, false); }
 int nmpc_loop_post_f32(nmpc_handle h, const nmpc_loop_args* a) { return loop_step<float>(h, a, true); }
 int nmpc_loop_post_f64(nmpc_handle h, const nmpc_loop_args* a) { return loop_step<double>(h, a, true); }
+
+int nmpc_kf_predict_f32(nmpc_handle h, const nmpc_kf_args* a) { return kf_predict<float>(h, a); }
+int nmpc_kf_predict_f64(nmpc_handle h, const nmpc_kf_args* a) { return kf_predict<double>(h, a); }
 
 int nmpc_last_kernel_ms(nmpc_handle h, float* ms)
 {

@@ -1,21 +1,26 @@
 """Batched closed-loop evaluator ("next" row f3): B independent warehouse scenarios advanced in lock-step on the device.
 
-Semantics of the reference's evaluation loop for the MPC tracker with the constant-velocity predictor
+Semantics of the reference's evaluation loop for the MPC tracker with the constant-velocity predictor (``cvmp``) or the
+Kalman-filter predictor (``kfmp``), the two predictor configurations of ``main_eva.py`` that need no network weights
 (``/root/reference/src``):
 
 * ``MainBase.run_once`` / ``run_one_step``                      main_base.py:267-346, 348-425
 * ``MainBase.run_cv_prediction`` + ``CvmpInterface``            main_base.py:238-264, interfaces/cvmp_interface.py:24-57
   (mean step of the last <= 5 positions, extrapolated; std 1.0 for predicted offsets, HUMAN_SIZE at offset 0)
+* ``MainBase.run_kf_prediction`` + ``KfmpInterface`` + ``zfilter`` main_base.py:210-236, interfaces/kfmp_interface.py:26-56,
+  zfilter.py:45-78 (``predictor="kfmp"``: the filter re-run over every pedestrian's whole past trajectory at every step,
+  ONE covariance per run carried through the pedestrians and the steps; rows ``[mu, P00, P11, 0, 1]``)
 * obstacle rows ``[mu_x, mu_y, std_x, std_y, 0, 1]``            main_base.py:293-302
 * ``MpcInterface.run_step`` -> ``TrajectoryTracker.run_step``   interfaces/mpc_interface.py:52-71, trajectory_tracker.py:273-337
   (reference-state window, speed-reference rule, previous action; multipliers carried between solves)
 * no-backward clip, robot / pedestrian motion                  main_base.py:320-324, basic_agent.py:52-82
 * metrics                                                       main_pre.py:20-53, main_base.py:326-335, 427-435
 
-One time step = CV prediction -> obstacle rows -> reference windows -> ``nmpc_assemble_params`` (f1) ->
+One time step = prediction -> obstacle rows -> reference windows -> ``nmpc_assemble_params`` (f1) ->
 ``nmpc_solve_batch`` -> first action -> agent motion -> metrics, for all scenarios at once; nothing leaves HBM
 between steps. Everything around the solve is two HIP kernels (``nmpc_loop_pre_*`` / ``nmpc_loop_post_*``,
-``csrc/nmpc_step.h``); the torch expressions further down (``fused=False``) are the same arithmetic written out op by
+``csrc/nmpc_step.h``), with ``predictor="kfmp"`` a third between ``loop_pre`` and f1 that overwrites the obstacle rows
+(``nmpc_kf_predict_*``, ``csrc/nmpc_kf.h``; fused path only -- its independent check is tests/kf_reference.py); the torch expressions further down (``fused=False``) are the same arithmetic written out op by
 op -- they were the implementation of rounds 1-2 and stay as the independent check of the kernels. Where the reference runs ``max_num_run`` scenarios one after another (main_base.py:448-464), this
 runs them side by side. Pedestrian stagger uses a seeded torch generator (the reference's ``random`` is unseeded).
 """
@@ -93,8 +98,14 @@ class BatchEvaluator:
                  human_stagger: float = 0.0, seed: int = 0, mode: str = "work",
                  tuning: Optional[Sequence[float]] = None, lin_vel_max: float = 1.5, warm_start: bool = False,
                  compact: Optional[bool] = None, fused: bool = True, n_hyp: int = 1, hyp_fan: float = 0.15,
-                 hyp_radius_growth: float = 0.05):
-        """``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
+                 hyp_radius_growth: float = 0.05, predictor: str = "cvmp", kf_Q=None, kf_R=None, kf_P0=None):
+        """``predictor``: ``"cvmp"`` = the constant-velocity predictor; ``"kfmp"`` = the Kalman-filter predictor
+        (constant-velocity model at the configuration's ``ts``; ``kf_Q`` [4,4], ``kf_R`` [2,2], ``kf_P0`` [4,4] default to
+        the identities main_base.py:165 and ``KfmpInterface`` use). It needs ``n_hyp == 1`` and ``fused=True``. The filter
+        runs over the whole past trajectory of every pedestrian at every step, so ``run(max_steps)`` keeps all of them on the
+        device: ``B * H * (max_steps + 1) * 2`` reals -- 254 MB in fp32 at B = 65 536, H = 4, 120 steps.
+
+        ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the
         multi-hypothesis obstacle tensor SURVEY.md 8(d) prescribes for BASELINE configs[2] (4 pedestrians x 10
         hypotheses), here produced closed-loop from the scenarios' own pedestrian motion instead of one-shot. ``n_hyp``
@@ -102,6 +113,16 @@ class BatchEvaluator:
         import torch
         self.torch = torch
         self.fused = fused
+        if predictor not in ("cvmp", "kfmp"):
+            raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp)")
+        if predictor == "kfmp" and (max(1, int(n_hyp)) != 1 or not fused):
+            raise ValueError("predictor = 'kfmp' needs n_hyp = 1 and fused = True")
+        self.predictor = predictor
+        eye = lambda m, n: np.eye(n) if m is None else np.asarray(m, dtype=np.float64).reshape(n, n)
+        self.kf_Q, self.kf_R, self.kf_P0 = eye(kf_Q, 4), eye(kf_R, 2), eye(kf_P0, 4)
+        # time_predictor: HIP events around every nmpc_kf_predict call; run() leaves the times (ms) in predictor_ms
+        self.time_predictor = False
+        self.predictor_ms: list = []
         self.time_solves = True     # record the HIP-event time of every batched solve (one event wait per time step)
         self.cfg = config
         self.dt = np.dtype(dtype)
@@ -366,6 +387,21 @@ class BatchEvaluator:
                         ("dyn_c", dyn_c), ("U", self.U), ("y", self.y)):
             assert t.is_contiguous(), name
             setattr(a, name, t.data_ptr())
+        kf = None
+        if self.predictor == "kfmp":
+            # past_traj of every pedestrian (nmpc_kf_predict appends the current position while hcount grows) and the
+            # run's covariance: main_base.py:158-172 makes a new interface object, i.e. P = P0, per run
+            cap = max(max_steps, 1) + 1
+            kf_traj = z(B, H, cap, 2)
+            kf_len = z(B, H, dtype=torch.long, fill=0)
+            kf_P = torch.as_tensor(self.kf_P0, dtype=tdt, device=dev).repeat(B, 1, 1).contiguous()
+            ts = float(self.ts)
+            kf = _capi.NmpcKfArgs().set_matrices([[1, 0, ts, 0], [0, 1, 0, ts], [0, 0, 1, 0], [0, 0, 0, 1]],
+                                                 [[1, 0, 0, 0], [0, 1, 0, 0]], self.kf_Q, self.kf_R)      # zfilter.model_CV(ts)
+            kf.B, kf.H, kf.cap, kf.human_size = B, H, cap, HUMAN_SIZE
+            kf.humans, kf.hcount, kf.dyn_c = self.humans.data_ptr(), self.hcount.data_ptr(), dyn_c.data_ptr()
+            kf.kf_traj, kf.kf_len, kf.kf_P = kf_traj.data_ptr(), kf_len.data_ptr(), kf_P.data_ptr()
+        kf_events = []
         solve_ms = []
         n_steps_run = 0
         for kt in range(max_steps):
@@ -390,6 +426,14 @@ class BatchEvaluator:
             a.stagger = None if st is None else st.data_ptr()
             a.U_c, a.y_c, a.gather_y = Ua.data_ptr(), ya.data_ptr(), int(not full)
             self.h.loop_step(self.dt, a, post=False)
+            if kf is not None:
+                kf.n_run, kf.run = nA, a.run
+                if self.time_predictor:
+                    kf_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                    kf_events[-1][0].record()
+                self.h.kf_predict(self.dt, kf)
+                if self.time_predictor:
+                    kf_events[-1][1].record()
             self.h.assemble_params(self.dt, nA, Pa, last_u_c, state_c, refs_c, speed_c, self.tuning, self.stcw, self.dynw,
                                    self.polys, dyn_c[:nA])
             if self.on_params is not None:
@@ -431,6 +475,9 @@ class BatchEvaluator:
                 record.append(rec)
             if self.time_solves:
                 solve_ms.append(hs.last_kernel_ms())
+        if kf_events:
+            torch.cuda.synchronize(dev)
+            self.predictor_ms = [e0.elapsed_time(e1) for e0, e1 in kf_events]
         alive_b, collision_b, complete_b = alive.bool(), collision.bool(), complete.bool()
         collision_b = collision_b | alive_b                                      # time-out, main_base.py:407-410
         T_run = n_steps_run

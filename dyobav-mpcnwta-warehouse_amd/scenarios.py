@@ -342,7 +342,7 @@ HUMAN_STAGGER = 0.5     # main_base.py:77
 
 def harvest_closed_loop(config, B: int, steps=(1, 8, 20), seed: int = 13, n_ped: int = 4, n_hyp: int = 10,
                         dtype=np.float32, human_stagger: float | None = None, return_device: bool = False,
-                        family: str = "corridor"):
+                        family: str = "corridor", predictor: str = "cvmp"):
     """Parameter vectors ``P[B, np]`` as the closed loop produces them: ``make_closed_loop_scenarios(B, seed, n_ped)``
     advanced by ``evaluate.BatchEvaluator`` (row f3, pinned to the reference) with ``n_hyp`` hypotheses per pedestrian
     fanned around the constant-velocity prediction (``config.Ndynobs`` >= n_ped * n_hyp), and the assembled
@@ -350,6 +350,8 @@ def harvest_closed_loop(config, B: int, steps=(1, 8, 20), seed: int = 13, n_ped:
     len(steps)]``: every scenario at every step) --
     or at the last earlier capture step it was still running. ``family``: ``"reference"`` = ``make_reference_scenarios``
     (scenario_0..2 on the warehouse map, HUMAN_STAGGER 0.5), ``"corridor"`` = ``make_closed_loop_scenarios`` (round 5).
+    ``predictor``: ``"cvmp"`` (the constant-velocity rows, fanned for ``n_hyp`` > 1) or ``"kfmp"`` (the Kalman-filter rows of
+    ``BatchEvaluator(predictor="kfmp")``; needs ``n_hyp = 1``).
     Needs the GPU (the closed loop solves on the device).
     Returns ``(P, step_of_row)``: numpy arrays, or torch device tensors with ``return_device``."""
     import copy
@@ -369,7 +371,7 @@ def harvest_closed_loop(config, B: int, steps=(1, 8, 20), seed: int = 13, n_ped:
         raise ValueError(f"family = {family!r} (reference or corridor)")
     cfg = copy.copy(config)
     cfg.max_active_dynobs = n_ped * n_hyp
-    ev = BatchEvaluator(cfg, dtype=dtype, human_stagger=human_stagger, seed=seed, n_hyp=n_hyp, **sc)
+    ev = BatchEvaluator(cfg, dtype=dtype, human_stagger=human_stagger, seed=seed, n_hyp=n_hyp, predictor=predictor, **sc)
     ev.time_solves = False
     out = torch.zeros(B, ev.h.np_, dtype=ev.tdt, device=ev.dev)
     step_of = torch.full((B,), -1, dtype=torch.int32, device=ev.dev)
