@@ -96,6 +96,24 @@ class NmpcKfArgs(C.Structure):
         return self
 
 
+class NmpcDwaArgs(C.Structure):
+    """Mirror of ``struct nmpc_dwa_args`` (device pointers)."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "n_run", "H", "M", "Pmax", "cap", "dyn_mode", "reserved")] +
+                [(n, C.c_void_p) for n in ("run", "state_c", "last_u_c", "dyn_c", "goal", "path", "path_len", "polys")] +
+                [(n, C.c_double) for n in ("lin_vel_min", "lin_vel_max", "lin_acc_max", "ang_vel_max", "ang_acc_max",
+                                           "base_speed_factor", "vel_resolution", "ang_resolution", "stuck_threshold",
+                                           "q_speed", "q_goal_dir", "q_ref_deviation", "q_stc_obstacle", "q_dyn_obstacle")] +
+                [(n, C.c_void_p) for n in ("U_c", "min_cost", "choice", "counts", "cost_all", "cand_all")])
+
+    def set_config(self, cfg, base_speed_factor: float = 0.8):
+        """Limits, resolutions and weights from a :class:`.configs.DwaConfiguration` ('work' mode: 0.8 lin_vel_max)."""
+        for n in ("lin_vel_min", "lin_vel_max", "lin_acc_max", "ang_vel_max", "ang_acc_max", "vel_resolution", "ang_resolution",
+                  "stuck_threshold", "q_speed", "q_goal_dir", "q_ref_deviation", "q_stc_obstacle", "q_dyn_obstacle"):
+            setattr(self, n, float(getattr(cfg, n)))
+        self.base_speed_factor = float(base_speed_factor)
+        return self
+
+
 class NmpcSnapArgs(C.Structure):
     """Mirror of ``struct nmpc_snap_args`` (device pointers)."""
     _fields_ = ([(n, C.c_int32) for n in ("n_ped", "n_hyp", "x_reverse", "y_reverse")] +
@@ -112,7 +130,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_hypotheses_to_ellipses_f32", "nmpc_hypotheses_to_ellipses_f64",
     "nmpc_set_map", "nmpc_snap_hypotheses_f32", "nmpc_snap_hypotheses_f64",
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
-    "nmpc_kf_predict_f32", "nmpc_kf_predict_f64",
+    "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_last_error",
 )
 
@@ -164,6 +182,7 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
         getattr(lib, "nmpc_loop_pre_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
         getattr(lib, "nmpc_loop_post_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
         getattr(lib, "nmpc_kf_predict_" + sfx).argtypes = [vp, C.POINTER(NmpcKfArgs)]
+        getattr(lib, "nmpc_dwa_step_" + sfx).argtypes = [vp, C.POINTER(NmpcDwaArgs)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     lib.nmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.nmpc_kernel_info.argtypes = [vp] + [C.POINTER(i32)] * 5
@@ -339,6 +358,12 @@ class Handle:
         stream."""
         fn = getattr(self._lib, "nmpc_kf_predict_" + _suffix(dtype))
         _check(fn(self._h, C.byref(args)))
+
+    def dwa_step(self, dtype, args: "NmpcDwaArgs"):
+        """``nmpc_dwa_step_*``: the dynamic-window tracker for the running scenarios (window, grid, rollouts, costs, ordered
+        arg-min; ``U_c`` = the chosen control repeated ``N_hor`` times), one launch enqueued on the handle's stream."""
+        fn = getattr(self._lib, "nmpc_dwa_step_" + _suffix(dtype))
+        _check(fn(self._h, C.byref(args) if args is not None else None))
 
     def hypotheses_to_ellipses(self, dtype, hypos, cur, dyn_out, n_obs_out=None, human_size=0.2, eps=1.0, enlarge=2.0,
                                extra_margin=0.0):

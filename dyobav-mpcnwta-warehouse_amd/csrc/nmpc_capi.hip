@@ -22,6 +22,7 @@
 #include "nmpc_hypotheses.h"
 #include "nmpc_step.h"
 #include "nmpc_kf.h"
+#include "nmpc_dwa.h"
 #include "nmpc_snap.h"
 
 using namespace nmpc_plan;
@@ -1473,6 +1474,69 @@ int kf_predict(nmpc_handle_s* h, const nmpc_kf_args* g)
     return 0;
 }
 
+// largest nv * nw a scenario's window can give: per axis the window is at most min(range, 2 acc ts) wide and np.arange's
+// count is ceil of a quotient that rounding can lift past an integer, so floor(...) + 1 (host only)
+static long long dwa_axis_bound(double range, double acc, double ts, double res)
+{
+    const double w = std::min(range, 2.0 * acc * ts);
+    if (!(w > 0.0)) return 1;
+    const double q = w / res * (1.0 + 1e-9);
+    return q < 1e9 ? (long long)q + 1 : 1000000000LL;
+}
+
+template <typename T>
+int dwa_step(nmpc_handle_s* h, const nmpc_dwa_args* g)
+{
+    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if (g->n_run < 0 || g->B < g->n_run || g->M < 0 || g->Pmax < 2 || g->cap < 1 || g->dyn_mode < 0 || g->dyn_mode > 2 ||
+        (g->dyn_mode > 0 && g->H < 1) || g->H < 0)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: bad dimensions (B %d, n_run %d, H %d, M %d, Pmax %d, cap %d, dyn_mode %d)",
+                    g->B, g->n_run, g->H, g->M, g->Pmax, g->cap, g->dyn_mode);
+    if (!g->run && g->n_run != g->B) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: run = NULL needs n_run = B");
+    if (!(g->vel_resolution > 0.0) || !(g->ang_resolution > 0.0) || !(g->lin_vel_max >= g->lin_vel_min) || !(g->ang_vel_max >= 0.0) ||
+        !(g->lin_acc_max >= 0.0) || !(g->ang_acc_max >= 0.0))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: resolutions must be positive, limits ordered, accelerations non-negative");
+    if (!g->state_c || !g->last_u_c || !g->goal || !g->path || !g->path_len || !g->U_c || !g->min_cost || !g->choice || !g->counts ||
+        (g->dyn_mode > 0 && !g->dyn_c) || (g->M > 0 && !g->polys))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: a required array is NULL");
+    const auto aligned = [](const void* q, size_t al) { return q == nullptr || reinterpret_cast<uintptr_t>(q) % al == 0; };
+    for (const void* q : {g->state_c, g->last_u_c, g->dyn_c, g->goal, g->path, g->polys, (const void*)g->U_c, (const void*)g->min_cost,
+                          (const void*)g->cost_all, (const void*)g->cand_all})
+        if (!aligned(q, sizeof(T))) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: a real array is not aligned to its element type");
+    if (!aligned(g->run, 8) || !aligned(g->path_len, 8) || !aligned(g->choice, 4) || !aligned(g->counts, 4))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: an integer array is not aligned to its element type");
+    const long long need = dwa_axis_bound(g->lin_vel_max - g->lin_vel_min, g->lin_acc_max, h->cfg.ts, g->vel_resolution) *
+                           dwa_axis_bound(2.0 * g->ang_vel_max, g->ang_acc_max, h->cfg.ts, g->ang_resolution);
+    if (need > g->cap)
+        return fail(NMPC_ERR_UNSUPPORTED, "nmpc_dwa_step: cap = %d candidates, these limits and resolutions can give %lld", g->cap, need);
+    const size_t lds = (size_t)g->M * 4 * nmpc::kDwaEdgeReals * sizeof(T);
+    if (g->M > 256) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_dwa_step: M = %d rectangles > 256", g->M);
+    if (g->n_run == 0) return 0;
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    // (a host pointer here would fault inside the kernel: three samples of the argument block are looked up)
+    if (h->ptr_mode != NMPC_PTR_DEVICE && (!is_device_ptr(g->state_c) || !is_device_ptr(g->U_c) || !is_device_ptr(g->path)))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: every array must be a device pointer");
+    nmpc::DwaParams<T> p;
+    std::memset(&p, 0, sizeof p);
+    p.B = g->B, p.n_run = g->n_run, p.N = h->cfg.N_hor, p.H = g->dyn_mode > 0 ? g->H : 0, p.M = g->M, p.Pmax = g->Pmax;
+    p.cap = g->cap, p.dyn_mode = g->dyn_mode;
+    p.run = reinterpret_cast<const long long*>(g->run);
+    p.state_c = static_cast<const T*>(g->state_c), p.last_u_c = static_cast<const T*>(g->last_u_c);
+    p.dyn_c = static_cast<const T*>(g->dyn_c), p.goal = static_cast<const T*>(g->goal), p.path = static_cast<const T*>(g->path);
+    p.path_len = reinterpret_cast<const long long*>(g->path_len), p.polys = static_cast<const T*>(g->polys);
+    p.ts = h->cfg.ts, p.vmin = g->lin_vel_min, p.vmax = g->lin_vel_max, p.acc = g->lin_acc_max;
+    p.wmax = g->ang_vel_max, p.wacc = g->ang_acc_max, p.dv = g->vel_resolution, p.dw = g->ang_resolution;
+    p.tsT = (T)h->cfg.ts, p.lin_vel_max = (T)g->lin_vel_max, p.base_speed = (T)g->lin_vel_max * (T)g->base_speed_factor;
+    p.stuck = (T)g->stuck_threshold, p.q_speed = (T)g->q_speed, p.q_goal = (T)g->q_goal_dir, p.q_ref = (T)g->q_ref_deviation;
+    p.q_stc = (T)g->q_stc_obstacle, p.q_dyn = (T)g->q_dyn_obstacle;
+    p.U_c = static_cast<T*>(g->U_c), p.min_cost = static_cast<T*>(g->min_cost), p.choice = g->choice, p.counts = g->counts;
+    p.cost_all = static_cast<T*>(g->cost_all), p.cand_all = static_cast<T*>(g->cand_all);
+    const int wpg = nmpc::kDwaThreads / 64;
+    hipLaunchKernelGGL(nmpc::dwa_step_kernel<T>, dim3((g->n_run + wpg - 1) / wpg), dim3(nmpc::kDwaThreads), lds, h->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // the kernel(s) of a variant may use `bytes` of dynamic LDS (beyond 48 KB a kernel has to be told)
 template <typename T>
 int allow_lds(const Variant& v, size_t bytes)
@@ -1828,6 +1892,8 @@ int nmpc_loop_post_f64(nmpc_handle h, const nmpc_loop_args* a) { return loop_ste
 
 int nmpc_kf_predict_f32(nmpc_handle h, const nmpc_kf_args* a) { return kf_predict<float>(h, a); }
 int nmpc_kf_predict_f64(nmpc_handle h, const nmpc_kf_args* a) { return kf_predict<double>(h, a); }
+int nmpc_dwa_step_f32(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<float>(h, a); }
+int nmpc_dwa_step_f64(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<double>(h, a); }
 
 int nmpc_last_kernel_ms(nmpc_handle h, float* ms)
 {

@@ -1,5 +1,9 @@
 """Batched closed-loop evaluator ("next" row f3): B independent warehouse scenarios advanced in lock-step on the device.
 
+Trackers: ``"mpc"`` (below) and ``"dwa"``, the reference's dynamic-window baseline (pkg_dwa_tracker/trajectory_tracker.py:304-355
+as main_base.py:303-321 drives it): ``nmpc_dwa_step_*`` (csrc/nmpc_dwa.h) takes the place of f1 + solve between the same
+``loop_pre`` / ``loop_post`` kernels, with the predictors ``None``, ``cvmp`` and ``kfmp``.
+
 Semantics of the reference's evaluation loop for the MPC tracker with the constant-velocity predictor (``cvmp``) or the
 Kalman-filter predictor (``kfmp``), the two predictor configurations of ``main_eva.py`` that need no network weights
 (``/root/reference/src``):
@@ -98,8 +102,16 @@ class BatchEvaluator:
                  human_stagger: float = 0.0, seed: int = 0, mode: str = "work",
                  tuning: Optional[Sequence[float]] = None, lin_vel_max: float = 1.5, warm_start: bool = False,
                  compact: Optional[bool] = None, fused: bool = True, n_hyp: int = 1, hyp_fan: float = 0.15,
-                 hyp_radius_growth: float = 0.05, predictor: str = "cvmp", kf_Q=None, kf_R=None, kf_P0=None):
-        """``predictor``: ``"cvmp"`` = the constant-velocity predictor; ``"kfmp"`` = the Kalman-filter predictor
+                 hyp_radius_growth: float = 0.05, predictor: Optional[str] = "cvmp", kf_Q=None, kf_R=None, kf_P0=None,
+                 tracker: str = "mpc", dwa_config=None):
+        """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
+        (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
+        :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
+        configuration's). It runs with ``predictor`` ``None`` (the pedestrians' current positions, as the reference without a
+        predictor), ``"cvmp"`` or ``"kfmp"`` (their mean positions per offset), on the fused path with ``n_hyp == 1``, and
+        creates no parameter vectors, multipliers or solver handles. Metrics, goal and collision rules are the shared ones.
+
+        ``predictor``: ``"cvmp"`` = the constant-velocity predictor; ``"kfmp"`` = the Kalman-filter predictor
         (constant-velocity model at the configuration's ``ts``; ``kf_Q`` [4,4], ``kf_R`` [2,2], ``kf_P0`` [4,4] default to
         the identities main_base.py:165 and ``KfmpInterface`` use). It needs ``n_hyp == 1`` and ``fused=True``. The filter
         runs over the whole past trajectory of every pedestrian at every step, so ``run(max_steps)`` keeps all of them on the
@@ -113,8 +125,26 @@ class BatchEvaluator:
         import torch
         self.torch = torch
         self.fused = fused
-        if predictor not in ("cvmp", "kfmp"):
-            raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp)")
+        if tracker not in ("mpc", "dwa"):
+            raise ValueError(f"tracker = {tracker!r} (mpc or dwa)")
+        if tracker == "mpc" and predictor is None:
+            raise ValueError("tracker = 'mpc' needs a predictor (cvmp or kfmp)")
+        if predictor not in ("cvmp", "kfmp") and not (tracker == "dwa" and predictor is None):
+            raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; None with tracker = 'dwa')")
+        if tracker == "dwa" and (max(1, int(n_hyp)) != 1 or not fused):
+            raise ValueError("tracker = 'dwa' needs n_hyp = 1 and fused = True")
+        self.tracker = tracker
+        self.dwa_config = None
+        if tracker == "dwa":
+            from .configs import DwaConfiguration
+            self.dwa_config = dwa_config if dwa_config is not None else DwaConfiguration()
+            if int(self.dwa_config.N_hor) != int(config.N_hor) or float(self.dwa_config.ts) != float(config.ts):
+                raise ValueError(f"dwa_config has N_hor = {self.dwa_config.N_hor}, ts = {self.dwa_config.ts}; the configuration "
+                                 f"{config.N_hor}, {config.ts}")
+            lin_vel_max = float(self.dwa_config.lin_vel_max)
+        # time_tracker: HIP events around every nmpc_dwa_step call; run() leaves the times (ms) in tracker_ms
+        self.time_tracker = False
+        self.tracker_ms: list = []
         if predictor == "kfmp" and (max(1, int(n_hyp)) != 1 or not fused):
             raise ValueError("predictor = 'kfmp' needs n_hyp = 1 and fused = True")
         self.predictor = predictor
@@ -128,7 +158,7 @@ class BatchEvaluator:
         self.dt = np.dtype(dtype)
         self.tdt = torch.float32 if self.dt == np.float32 else torch.float64
         self.dev = torch.device("cuda", config.device_id)
-        if config.axis_aligned == 0:
+        if config.axis_aligned == 0 and tracker == "mpc":
             # the pedestrians' obstacle rows are written here with angle = 0 (main_base.py:302), so the promise can be
             # made once instead of leaving the code path to the per-call scan of the batch (nmpc_hip.h, axis_aligned:
             # with 0 the path -- and with it the last bits of every result -- depends on the batch composition)
@@ -140,7 +170,7 @@ class BatchEvaluator:
         streamed = bool(li.global_table_f32 if self.dt == np.float32 else li.global_table_f64)
         # (obstacle table streamed from global memory -- e.g. N = 40, 160 rows: the library's automatic choice there is
         #  the cooperative kernel, whatever the batch size; pinning latency_waves would switch it off)
-        if config.latency_waves == 0 and not streamed and (robot_starts.shape[0] > 1024 if compact is None else compact):
+        if tracker == "mpc" and config.latency_waves == 0 and not streamed and (robot_starts.shape[0] > 1024 if compact is None else compact):
             # The batch shrinks as scenarios finish (compaction) and the library's automatic choice between its kernel
             # families follows the batch size. A scenario's closed-loop trajectory must not depend on who else is still
             # running, so either every plan computes the same bits -- fp32 with the obstacle table in registers:
@@ -162,7 +192,7 @@ class BatchEvaluator:
         # 3, 4 -- tests/test_gpu_options.py), so W follows the number of scenarios still running: as many wavefronts per
         # instance as stay resident together. One handle per W.
         self._h_by_waves = {}
-        if config.latency_waves >= 2:
+        if config.latency_waves >= 2 and tracker == "mpc":
             import copy
             self._n_simd = 4 * torch.cuda.get_device_properties(self.dev).multi_processor_count
             for w in (2, 3, 4):
@@ -200,6 +230,7 @@ class BatchEvaluator:
         self.stagger_replay: Optional[list] = None
         scale = {"safe": 0.2, "work": 0.8, "super": 1.0}[mode]
         self.base_speed = lin_vel_max * scale
+        self.speed_scale = scale
         self.lin_vel_max = lin_vel_max
         # global reference trajectories: TrajectoryTracker.get_ref_traj per scenario (host, once), padded
         # (the Monte-Carlo runs of one scenario share start and path: make_reference_scenarios has three distinct pairs
@@ -221,8 +252,19 @@ class BatchEvaluator:
                                    (0.0, 10.0, 0.0, 0.0, 0.0, 0.0, 0.0, 100.0, 10.0, 20.0), dtype=float))
         self.stcw = torch.full((self.N,), 10.0, dtype=self.tdt, device=self.dev)   # set_obstacle_weights(10, 10)
         self.dynw = torch.full((self.N,), 10.0, dtype=self.tdt, device=self.dev)
-        self.P = torch.empty(B, self.h.np_, dtype=self.tdt, device=self.dev)
         self.U = torch.empty(B, 2 * self.N, dtype=self.tdt, device=self.dev)
+        if tracker == "dwa":
+            # the node paths the deviation term measures against, padded with their last node; no solver state
+            pmax = max(2, max(len(p) for p in robot_paths))
+            nodes = np.stack([np.array([tuple(q)[:2] for q in p] + [tuple(p[-1])[:2]] * (pmax - len(p)), dtype=float) for p in robot_paths])
+            self.node_path = T(nodes)                                  # [B,Pmax,2]
+            self.node_len = torch.as_tensor([len(p) for p in robot_paths], dtype=torch.long, device=self.dev)
+            self.dwa_cap = self._dwa_capacity()
+            self.y = torch.zeros(B, 2 * self.N, dtype=self.tdt, device=self.dev)     # (nmpc_loop_args wants the arrays; never read)
+            self._Ua = torch.empty(B, 2 * self.N, dtype=self.tdt, device=self.dev)
+            self.dispatch_by_history, self.count_status, self.status_counts = False, False, []
+            return
+        self.P = torch.empty(B, self.h.np_, dtype=self.tdt, device=self.dev)
         self._Ua = torch.empty(B, 2 * self.N, dtype=self.tdt, device=self.dev)   # compacted batch of the running scenarios
         # dispatch order of a time step's solves from the evaluation counts of the previous one (nmpc_set_dispatch_order)
         self.dispatch_by_history, self.dispatch_min_batch = True, 32768   # (measured: -4 % at 16 384 scenarios, +10 % at 65 536)
@@ -235,6 +277,15 @@ class BatchEvaluator:
         # evaluation budget (nmpc_config.max_evaluations) cuts a solve off, and how often the loop runs on a converged answer
         self.count_status = False
         self.status_counts: list = []
+
+    def _dwa_capacity(self) -> int:
+        """Candidates per scenario the limits and resolutions can give (the bound nmpc_dwa_step checks ``cap`` against)."""
+        c = self.dwa_config
+
+        def axis(rng, acc, res):
+            w = min(rng, 2.0 * acc * float(self.ts))
+            return int(w / res * (1.0 + 1e-9)) + 1 if w > 0 else 1
+        return axis(c.lin_vel_max - c.lin_vel_min, c.lin_acc_max, c.vel_resolution) * axis(2.0 * c.ang_vel_max, c.ang_acc_max, c.ang_resolution)
 
     # ---------------------------------------------------------------------------------------------------------
     def _predict_cv(self):
@@ -401,6 +452,18 @@ class BatchEvaluator:
             kf.B, kf.H, kf.cap, kf.human_size = B, H, cap, HUMAN_SIZE
             kf.humans, kf.hcount, kf.dyn_c = self.humans.data_ptr(), self.hcount.data_ptr(), dyn_c.data_ptr()
             kf.kf_traj, kf.kf_len, kf.kf_P = kf_traj.data_ptr(), kf_len.data_ptr(), kf_P.data_ptr()
+        dw = None
+        if self.tracker == "dwa":
+            dwa_cost, dwa_choice = z(B), z(B, dtype=torch.int32, fill=0)
+            dwa_counts = z(B, 2, dtype=torch.int32, fill=0)
+            dw = _capi.NmpcDwaArgs().set_config(self.dwa_config, self.speed_scale)
+            dw.B, dw.H, dw.M, dw.Pmax, dw.cap = B, H, int(self.polys.shape[0]), int(self.node_path.shape[1]), self.dwa_cap
+            dw.dyn_mode = 1 if self.predictor is None else 2
+            dw.state_c, dw.last_u_c, dw.dyn_c = state_c.data_ptr(), last_u_c.data_ptr(), dyn_c.data_ptr()
+            dw.goal, dw.path, dw.path_len = self.goal.data_ptr(), self.node_path.data_ptr(), self.node_len.data_ptr()
+            dw.polys = self.polys.data_ptr() if self.polys.numel() else None
+            dw.min_cost, dw.choice, dw.counts = dwa_cost.data_ptr(), dwa_choice.data_ptr(), dwa_counts.data_ptr()
+        dwa_events = []
         kf_events = []
         solve_ms = []
         n_steps_run = 0
@@ -411,7 +474,7 @@ class BatchEvaluator:
             idx = torch.nonzero(alive, as_tuple=False).squeeze(1).contiguous() if self.compact else None
             nA = int(idx.numel()) if idx is not None else B
             full = nA == B
-            Pa = self.P if full else self.P[:nA]
+            Pa = None if dw is not None else self.P if full else self.P[:nA]
             Ua = self.U if full else self._Ua[:nA]
             ya = self.y if full else ya_buf[:nA]
             st = None
@@ -434,6 +497,21 @@ class BatchEvaluator:
                 self.h.kf_predict(self.dt, kf)
                 if self.time_predictor:
                     kf_events[-1][1].record()
+            if dw is not None:
+                # the dynamic-window tracker in place of f1 + solve: U_c = the chosen control, N times (nmpc_dwa.h)
+                dw.n_run, dw.run, dw.U_c = nA, a.run, Ua.data_ptr()
+                if self.time_tracker:
+                    dwa_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                    dwa_events[-1][0].record()
+                self.h.dwa_step(self.dt, dw)
+                if self.time_tracker:
+                    dwa_events[-1][1].record()
+                if record is not None:
+                    record.append(dict(robot=self.robot.cpu().numpy(), humans=self.humans.cpu().numpy(), alive=alive.bool().cpu().numpy(),
+                                       run=None if idx is None else idx.cpu().numpy(), U_c=Ua.cpu().numpy(), min_cost=dwa_cost[:nA].cpu().numpy(),
+                                       choice=dwa_choice[:nA].cpu().numpy(), counts=dwa_counts[:nA].cpu().numpy()))
+                self.h.loop_step(self.dt, a, post=True)
+                continue
             self.h.assemble_params(self.dt, nA, Pa, last_u_c, state_c, refs_c, speed_c, self.tuning, self.stcw, self.dynw,
                                    self.polys, dyn_c[:nA])
             if self.on_params is not None:
@@ -478,6 +556,9 @@ class BatchEvaluator:
         if kf_events:
             torch.cuda.synchronize(dev)
             self.predictor_ms = [e0.elapsed_time(e1) for e0, e1 in kf_events]
+        if dwa_events:
+            torch.cuda.synchronize(dev)
+            self.tracker_ms = [e0.elapsed_time(e1) for e0, e1 in dwa_events]
         alive_b, collision_b, complete_b = alive.bool(), collision.bool(), complete.bool()
         collision_b = collision_b | alive_b                                      # time-out, main_base.py:407-410
         T_run = n_steps_run
@@ -605,5 +686,5 @@ class BatchEvaluator:
             trajectory=torch.stack(traj, dim=1).cpu().numpy(), actions=A.cpu().numpy(), solve_ms=solve_ms)
 
     def close(self):
-        for h in set(self._h_by_waves.values()) | {self.h}:
+        for h in set(getattr(self, "_h_by_waves", {}).values()) | {self.h}:
             h.close()
