@@ -6,7 +6,7 @@ as main_base.py:303-321 drives it): ``nmpc_dwa_step_*`` (csrc/nmpc_dwa.h) takes 
 
 Semantics of the reference's evaluation loop for the MPC tracker with the constant-velocity predictor (``cvmp``) or the
 Kalman-filter predictor (``kfmp``), the two predictor configurations of ``main_eva.py`` that need no network weights
-(``/root/reference/src``):
+(the reference's ``src/``):
 
 * ``MainBase.run_once`` / ``run_one_step``                      main_base.py:267-346, 348-425
 * ``MainBase.run_cv_prediction`` + ``CvmpInterface``            main_base.py:238-264, interfaces/cvmp_interface.py:24-57
@@ -22,15 +22,26 @@ Kalman-filter predictor (``kfmp``), the two predictor configurations of ``main_e
 
 One time step = prediction -> obstacle rows -> reference windows -> ``nmpc_assemble_params`` (f1) ->
 ``nmpc_solve_batch`` -> first action -> agent motion -> metrics, for all scenarios at once; nothing leaves HBM
-between steps. Everything around the solve is two HIP kernels (``nmpc_loop_pre_*`` / ``nmpc_loop_post_*``,
-``csrc/nmpc_step.h``), with ``predictor="kfmp"`` a third between ``loop_pre`` and f1 that overwrites the obstacle rows
-(``nmpc_kf_predict_*``, ``csrc/nmpc_kf.h``; fused path only -- its independent check is tests/kf_reference.py); the torch expressions further down (``fused=False``) are the same arithmetic written out op by
-op -- they were the implementation of rounds 1-2 and stay as the independent check of the kernels. Where the reference runs ``max_num_run`` scenarios one after another (main_base.py:448-464), this
-runs them side by side. Pedestrian stagger uses a seeded torch generator (the reference's ``random`` is unseeded).
+between steps. ``BatchEvaluator._run_fused`` composes it from stages, each a HIP kernel launch on the compact buffers of the
+scenarios still running:
+
+1. ``nmpc_loop_pre_*`` (``csrc/nmpc_step.h``): constant-velocity obstacle rows, reference windows, speed reference;
+2. predictor stage, with ``predictor="kfmp"`` only: ``nmpc_kf_predict_*`` (``csrc/nmpc_kf.h``) overwrites the obstacle rows
+   (fused path only -- its independent check is tests/kf_reference.py);
+3. tracker stage: ``_mpc_step`` = f1, the ``on_params`` hook, ``_solve_step`` (warm start, handle by batch size, dispatch
+   order, status counts, ``_solve``); or ``_dwa_step`` = ``nmpc_dwa_step_*``;
+4. ``nmpc_loop_post_*``: first action, agent motion, metrics, flags.
+
+A run starts in ``_start_run`` (flags and metrics, one namespace with the ``_loop_args`` / ``_kf_args`` / ``_dwa_args`` buffers)
+and ends in ``_finish_run``. ``_run_torch`` (``fused=False``) is stages 1 and 4 written out op by op in torch around the same
+``_mpc_step`` -- the implementation of rounds 1-2, kept as the independent check of the kernels. Where the reference runs
+``max_num_run`` scenarios one after another (main_base.py:448-464), this runs them side by side. Pedestrian stagger
+(``_draw_stagger``) uses a seeded torch generator (the reference's ``random`` is unseeded).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -125,15 +136,16 @@ class BatchEvaluator:
         import torch
         self.torch = torch
         self.fused = fused
+        self.n_hyp, self.hyp_fan, self.hyp_grow = max(1, int(n_hyp)), float(hyp_fan), float(hyp_radius_growth)
         if tracker not in ("mpc", "dwa"):
             raise ValueError(f"tracker = {tracker!r} (mpc or dwa)")
         if tracker == "mpc" and predictor is None:
             raise ValueError("tracker = 'mpc' needs a predictor (cvmp or kfmp)")
         if predictor not in ("cvmp", "kfmp") and not (tracker == "dwa" and predictor is None):
             raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; None with tracker = 'dwa')")
-        if tracker == "dwa" and (max(1, int(n_hyp)) != 1 or not fused):
+        if tracker == "dwa" and (self.n_hyp != 1 or not fused):
             raise ValueError("tracker = 'dwa' needs n_hyp = 1 and fused = True")
-        self.tracker = tracker
+        self.tracker, self.predictor = tracker, predictor
         self.dwa_config = None
         if tracker == "dwa":
             from .configs import DwaConfiguration
@@ -142,80 +154,33 @@ class BatchEvaluator:
                 raise ValueError(f"dwa_config has N_hor = {self.dwa_config.N_hor}, ts = {self.dwa_config.ts}; the configuration "
                                  f"{config.N_hor}, {config.ts}")
             lin_vel_max = float(self.dwa_config.lin_vel_max)
-        # time_tracker: HIP events around every nmpc_dwa_step call; run() leaves the times (ms) in tracker_ms
-        self.time_tracker = False
-        self.tracker_ms: list = []
-        if predictor == "kfmp" and (max(1, int(n_hyp)) != 1 or not fused):
+        if predictor == "kfmp" and (self.n_hyp != 1 or not fused):
             raise ValueError("predictor = 'kfmp' needs n_hyp = 1 and fused = True")
-        self.predictor = predictor
         eye = lambda m, n: np.eye(n) if m is None else np.asarray(m, dtype=np.float64).reshape(n, n)
         self.kf_Q, self.kf_R, self.kf_P0 = eye(kf_Q, 4), eye(kf_R, 2), eye(kf_P0, 4)
-        # time_predictor: HIP events around every nmpc_kf_predict call; run() leaves the times (ms) in predictor_ms
-        self.time_predictor = False
-        self.predictor_ms: list = []
+        # time_predictor / time_tracker: HIP events around every nmpc_kf_predict / nmpc_dwa_step call; run() leaves the
+        # times (ms) in predictor_ms / tracker_ms
+        self.time_predictor, self.time_tracker = False, False
+        self.predictor_ms, self.tracker_ms = [], []
         self.time_solves = True     # record the HIP-event time of every batched solve (one event wait per time step)
-        self.cfg = config
         self.dt = np.dtype(dtype)
         self.tdt = torch.float32 if self.dt == np.float32 else torch.float64
         self.dev = torch.device("cuda", config.device_id)
-        if config.axis_aligned == 0 and tracker == "mpc":
-            # the pedestrians' obstacle rows are written here with angle = 0 (main_base.py:302), so the promise can be
-            # made once instead of leaving the code path to the per-call scan of the batch (nmpc_hip.h, axis_aligned:
-            # with 0 the path -- and with it the last bits of every result -- depends on the batch composition)
-            import copy
-            config = copy.copy(config)
-            config.axis_aligned = 1
-            self.cfg = config
-        li = _capi.layout_info(config)
-        streamed = bool(li.global_table_f32 if self.dt == np.float32 else li.global_table_f64)
-        # (obstacle table streamed from global memory -- e.g. N = 40, 160 rows: the library's automatic choice there is
-        #  the cooperative kernel, whatever the batch size; pinning latency_waves would switch it off)
-        if tracker == "mpc" and config.latency_waves == 0 and not streamed and (robot_starts.shape[0] > 1024 if compact is None else compact):
-            # The batch shrinks as scenarios finish (compaction) and the library's automatic choice between its kernel
-            # families follows the batch size. A scenario's closed-loop trajectory must not depend on who else is still
-            # running, so either every plan computes the same bits -- fp32 with the obstacle table in registers:
-            # nmpc_config.batch_invariant, and the library goes on choosing the fastest plan for what is left (latency
-            # kernels for the last few hundred scenarios) -- or, where the families agree to rounding only (fp64, LDS
-            # table), the family is fixed here from the initial batch.
-            import copy
-            config = copy.copy(config)
-            if self.dt == np.float32 and li.reg_slots_f32 > 0:
-                config.batch_invariant = 1
-            else:
-                n_simd = 4 * self.torch.cuda.get_device_properties(self.dev).multi_processor_count
-                config.latency_waves = 1 if robot_starts.shape[0] > 4 * n_simd else 2
-            self.cfg = config
+        B = self.B = robot_starts.shape[0]
+        self.compact = (B > 1024) if compact is None else bool(compact)
+        self.cfg = config = self._mpc_config(config) if tracker == "mpc" else config
         self.h = _capi.Handle(config)
         self.h.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-        # Within the latency-kernel family the number of wavefronts per instance does not change the result (the W
-        # candidates of a round are evaluated with the same arithmetic as one after the other; bit-identical for W = 2,
-        # 3, 4 -- tests/test_gpu_options.py), so W follows the number of scenarios still running: as many wavefronts per
-        # instance as stay resident together. One handle per W.
         self._h_by_waves = {}
-        if config.latency_waves >= 2 and tracker == "mpc":
-            import copy
-            self._n_simd = 4 * torch.cuda.get_device_properties(self.dev).multi_processor_count
-            for w in (2, 3, 4):
-                if w == config.latency_waves:
-                    self._h_by_waves[w] = self.h
-                else:
-                    c = copy.copy(config)
-                    c.latency_waves = w
-                    self._h_by_waves[w] = _capi.Handle(c)
-                    self._h_by_waves[w].set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+        # ---- the scenarios' state, common to both trackers
         self.N, self.ts = config.N_hor, config.ts
-        B = self.B = robot_starts.shape[0]
-        T = lambda x, dt=None: torch.as_tensor(np.ascontiguousarray(x), dtype=dt or self.tdt, device=self.dev)
+        T = self._tensor
         self.robot = T(robot_starts)                               # [B,3]
         self.goal = T(np.array([p[-1] for p in robot_paths], dtype=float))   # [B,2]
         self.humans = T(human_starts)                              # [B,H,2]
         self.H = self.humans.shape[1]
-        self.n_hyp, self.hyp_fan, self.hyp_grow = max(1, int(n_hyp)), float(hyp_fan), float(hyp_radius_growth)
         if self.H * self.n_hyp > config.Ndynobs:
             raise ValueError(f"{self.H} pedestrians x {self.n_hyp} hypotheses exceed Ndynobs = {config.Ndynobs}")
-        # hook for harvesting (scenarios.harvest_closed_loop): called as on_params(kt, idx, Pa) after the parameter
-        # vectors of time step kt have been assembled (idx = running scenarios of the compact batch, None = all)
-        self.on_params = None
         self.hpath = T(human_paths)                                # [B,H,W,2]
         self.hidx = torch.zeros(B, self.H, dtype=torch.long, device=self.dev)
         self.hist = self.humans[:, :, None, :].repeat(1, 1, 5, 1)  # last <= 5 positions, newest last
@@ -223,7 +188,6 @@ class BatchEvaluator:
         self.polys = T(map_polygons)                               # [M,4,2]
         self.stagger = float(human_stagger)
         self.warm_start = warm_start       # row f4 (extension): shifted previous solution as the initial guess
-        self.compact = (robot_starts.shape[0] > 1024) if compact is None else bool(compact)
         self.gen = torch.Generator(device=self.dev).manual_seed(seed)
         # replay hook for tests: a list of [B, H] tensors, one per pedestrian step, used instead of the generator
         # (the reference draws the stagger with python's `random`, basic_agent.py:64; a recording can be replayed)
@@ -248,35 +212,92 @@ class BatchEvaluator:
         pad = np.stack([np.concatenate([t, np.repeat(t[-1:], Lmax - len(t), axis=0)]) for t in trajs])
         self.ref_traj = T(pad)                                     # [B,Lmax,3]
         self.idx_ref = torch.zeros(B, dtype=torch.long, device=self.dev)
-        self.tuning = T(np.asarray(tuning if tuning is not None else
-                                   (0.0, 10.0, 0.0, 0.0, 0.0, 0.0, 0.0, 100.0, 10.0, 20.0), dtype=float))
-        self.stcw = torch.full((self.N,), 10.0, dtype=self.tdt, device=self.dev)   # set_obstacle_weights(10, 10)
-        self.dynw = torch.full((self.N,), 10.0, dtype=self.tdt, device=self.dev)
+        # the controls and multipliers of all scenarios and of the compacted batch of the running ones (the loop kernels
+        # want the arrays; the dynamic-window tracker never reads y)
         self.U = torch.empty(B, 2 * self.N, dtype=self.tdt, device=self.dev)
-        if tracker == "dwa":
-            # the node paths the deviation term measures against, padded with their last node; no solver state
-            pmax = max(2, max(len(p) for p in robot_paths))
-            nodes = np.stack([np.array([tuple(q)[:2] for q in p] + [tuple(p[-1])[:2]] * (pmax - len(p)), dtype=float) for p in robot_paths])
-            self.node_path = T(nodes)                                  # [B,Pmax,2]
-            self.node_len = torch.as_tensor([len(p) for p in robot_paths], dtype=torch.long, device=self.dev)
-            self.dwa_cap = self._dwa_capacity()
-            self.y = torch.zeros(B, 2 * self.N, dtype=self.tdt, device=self.dev)     # (nmpc_loop_args wants the arrays; never read)
-            self._Ua = torch.empty(B, 2 * self.N, dtype=self.tdt, device=self.dev)
-            self.dispatch_by_history, self.count_status, self.status_counts = False, False, []
-            return
-        self.P = torch.empty(B, self.h.np_, dtype=self.tdt, device=self.dev)
-        self._Ua = torch.empty(B, 2 * self.N, dtype=self.tdt, device=self.dev)   # compacted batch of the running scenarios
-        # dispatch order of a time step's solves from the evaluation counts of the previous one (nmpc_set_dispatch_order)
-        self.dispatch_by_history, self.dispatch_min_batch = True, 32768   # (measured: -4 % at 16 384 scenarios, +10 % at 65 536)
-        self._info = torch.zeros(B, 8, dtype=self.tdt, device=self.dev)
-        self._evals = torch.zeros(B, dtype=self.tdt, device=self.dev)
+        self._Ua = torch.empty(B, 2 * self.N, dtype=self.tdt, device=self.dev)
         self.y = torch.zeros(B, 2 * self.N, dtype=self.tdt, device=self.dev)
-        self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
+        # hook for harvesting (scenarios.harvest_closed_loop), MPC only: called as on_params(kt, idx, Pa) after the parameter
+        # vectors of time step kt have been assembled (idx = running scenarios of the compact batch, None = all)
+        self.on_params = None
+        # dispatch order of a time step's solves from the evaluation counts of the previous one (nmpc_set_dispatch_order)
+        self.dispatch_by_history, self.dispatch_min_batch = tracker == "mpc", 32768   # (measured: -4 % at 16 384 scenarios, +10 % at 65 536)
         # count_status: the exit statuses of every time step's solves are counted on the device (status_counts: one [4]
         # tensor per step -- Converged / NotConvergedIterations / NotConvergedOutOfTime / anything else) -- how often the
         # evaluation budget (nmpc_config.max_evaluations) cuts a solve off, and how often the loop runs on a converged answer
         self.count_status = False
         self.status_counts: list = []
+        if tracker == "mpc":
+            self._init_mpc(tuning)
+        else:
+            self._init_dwa(robot_paths)
+
+    def _tensor(self, x):
+        return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
+
+    def _full(self, *shape, dtype=None, fill=0.0):
+        return self.torch.full(shape, fill, dtype=dtype or self.tdt, device=self.dev)
+
+    def _mpc_config(self, config):
+        """The configuration the MPC handles are made from: the caller's, with the choices fixed that must not follow the batch."""
+        import copy
+        if config.axis_aligned == 0:
+            # the pedestrians' obstacle rows are written here with angle = 0 (main_base.py:302), so the promise can be
+            # made once instead of leaving the code path to the per-call scan of the batch (nmpc_hip.h, axis_aligned:
+            # with 0 the path -- and with it the last bits of every result -- depends on the batch composition)
+            config = copy.copy(config)
+            config.axis_aligned = 1
+        li = _capi.layout_info(config)
+        streamed = bool(li.global_table_f32 if self.dt == np.float32 else li.global_table_f64)
+        # (obstacle table streamed from global memory -- e.g. N = 40, 160 rows: the library's automatic choice there is
+        #  the cooperative kernel, whatever the batch size; pinning latency_waves would switch it off, ADVICE r2)
+        if config.latency_waves == 0 and not streamed and self.compact:
+            # The batch shrinks as scenarios finish (compaction) and the library's automatic choice between its kernel
+            # families follows the batch size. A scenario's closed-loop trajectory must not depend on who else is still
+            # running, so either every plan computes the same bits -- fp32 with the obstacle table in registers:
+            # nmpc_config.batch_invariant, and the library goes on choosing the fastest plan for what is left (latency
+            # kernels for the last few hundred scenarios) -- or, where the families agree to rounding only (fp64, LDS
+            # table), the family is fixed here from the initial batch.
+            config = copy.copy(config)
+            if self.dt == np.float32 and li.reg_slots_f32 > 0:
+                config.batch_invariant = 1
+            else:
+                n_simd = 4 * self.torch.cuda.get_device_properties(self.dev).multi_processor_count
+                config.latency_waves = 1 if self.B > 4 * n_simd else 2
+        return config
+
+    def _init_mpc(self, tuning):
+        """Solver state: parameter vectors, weights, evaluation counts, statuses, one handle per latency-kernel width."""
+        import copy
+        torch, B, config = self.torch, self.B, self.cfg
+        # Within the latency-kernel family the number of wavefronts per instance does not change the result (the W
+        # candidates of a round are evaluated with the same arithmetic as one after the other; bit-identical for W = 2,
+        # 3, 4 -- tests/test_gpu_options.py), so W follows the number of scenarios still running: as many wavefronts per
+        # instance as stay resident together. One handle per W.
+        if config.latency_waves >= 2:
+            self._n_simd = 4 * torch.cuda.get_device_properties(self.dev).multi_processor_count
+            for w in (2, 3, 4):
+                if w == config.latency_waves:
+                    self._h_by_waves[w] = self.h
+                else:
+                    c = copy.copy(config)
+                    c.latency_waves = w
+                    self._h_by_waves[w] = _capi.Handle(c)
+                    self._h_by_waves[w].set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+        self.tuning = self._tensor(np.asarray(tuning if tuning is not None else
+                                              (0.0, 10.0, 0.0, 0.0, 0.0, 0.0, 0.0, 100.0, 10.0, 20.0), dtype=float))
+        self.stcw, self.dynw = self._full(self.N, fill=10.0), self._full(self.N, fill=10.0)   # set_obstacle_weights(10, 10)
+        self.P = torch.empty(B, self.h.np_, dtype=self.tdt, device=self.dev)
+        self._info, self._evals = self._full(B, 8), self._full(B)
+        self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
+
+    def _init_dwa(self, robot_paths):
+        """The node paths the deviation term measures against, padded with their last node; no solver state."""
+        pmax = max(2, max(len(p) for p in robot_paths))
+        nodes = np.stack([np.array([tuple(q)[:2] for q in p] + [tuple(p[-1])[:2]] * (pmax - len(p)), dtype=float) for p in robot_paths])
+        self.node_path = self._tensor(nodes)                                  # [B,Pmax,2]
+        self.node_len = self.torch.as_tensor([len(p) for p in robot_paths], dtype=self.torch.long, device=self.dev)
+        self.dwa_cap = self._dwa_capacity()
 
     def _dwa_capacity(self) -> int:
         """Candidates per scenario the limits and resolutions can give (the bound nmpc_dwa_step checks ``cap`` against)."""
@@ -357,6 +378,18 @@ class BatchEvaluator:
         inside = (cross > 0).all(dim=2) | (cross < 0).all(dim=2)
         return torch.where(inside, torch.zeros_like(d), d).min(dim=1).values
 
+    def _draw_stagger(self):
+        """The [B, H] stagger of one pedestrian step, or None without one: the next recorded draw of ``stagger_replay``, else
+        sign x magnitude from the seeded generator (two calls, in this order: a seed fixes the run)."""
+        torch = self.torch
+        if self.stagger_replay is not None:
+            return self.stagger_replay.pop(0).to(self.tdt).contiguous()
+        if self.stagger > 0:
+            sign = torch.randint(0, 2, (self.B, self.H), generator=self.gen, device=self.dev) * 2 - 1
+            mag = torch.randint(0, 11, (self.B, self.H), generator=self.gen, device=self.dev).to(self.tdt) / 10
+            return (sign.to(self.tdt) * mag * self.stagger).contiguous()
+        return None
+
     def _step_humans(self):
         torch = self.torch
         W = self.hpath.shape[2]
@@ -368,14 +401,8 @@ class BatchEvaluator:
         tgt = torch.gather(self.hpath, 2, self.hidx.clamp(max=W - 1)[..., None, None].expand(-1, -1, 1, 2))[:, :, 0]
         dist = torch.linalg.norm(tgt - self.humans, dim=-1).clamp(min=1e-12)
         dire = (tgt - self.humans) / dist[..., None]
-        if self.stagger_replay is not None:
-            st = self.stagger_replay.pop(0).to(self.tdt)[..., None]
-        elif self.stagger > 0:
-            sign = torch.randint(0, 2, dist.shape, generator=self.gen, device=self.dev) * 2 - 1
-            mag = torch.randint(0, 11, dist.shape, generator=self.gen, device=self.dev).to(self.tdt) / 10
-            st = (sign.to(self.tdt) * mag * self.stagger)[..., None]
-        else:
-            st = 0.0
+        st = self._draw_stagger()
+        st = 0.0 if st is None else st[..., None]
         new = self.humans + self.ts * (dire * HUMAN_VMAX + st)                   # omnidirectional model
         self.humans = torch.where(moving[..., None], new, self.humans)
         # past_traj grows only while the pedestrian moves (basic_agent.py:72-82)
@@ -396,94 +423,178 @@ class BatchEvaluator:
         device->host copy per step."""
         return self._run_fused(max_steps, record) if self.fused else self._run_torch(max_steps, record)
 
-    def _run_fused(self, max_steps, record):
-        """The time step as two HIP kernels around f1 + solve (csrc/nmpc_step.h)."""
-        torch = self.torch
-        B, N, H = self.B, self.N, self.H
-        dev, tdt = self.dev, self.tdt
-        z = lambda *shape, dtype=tdt, fill=0.0: torch.full(shape, fill, dtype=dtype, device=dev)
-        alive = z(B, dtype=torch.uint8, fill=1)
-        collision, complete = z(B, dtype=torch.uint8, fill=0), z(B, dtype=torch.uint8, fill=0)
-        steps = z(B, dtype=torch.long, fill=0)
-        last_u = z(B, 2)
-        traj = torch.empty(B, max_steps + 1, 3, dtype=tdt, device=dev)
-        traj[:, 0] = self.robot
-        acts = z(B, max(max_steps, 1), 2, fill=float("nan"))
-        clr_dyn = z(B, fill=float("inf"))
-        clr_stc = self._polygon_distance(self.robot[:, :2]).contiguous()
+    # ---- one run: its buffers, the argument structs of the stage kernels, its result ---------------------------
+    def _start_run(self, flag_dtype):
+        """Flags, counters and metrics of a run that starts now (``flag_dtype``: uint8 for the kernels, bool for torch)."""
+        torch, B, z = self.torch, self.B, self._full
         d0 = torch.cdist(self.robot[:, None, :2], self.ref_traj[:, :, :2])[:, 0]
         dev_sum = d0.min(dim=1).values.clone()      # trajectory metrics include the start state (robot.past_traj[0])
-        dev_max = dev_sum.clone()
-        n_traj = z(B, fill=1.0)
-        state_c, last_u_c, refs_c, speed_c = z(B, 3), z(B, 2), z(B, N, 3), z(B)
-        dyn_c = z(B, H * self.n_hyp, N + 1, 6)
-        ya_buf = z(B, 2 * N)
-        self.hidx = self.hidx.contiguous()
-        self.hcount = self.hcount.contiguous()
-        self.idx_ref = self.idx_ref.contiguous()
-        self.hist = self.hist.contiguous()
-        self.humans = self.humans.contiguous()
-        self.robot = self.robot.contiguous()
-        ref_len = self.ref_len.to(torch.long).contiguous()
+        return SimpleNamespace(
+            alive=z(B, dtype=flag_dtype, fill=1), collision=z(B, dtype=flag_dtype, fill=0), complete=z(B, dtype=flag_dtype, fill=0),
+            steps=z(B, dtype=torch.long, fill=0), last_u=z(B, 2), clr_dyn=z(B, fill=float("inf")),
+            clr_stc=self._polygon_distance(self.robot[:, :2]).contiguous(), dev_sum=dev_sum, dev_max=dev_sum.clone(), n_traj=z(B, fill=1.0))
+
+    def _finish_run(self, r, traj, acts, solve_ms) -> EvaluationResult:
+        """``traj`` [B, T+1, 3] and ``acts`` [B, T, 2] of the T lock-steps run -> the result on the host."""
+        torch = self.torch
+        T_run = acts.shape[1]
+        collision = r.collision.bool() | r.alive.bool()                          # time-out, main_base.py:407-410
+        # rows after a scenario's end repeat its last state
+        t_idx = torch.minimum(torch.arange(T_run + 1, device=self.dev)[None, :], r.steps.clamp(max=T_run)[:, None])
+        traj = torch.gather(traj, 1, t_idx[..., None].expand(-1, -1, 3))
+        return EvaluationResult(
+            collision=collision.cpu().numpy(), complete=r.complete.bool().cpu().numpy(), steps=r.steps.cpu().numpy(),
+            smoothness=action_smoothness(acts).cpu().numpy(), clearance=r.clr_stc.cpu().numpy(), clearance_dyn=r.clr_dyn.cpu().numpy(),
+            deviation=torch.stack([r.dev_sum / r.n_traj, r.dev_max], dim=1).cpu().numpy(),
+            trajectory=traj.cpu().numpy(), actions=acts.cpu().numpy(), solve_ms=solve_ms)
+
+    def _loop_args(self, r, max_steps):
+        """``NmpcLoopArgs`` of a run: the evaluator's state (made contiguous: the kernels update it in place), the run's
+        flags and metrics, and the compact buffers of the running scenarios that the stages between pre and post read."""
+        torch, B, N, H, z = self.torch, self.B, self.N, self.H, self._full
+        r.traj = torch.empty(B, max_steps + 1, 3, dtype=self.tdt, device=self.dev)
+        r.traj[:, 0] = self.robot
+        r.acts = z(B, max(max_steps, 1), 2, fill=float("nan"))
+        r.state_c, r.last_u_c, r.refs_c, r.speed_c = z(B, 3), z(B, 2), z(B, N, 3), z(B)
+        r.dyn_c = z(B, H * self.n_hyp, N + 1, 6)
+        r.ya_buf = z(B, 2 * N)
+        r.ref_len = self.ref_len.to(torch.long).contiguous()
+        for name in ("hidx", "hcount", "idx_ref", "hist", "humans", "robot"):
+            setattr(self, name, getattr(self, name).contiguous())
         a = _capi.NmpcLoopArgs()
         a.B, a.H, a.W, a.Lmax, a.M, a.max_steps = B, H, int(self.hpath.shape[2]), int(self.ref_traj.shape[1]), int(self.polys.shape[0]), max(max_steps, 1)
         a.base_speed, a.lin_vel_max, a.human_size, a.human_vmax = self.base_speed, self.lin_vel_max, HUMAN_SIZE, HUMAN_VMAX
         a.n_hyp, a.hyp_fan_rad, a.hyp_radius0, a.hyp_radius_growth = self.n_hyp, self.hyp_fan, HUMAN_SIZE, self.hyp_grow
-        for name, t in (("robot", self.robot), ("last_u", last_u), ("humans", self.humans), ("hist", self.hist), ("hcount", self.hcount),
-                        ("hidx", self.hidx), ("hpath", self.hpath), ("ref_traj", self.ref_traj), ("ref_len", ref_len),
-                        ("idx_ref", self.idx_ref), ("goal", self.goal), ("polys", self.polys), ("alive", alive),
-                        ("collision", collision), ("complete", complete), ("steps", steps), ("clr_dyn", clr_dyn),
-                        ("clr_stc", clr_stc), ("dev_sum", dev_sum), ("dev_max", dev_max), ("n_traj", n_traj), ("traj", traj),
-                        ("acts", acts), ("state_c", state_c), ("last_u_c", last_u_c), ("refs_c", refs_c), ("speed_c", speed_c),
-                        ("dyn_c", dyn_c), ("U", self.U), ("y", self.y)):
-            assert t.is_contiguous(), name
-            setattr(a, name, t.data_ptr())
-        kf = None
-        if self.predictor == "kfmp":
-            # past_traj of every pedestrian (nmpc_kf_predict appends the current position while hcount grows) and the
-            # run's covariance: main_base.py:158-172 makes a new interface object, i.e. P = P0, per run
-            cap = max(max_steps, 1) + 1
-            kf_traj = z(B, H, cap, 2)
-            kf_len = z(B, H, dtype=torch.long, fill=0)
-            kf_P = torch.as_tensor(self.kf_P0, dtype=tdt, device=dev).repeat(B, 1, 1).contiguous()
-            ts = float(self.ts)
-            kf = _capi.NmpcKfArgs().set_matrices([[1, 0, ts, 0], [0, 1, 0, ts], [0, 0, 1, 0], [0, 0, 0, 1]],
-                                                 [[1, 0, 0, 0], [0, 1, 0, 0]], self.kf_Q, self.kf_R)      # zfilter.model_CV(ts)
-            kf.B, kf.H, kf.cap, kf.human_size = B, H, cap, HUMAN_SIZE
-            kf.humans, kf.hcount, kf.dyn_c = self.humans.data_ptr(), self.hcount.data_ptr(), dyn_c.data_ptr()
-            kf.kf_traj, kf.kf_len, kf.kf_P = kf_traj.data_ptr(), kf_len.data_ptr(), kf_P.data_ptr()
-        dw = None
-        if self.tracker == "dwa":
-            dwa_cost, dwa_choice = z(B), z(B, dtype=torch.int32, fill=0)
-            dwa_counts = z(B, 2, dtype=torch.int32, fill=0)
-            dw = _capi.NmpcDwaArgs().set_config(self.dwa_config, self.speed_scale)
-            dw.B, dw.H, dw.M, dw.Pmax, dw.cap = B, H, int(self.polys.shape[0]), int(self.node_path.shape[1]), self.dwa_cap
-            dw.dyn_mode = 1 if self.predictor is None else 2
-            dw.state_c, dw.last_u_c, dw.dyn_c = state_c.data_ptr(), last_u_c.data_ptr(), dyn_c.data_ptr()
-            dw.goal, dw.path, dw.path_len = self.goal.data_ptr(), self.node_path.data_ptr(), self.node_len.data_ptr()
-            dw.polys = self.polys.data_ptr() if self.polys.numel() else None
-            dw.min_cost, dw.choice, dw.counts = dwa_cost.data_ptr(), dwa_choice.data_ptr(), dwa_counts.data_ptr()
-        dwa_events = []
-        kf_events = []
-        solve_ms = []
-        n_steps_run = 0
+        for src, names in ((self, ("robot", "humans", "hist", "hcount", "hidx", "hpath", "ref_traj", "idx_ref", "goal", "polys", "U", "y")),
+                           (r, ("last_u", "ref_len", "alive", "collision", "complete", "steps", "clr_dyn", "clr_stc", "dev_sum", "dev_max",
+                                "n_traj", "traj", "acts", "state_c", "last_u_c", "refs_c", "speed_c", "dyn_c"))):
+            for name in names:
+                assert getattr(src, name).is_contiguous(), name
+                setattr(a, name, getattr(src, name).data_ptr())
+        return a
+
+    def _kf_args(self, r, max_steps):
+        """``NmpcKfArgs`` of a run: past_traj of every pedestrian (nmpc_kf_predict appends the current position while hcount
+        grows) and the run's covariance: main_base.py:158-172 makes a new interface object, i.e. P = P0, per run."""
+        B, H, ts, z = self.B, self.H, float(self.ts), self._full
+        cap = max(max_steps, 1) + 1
+        r.kf_traj, r.kf_len = z(B, H, cap, 2), z(B, H, dtype=self.torch.long, fill=0)
+        r.kf_P = self.torch.as_tensor(self.kf_P0, dtype=self.tdt, device=self.dev).repeat(B, 1, 1).contiguous()
+        kf = _capi.NmpcKfArgs().set_matrices([[1, 0, ts, 0], [0, 1, 0, ts], [0, 0, 1, 0], [0, 0, 0, 1]],
+                                             [[1, 0, 0, 0], [0, 1, 0, 0]], self.kf_Q, self.kf_R)      # zfilter.model_CV(ts)
+        kf.B, kf.H, kf.cap, kf.human_size = B, H, cap, HUMAN_SIZE
+        kf.humans, kf.hcount, kf.dyn_c = self.humans.data_ptr(), self.hcount.data_ptr(), r.dyn_c.data_ptr()
+        kf.kf_traj, kf.kf_len, kf.kf_P = r.kf_traj.data_ptr(), r.kf_len.data_ptr(), r.kf_P.data_ptr()
+        return kf
+
+    def _dwa_args(self, r):
+        """``NmpcDwaArgs`` of a run: the compact buffers ``loop_pre`` fills in, the node paths, the outputs per scenario."""
+        B, z, i32 = self.B, self._full, self.torch.int32
+        r.dwa_cost, r.dwa_choice, r.dwa_counts = z(B), z(B, dtype=i32, fill=0), z(B, 2, dtype=i32, fill=0)
+        dw = _capi.NmpcDwaArgs().set_config(self.dwa_config, self.speed_scale)
+        dw.B, dw.H, dw.M, dw.Pmax, dw.cap = B, self.H, int(self.polys.shape[0]), int(self.node_path.shape[1]), self.dwa_cap
+        dw.dyn_mode = 1 if self.predictor is None else 2
+        dw.state_c, dw.last_u_c, dw.dyn_c = r.state_c.data_ptr(), r.last_u_c.data_ptr(), r.dyn_c.data_ptr()
+        dw.goal, dw.path, dw.path_len = self.goal.data_ptr(), self.node_path.data_ptr(), self.node_len.data_ptr()
+        dw.polys = self.polys.data_ptr() if self.polys.numel() else None
+        dw.min_cost, dw.choice, dw.counts = r.dwa_cost.data_ptr(), r.dwa_choice.data_ptr(), r.dwa_counts.data_ptr()
+        return dw
+
+    def _timed(self, call, flag):
+        """A stage call and the list of its HIP event pairs: ``call`` itself and None, or, with the stage's timing flag set,
+        ``call`` between two events that are appended to the list."""
+        if not flag:
+            return call, None
+        Event, events = self.torch.cuda.Event, []
+
+        def timed(*args):
+            events.append((Event(enable_timing=True), Event(enable_timing=True)))
+            events[-1][0].record()
+            call(*args)
+            events[-1][1].record()
+        return timed, events
+
+    def _record_entry(self, alive):
+        """What a time step saw, on the host; the tracker stage adds what it produced."""
+        return dict(robot=self.robot.cpu().numpy(), humans=self.humans.cpu().numpy(), alive=alive.bool().cpu().numpy())
+
+    # ---- the tracker stage ----------------------------------------------------------------------------------------
+    def _solve_step(self, kt, idx, nA, Pa, Ua, ya, rec):
+        """The solves of time step ``kt`` for the ``nA`` running scenarios (``idx``, None = all): ``Pa`` -> ``Ua``, ``ya``
+        in / out. Returns the handle that ran them (its ``last_kernel_ms()`` is the step's solve time)."""
+        torch = self.torch
+        full = nA == self.B
+        if rec is not None:
+            rec["y_in"] = self.y.cpu().numpy()
+        u0 = None
+        if self.warm_start and kt > 0:
+            shifted = torch.cat([self.U[:, 2:], self.U[:, -2:]], dim=1)
+            u0 = shifted.contiguous() if full else shifted.index_select(0, idx).contiguous()
+        hs = self.h
+        if self._h_by_waves:      # latency-kernel family: W by the size of the running batch (results unchanged)
+            cap = 3 * self._n_simd if self.dt == np.float32 else 2 * self._n_simd     # resident wavefronts
+            hs = self._h_by_waves[min(4, max(2, cap // max(nA, 1)))]
+        # longest first: the evaluation counts of the previous time step rank this step's solves (a scenario that
+        # was hard a moment ago still is); pure scheduling -- the results do not depend on the order
+        info = None
+        if self.dispatch_by_history and nA >= self.dispatch_min_batch:
+            if kt > 0:
+                prev = self._evals if full else self._evals.index_select(0, idx)
+                hs.set_dispatch_order(torch.argsort(prev, descending=True, stable=True).to(torch.int32))
+            info = self._info[:nA]
+        # (-2: a solver put into _solve that does not report statuses leaves them uncounted)
+        st_buf = self.status[:nA].fill_(-2) if self.count_status else None
+        self._solve(hs, Pa, nA, Ua, u0, ya, kt > 0, info, status=st_buf)
+        if st_buf is not None:
+            self.status_counts.append(torch.bincount(st_buf.clamp(min=-1, max=3) + 1, minlength=5)[1:])
+        if info is not None:
+            if full:
+                self._evals.copy_(info[:, 4])
+            else:
+                self._evals.index_copy_(0, idx, info[:, 4].contiguous())
+        if rec is not None:
+            rec["P"] = (self.P if full else torch.zeros_like(self.P).index_copy_(0, idx, Pa)).cpu().numpy()
+        return hs
+
+    def _mpc_step(self, r, kt, idx, nA, Ua, ya, rec):
+        """The MPC tracker on the compact buffers of the running scenarios (``loop_pre``'s, or the torch path's): f1, the
+        harvesting hook, the solves."""
+        Pa = self.P if nA == self.B else self.P[:nA]
+        self.h.assemble_params(self.dt, nA, Pa, r.last_u_c, r.state_c, r.refs_c, r.speed_c, self.tuning, self.stcw, self.dynw,
+                               self.polys, r.dyn_c[:nA])
+        if self.on_params is not None:
+            self.on_params(kt, idx, Pa)
+        return self._solve_step(kt, idx, nA, Pa, Ua, ya, rec)
+
+    def _dwa_step(self, r, dw, dwa_step, idx, nA, Ua, rec):
+        """The dynamic-window tracker in place of f1 + solve: U_c = the chosen control, N times (nmpc_dwa.h). There is no
+        solve, so no handle is returned."""
+        dwa_step(self.dt, dw)
+        if rec is not None:
+            rec.update(run=None if idx is None else idx.cpu().numpy(), U_c=Ua.cpu().numpy(), min_cost=r.dwa_cost[:nA].cpu().numpy(),
+                       choice=r.dwa_choice[:nA].cpu().numpy(), counts=r.dwa_counts[:nA].cpu().numpy())
+
+    # ---- the time step --------------------------------------------------------------------------------------------
+    def _run_fused(self, max_steps, record):
+        """The time step as HIP kernels (csrc/nmpc_step.h): ``loop_pre`` -> predictor stage -> tracker stage -> ``loop_post``."""
+        torch, B = self.torch, self.B
+        r = self._start_run(torch.uint8)
+        a = self._loop_args(r, max_steps)
+        kf = self._kf_args(r, max_steps) if self.predictor == "kfmp" else None
+        dw = self._dwa_args(r) if self.tracker == "dwa" else None
+        kf_predict, kf_events = self._timed(self.h.kf_predict, self.time_predictor)
+        dwa_step, dwa_events = self._timed(self.h.dwa_step, self.time_tracker)
+        solve_ms, n_steps_run = [], 0
         for kt in range(max_steps):
-            if not bool(alive.any()):
+            if not bool(r.alive.any()):
                 break
             n_steps_run = kt + 1
-            idx = torch.nonzero(alive, as_tuple=False).squeeze(1).contiguous() if self.compact else None
+            idx = torch.nonzero(r.alive, as_tuple=False).squeeze(1).contiguous() if self.compact else None
             nA = int(idx.numel()) if idx is not None else B
             full = nA == B
-            Pa = None if dw is not None else self.P if full else self.P[:nA]
             Ua = self.U if full else self._Ua[:nA]
-            ya = self.y if full else ya_buf[:nA]
-            st = None
-            if self.stagger_replay is not None:
-                st = self.stagger_replay.pop(0).to(tdt).contiguous()
-            elif self.stagger > 0:
-                sign = torch.randint(0, 2, (B, H), generator=self.gen, device=dev) * 2 - 1
-                mag = torch.randint(0, 11, (B, H), generator=self.gen, device=dev).to(tdt) / 10
-                st = (sign.to(tdt) * mag * self.stagger).contiguous()
+            ya = self.y if full else r.ya_buf[:nA]
+            st = self._draw_stagger()
             a.n_run, a.step = nA, kt
             a.run = None if full else idx.data_ptr()
             a.stagger = None if st is None else st.data_ptr()
@@ -491,108 +602,35 @@ class BatchEvaluator:
             self.h.loop_step(self.dt, a, post=False)
             if kf is not None:
                 kf.n_run, kf.run = nA, a.run
-                if self.time_predictor:
-                    kf_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-                    kf_events[-1][0].record()
-                self.h.kf_predict(self.dt, kf)
-                if self.time_predictor:
-                    kf_events[-1][1].record()
+                kf_predict(self.dt, kf)
+            rec = None if record is None else self._record_entry(r.alive)
             if dw is not None:
-                # the dynamic-window tracker in place of f1 + solve: U_c = the chosen control, N times (nmpc_dwa.h)
                 dw.n_run, dw.run, dw.U_c = nA, a.run, Ua.data_ptr()
-                if self.time_tracker:
-                    dwa_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-                    dwa_events[-1][0].record()
-                self.h.dwa_step(self.dt, dw)
-                if self.time_tracker:
-                    dwa_events[-1][1].record()
-                if record is not None:
-                    record.append(dict(robot=self.robot.cpu().numpy(), humans=self.humans.cpu().numpy(), alive=alive.bool().cpu().numpy(),
-                                       run=None if idx is None else idx.cpu().numpy(), U_c=Ua.cpu().numpy(), min_cost=dwa_cost[:nA].cpu().numpy(),
-                                       choice=dwa_choice[:nA].cpu().numpy(), counts=dwa_counts[:nA].cpu().numpy()))
-                self.h.loop_step(self.dt, a, post=True)
-                continue
-            self.h.assemble_params(self.dt, nA, Pa, last_u_c, state_c, refs_c, speed_c, self.tuning, self.stcw, self.dynw,
-                                   self.polys, dyn_c[:nA])
-            if self.on_params is not None:
-                self.on_params(kt, idx, Pa)
-            if record is not None:
-                rec = dict(robot=self.robot.cpu().numpy(), humans=self.humans.cpu().numpy(), alive=alive.bool().cpu().numpy(),
-                           y_in=self.y.cpu().numpy())
-            u0 = None
-            if self.warm_start and kt > 0:
-                shifted = torch.cat([self.U[:, 2:], self.U[:, -2:]], dim=1)
-                u0 = shifted.contiguous() if full else shifted.index_select(0, idx).contiguous()
-            hs = self.h
-            if self._h_by_waves:      # latency-kernel family: W by the size of the running batch (results unchanged)
-                cap = 3 * self._n_simd if self.dt == np.float32 else 2 * self._n_simd     # resident wavefronts
-                hs = self._h_by_waves[min(4, max(2, cap // max(nA, 1)))]
-            if self.dispatch_by_history and nA >= self.dispatch_min_batch:
-                if kt > 0:
-                    prev = self._evals if full else self._evals.index_select(0, idx)
-                    hs.set_dispatch_order(torch.argsort(prev, descending=True, stable=True).to(torch.int32))
-                info = self._info[:nA]
+                hs = self._dwa_step(r, dw, dwa_step, idx, nA, Ua, rec)
             else:
-                info = None
-            if self.count_status:
-                st_buf = self.status[:nA]
-                st_buf.fill_(-2)      # (a solver put into _solve that does not report statuses leaves them uncounted)
-                self._solve(hs, Pa, nA, Ua, u0, ya, kt > 0, info, status=st_buf)
-                self.status_counts.append(torch.bincount(st_buf.clamp(min=-1, max=3) + 1, minlength=5)[1:])
-            else:
-                self._solve(hs, Pa, nA, Ua, u0, ya, kt > 0, info)
-            if info is not None:
-                if full:
-                    self._evals.copy_(info[:, 4])
-                else:
-                    self._evals.index_copy_(0, idx, info[:, 4].contiguous())
+                hs = self._mpc_step(r, kt, idx, nA, Ua, ya, rec)
             self.h.loop_step(self.dt, a, post=True)
-            if record is not None:
-                Pfull = self.P if full else torch.zeros_like(self.P).index_copy_(0, idx, Pa)
-                rec.update(P=Pfull.cpu().numpy(), U=self.U.cpu().numpy())
+            if rec is not None:
+                if hs is not None:
+                    rec["U"] = self.U.cpu().numpy()
                 record.append(rec)
-            if self.time_solves:
+            if hs is not None and self.time_solves:
                 solve_ms.append(hs.last_kernel_ms())
-        if kf_events:
-            torch.cuda.synchronize(dev)
-            self.predictor_ms = [e0.elapsed_time(e1) for e0, e1 in kf_events]
-        if dwa_events:
-            torch.cuda.synchronize(dev)
-            self.tracker_ms = [e0.elapsed_time(e1) for e0, e1 in dwa_events]
-        alive_b, collision_b, complete_b = alive.bool(), collision.bool(), complete.bool()
-        collision_b = collision_b | alive_b                                      # time-out, main_base.py:407-410
-        T_run = n_steps_run
-        A = acts[:, :T_run]
-        # rows after a scenario's end repeat its last state
-        trj = traj[:, :T_run + 1]
-        last = steps.clamp(max=T_run)
-        t_idx = torch.minimum(torch.arange(T_run + 1, device=dev)[None, :], last[:, None])
-        trj = torch.gather(trj, 1, t_idx[..., None].expand(-1, -1, 3))
-        smooth = action_smoothness(A)
-        return EvaluationResult(
-            collision=collision_b.cpu().numpy(), complete=complete_b.cpu().numpy(), steps=steps.cpu().numpy(),
-            smoothness=smooth.cpu().numpy(), clearance=clr_stc.cpu().numpy(), clearance_dyn=clr_dyn.cpu().numpy(),
-            deviation=torch.stack([dev_sum / n_traj, dev_max], dim=1).cpu().numpy(),
-            trajectory=trj.cpu().numpy(), actions=A.cpu().numpy(), solve_ms=solve_ms)
+        for name, events in (("predictor_ms", kf_events), ("tracker_ms", dwa_events)):
+            if events:
+                torch.cuda.synchronize(self.dev)
+                setattr(self, name, [e0.elapsed_time(e1) for e0, e1 in events])
+        return self._finish_run(r, r.traj[:, :n_steps_run + 1], r.acts[:, :n_steps_run], solve_ms)
 
     def _run_torch(self, max_steps: int = 120, record: Optional[list] = None) -> EvaluationResult:
         """The same time step written out as torch expressions (rounds 1-2): the independent check of the kernels."""
         torch = self.torch
         B, N, ts = self.B, self.N, self.ts
-        alive = torch.ones(B, dtype=torch.bool, device=self.dev)
-        collision = torch.zeros(B, dtype=torch.bool, device=self.dev)
-        complete = torch.zeros(B, dtype=torch.bool, device=self.dev)
-        steps = torch.zeros(B, dtype=torch.long, device=self.dev)
-        last_u = torch.zeros(B, 2, dtype=self.tdt, device=self.dev)
+        r = self._start_run(torch.bool)
         traj = [self.robot.clone()]
         acts, solve_ms = [], []
-        clr_dyn = torch.full((B,), float("inf"), dtype=self.tdt, device=self.dev)
-        clr_stc = self._polygon_distance(self.robot[:, :2])
-        d0 = torch.cdist(self.robot[:, None, :2], self.ref_traj[:, :, :2])[:, 0]
-        dev_sum = d0.min(dim=1).values.clone()      # trajectory metrics include the start state (robot.past_traj[0])
-        dev_max = dev_sum.clone()
-        n_traj = torch.ones(B, dtype=self.tdt, device=self.dev)
         for kt in range(max_steps):
+            alive = r.alive
             if not bool(alive.any()):
                 break
             dyn = self._predict_cv()
@@ -607,84 +645,44 @@ class BatchEvaluator:
             nA = int(idx.numel()) if idx is not None else B
             full = nA == B
             sel = (lambda x: x.contiguous()) if full else (lambda x: x.index_select(0, idx).contiguous())
-            Pa = self.P if full else self.P[:nA]
             Ua = self.U if full else self._Ua[:nA]
             ya = self.y if full else self.y.index_select(0, idx).contiguous()
-            self.h.assemble_params(self.dt, nA, Pa, sel(last_u), sel(self.robot), sel(refs), sel(speed),
-                                   self.tuning, self.stcw, self.dynw, self.polys, sel(dyn))
-            if self.on_params is not None:
-                self.on_params(kt, idx, Pa)
-            if record is not None:
-                rec = dict(robot=self.robot.cpu().numpy(), humans=self.humans.cpu().numpy(), alive=alive.cpu().numpy(),
-                           y_in=self.y.cpu().numpy())
-            u0 = None
-            if self.warm_start and kt > 0:
-                u0 = sel(torch.cat([self.U[:, 2:], self.U[:, -2:]], dim=1))
-            # longest first: the evaluation counts of the previous time step rank this step's solves (a scenario that
-            # was hard a moment ago still is); pure scheduling -- the results do not depend on the order
-            hs = self.h
-            if self._h_by_waves:      # latency-kernel family: W by the size of the running batch (results unchanged)
-                cap = 3 * self._n_simd if self.dt == np.float32 else 2 * self._n_simd     # resident wavefronts
-                hs = self._h_by_waves[min(4, max(2, cap // max(nA, 1)))]
-            if self.dispatch_by_history and nA >= self.dispatch_min_batch:
-                if kt > 0:
-                    prev = self._evals if full else self._evals.index_select(0, idx)
-                    hs.set_dispatch_order(torch.argsort(prev, descending=True, stable=True).to(torch.int32))
-                info = self._info[:nA]
-            else:
-                info = None
-            if self.count_status:
-                st_buf = self.status[:nA]
-                st_buf.fill_(-2)      # (a solver put into _solve that does not report statuses leaves them uncounted)
-                self._solve(hs, Pa, nA, Ua, u0, ya, kt > 0, info, status=st_buf)
-                self.status_counts.append(torch.bincount(st_buf.clamp(min=-1, max=3) + 1, minlength=5)[1:])
-            else:
-                self._solve(hs, Pa, nA, Ua, u0, ya, kt > 0, info)
-            if info is not None:
-                if full:
-                    self._evals.copy_(info[:, 4])
-                else:
-                    self._evals.index_copy_(0, idx, info[:, 4].contiguous())
+            r.last_u_c, r.state_c, r.refs_c, r.speed_c, r.dyn_c = sel(r.last_u), sel(self.robot), sel(refs), sel(speed), sel(dyn)
+            rec = None if record is None else self._record_entry(alive)
+            hs = self._mpc_step(r, kt, idx, nA, Ua, ya, rec)
             if not full:
                 self.U.index_copy_(0, idx, Ua)
                 self.y.index_copy_(0, idx, ya)
-            if record is not None:
-                Pfull = self.P if full else torch.zeros_like(self.P).index_copy_(0, idx, Pa)
-                rec.update(P=Pfull.cpu().numpy(), U=self.U.cpu().numpy())
+            if rec is not None:
+                rec["U"] = self.U.cpu().numpy()
                 record.append(rec)
             solve_ms.append(hs.last_kernel_ms())
             raw = self.U[:, :2].clone()
             act = torch.where((raw[:, 0:1] < 0), torch.zeros_like(raw), raw)     # no-backward, main_base.py:320-321
             new_robot = unicycle_rk4_step(self.robot, act, ts)
             self.robot = torch.where(alive[:, None], new_robot, self.robot)
-            last_u = torch.where(alive[:, None], raw, last_u)
+            r.last_u = torch.where(alive[:, None], raw, r.last_u)
             self._step_humans()
-            steps = steps + alive.long()
+            r.steps = r.steps + alive.long()
             traj.append(self.robot.clone())
             acts.append(torch.where(alive[:, None], raw, torch.full_like(raw, float("nan"))))
             # metrics and flags (main_base.py:326-335)
             dd = min_dynamic_distance(self.robot[:, :2], self.humans)
-            clr_dyn = torch.where(alive, torch.minimum(clr_dyn, dd), clr_dyn)
-            clr_stc = torch.where(alive, torch.minimum(clr_stc, self._polygon_distance(self.robot[:, :2])), clr_stc)
+            r.clr_dyn = torch.where(alive, torch.minimum(r.clr_dyn, dd), r.clr_dyn)
+            r.clr_stc = torch.where(alive, torch.minimum(r.clr_stc, self._polygon_distance(self.robot[:, :2])), r.clr_stc)
             dref = deviation_to_reference(self.robot[:, :2], self.ref_traj, self.ref_len)
-            dev_sum = dev_sum + torch.where(alive, dref, torch.zeros_like(dref))
-            dev_max = torch.where(alive, torch.maximum(dev_max, dref), dev_max)
-            n_traj = n_traj + alive.to(self.tdt)
+            r.dev_sum = r.dev_sum + torch.where(alive, dref, torch.zeros_like(dref))
+            r.dev_max = torch.where(alive, torch.maximum(r.dev_max, dref), r.dev_max)
+            r.n_traj = r.n_traj + alive.to(self.tdt)
             col = alive & (self._in_polygon(self.robot[:, :2]) | (dd <= HUMAN_SIZE))
             done = alive & ~col & ((self.robot[:, 0] - self.goal[:, 0]).abs() <= 0.5) & \
                 ((self.robot[:, 1] - self.goal[:, 1]).abs() <= 0.5) & (act[:, 0].abs() < 0.4)
-            collision |= col
-            complete |= done
-            alive = alive & ~col & ~done
-        collision |= alive                                                       # time-out, main_base.py:407-410
+            r.collision |= col
+            r.complete |= done
+            r.alive = alive & ~col & ~done
         A = torch.stack(acts, dim=1) if acts else torch.zeros(B, 0, 2, dtype=self.tdt, device=self.dev)
-        smooth = action_smoothness(A)
-        return EvaluationResult(
-            collision=collision.cpu().numpy(), complete=complete.cpu().numpy(), steps=steps.cpu().numpy(),
-            smoothness=smooth.cpu().numpy(), clearance=clr_stc.cpu().numpy(), clearance_dyn=clr_dyn.cpu().numpy(),
-            deviation=torch.stack([dev_sum / n_traj, dev_max], dim=1).cpu().numpy(),
-            trajectory=torch.stack(traj, dim=1).cpu().numpy(), actions=A.cpu().numpy(), solve_ms=solve_ms)
+        return self._finish_run(r, torch.stack(traj, dim=1), A, solve_ms)
 
     def close(self):
-        for h in set(getattr(self, "_h_by_waves", {}).values()) | {self.h}:
+        for h in set(self._h_by_waves.values()) | {self.h}:
             h.close()

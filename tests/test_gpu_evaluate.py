@@ -285,3 +285,122 @@ def test_loop_kernels_refuse_host_pointers():
         a.robot = None
         with pytest.raises(nm.NmpcError, match="NULL"):
             h.loop_step(np.float64, a, post=True)
+
+
+# ---- the evaluator's options that are believed to touch no result: dispatch order, status counting, stage timing --------
+_RESULT_FIELDS = ("collision", "complete", "steps", "smoothness", "clearance", "clearance_dyn", "deviation", "trajectory",
+                  "actions")        # every EvaluationResult field except solve_ms
+_runs96 = {}
+
+
+def _assert_same_results(a, b, what):
+    for key in _RESULT_FIELDS:
+        assert np.array_equal(getattr(a, key), getattr(b, key), equal_nan=True), (what, key)
+
+
+def _run96(compact, fused=True, record=None, **flags):
+    """B = 96 fp32 corridor scenarios, 40 steps, stagger 0.2, seed 5, ``flags`` set on the evaluator before the run;
+    -> (result, evaluator, closed). The run with ``dispatch_by_history = False`` and nothing else is made once per
+    (compact, fused) and shared."""
+    plain = flags == dict(dispatch_by_history=False) and record is None
+    if plain and (compact, fused) in _runs96:
+        return _runs96[(compact, fused)]
+    boxes, starts, paths, hstart, hpath = _scenarios(96, np.random.default_rng(14))
+    cfg = nm.default_config_struct()
+    cfg.latency_waves = 2
+    ev = BatchEvaluator(cfg, starts, paths, hstart, hpath, boxes, dtype=np.float32, human_stagger=0.2, seed=5,
+                        compact=compact, fused=fused)
+    for name, value in flags.items():
+        assert hasattr(ev, name), name
+        setattr(ev, name, value)
+    out = ev.run(max_steps=40, record=record), ev
+    ev.close()
+    if plain:
+        _runs96[(compact, fused)] = out
+    return out
+
+
+@pytest.mark.parametrize("compact,fused", [(False, True), (True, True), (True, False)])
+def test_dispatch_by_history_changes_no_result(compact, fused):
+    """``dispatch_min_batch`` is 32 768, so no other test reaches the longest-first order of the solves
+    (nmpc_set_dispatch_order from the previous step's evaluation counts). It is scheduling only: the same bits with it
+    (``dispatch_min_batch = 1``) and without it, whole batch or compacted, kernels or torch expressions around the solve."""
+    a, _ = _run96(compact, fused, dispatch_by_history=False)
+    b, ev = _run96(compact, fused, dispatch_min_batch=1)
+    assert ev.dispatch_by_history
+    assert (a.steps < 40).any()                                           # scenarios did finish along the way
+    _assert_same_results(a, b, (compact, fused))
+
+
+def test_status_counting_changes_no_result_and_counts_every_solve():
+    """``count_status``: one [4] count per lock-step, summing to the scenarios that step solved -- with compaction, those
+    still alive (without it every step solves all 96) -- and the same results as without it."""
+    a, _ = _run96(True, dispatch_by_history=False)
+    rec = []
+    b, ev = _run96(True, record=rec, count_status=True)
+    _assert_same_results(a, b, "count_status")
+    assert len(ev.status_counts) == len(rec) == len(b.solve_ms) > 0
+    for k, (counts, r) in enumerate(zip(ev.status_counts, rec)):
+        assert counts.shape == (4,) and int(counts.sum()) == int(r["alive"].sum()), k
+    assert int(rec[-1]["alive"].sum()) < 96
+
+
+def test_stage_timing_flags_change_no_result_and_time_every_stage_call():
+    """``time_predictor`` / ``time_tracker`` put HIP events around every call of the stage: one finite positive time per
+    lock-step, nothing without the flag, and the same results either way."""
+    sc = nm.scenarios.make_reference_scenarios(6)
+    sc.pop("scenario_index")
+
+    def run(flag, **kw):
+        cfg = nm.default_config_struct()
+        cfg.latency_waves = 2
+        ev = BatchEvaluator(cfg, dtype=np.float64, **kw, **sc)
+        if flag:
+            setattr(ev, flag, True)
+        rec = []
+        res = ev.run(max_steps=8, record=rec)
+        ev.close()
+        return res, ev, rec
+    for flag, attr, kw in (("time_predictor", "predictor_ms", dict(predictor="kfmp")),
+                           ("time_tracker", "tracker_ms", dict(tracker="dwa", predictor="cvmp"))):
+        a, ev_a, rec_a = run(None, **kw)
+        b, ev_b, rec_b = run(flag, **kw)
+        assert ev_a.predictor_ms == [] and ev_a.tracker_ms == [], flag
+        ms = getattr(ev_b, attr)
+        n_calls = len(b.solve_ms) if flag == "time_predictor" else len(rec_b)
+        assert len(ms) == n_calls == len(rec_a) > 0, flag
+        assert all(np.isfinite(m) and m > 0 for m in ms), (flag, ms)
+        assert getattr(ev_b, "tracker_ms" if flag == "time_predictor" else "predictor_ms") == [], flag
+        _assert_same_results(a, b, flag)
+
+
+def test_warm_start_through_the_kernels_and_the_torch_expressions():
+    """``warm_start=True`` (the shifted previous solution as the initial guess, gathered for the compacted batch) through
+    both paths: steps 0 and 1 compared as test_fused_step_kernels_against_the_torch_expressions compares them; later steps
+    amplify rounding (see there) and are only required to run."""
+    import torch
+    rng = np.random.default_rng(22)
+    B = 32
+    boxes, starts, paths, hstart, hpath = _scenarios(B, rng)
+    draws = [torch.from_numpy(rng.integers(-10, 11, (B, hstart.shape[1])) / 10 * 0.2).cuda() for _ in range(40)]
+    out, recs = [], []
+    for fused in (False, True):
+        cfg = _cfg()
+        cfg.latency_waves = 2
+        ev = BatchEvaluator(cfg, starts, paths, hstart, hpath, boxes, dtype=np.float64, warm_start=True, compact=True,
+                            fused=fused)
+        ev.stagger_replay = [d.clone() for d in draws]
+        rec = []
+        out.append(ev.run(max_steps=40, record=rec))
+        recs.append(rec)
+        ev.close()
+    a, b = out
+    assert len(recs[0]) >= 2 and len(recs[1]) >= 2
+    for key in ("robot", "humans", "P", "U"):
+        x, y = recs[0][0][key], recs[1][0][key]
+        assert np.abs(x - y).max() <= 1e-13 * max(1.0, np.abs(x).max()), key
+    assert np.abs(a.trajectory[:, 1] - b.trajectory[:, 1]).max() < 1e-12
+    assert np.abs(recs[0][1]["humans"] - recs[1][1]["humans"]).max() < 1e-12
+    live = recs[0][1]["alive"] & recs[1][1]["alive"]
+    dP = np.abs(recs[0][1]["P"] - recs[1][1]["P"])[live].max(axis=1)
+    assert dP.max() < 1e-12, dP.max()
