@@ -13,6 +13,9 @@ Fixtures written:
   problem_n20.npz      f, F1, F2 from MpcModule.build(unicycle_model, test=True) (mpc_builder.py:28-201) on
                        config/mpc_fast.yaml for random (u, p): U, P, f, F1, F2 (+ finite-difference grad f).
   problem_small.npz    same for a reduced-dimension yaml (N=6, Nother=3, Nstc=2, Ndyn=4).
+  problem_offnominal.npz  same at the default dimensions for a yaml with EVERY robot constant changed (OFFNOMINAL below:
+                       no two magnitudes equal, asymmetric acceleration bounds); its constants and the captured sets
+                       U / C are the "offnominal" entry of problem_meta.json.
   motion_model.npz     unicycle_model RK4 (basic_motion_model/motion_model.py:141-163) on random states/actions.
   tracker_harness.json parameter lists / return values of TrajectoryTracker.run_step
                        (pkg_mpc_tracker/trajectory_tracker.py:273-383) driven by a scripted fake solver.
@@ -23,7 +26,9 @@ Fixtures written:
   hypotheses_edge_cases.json  the same functions on the edge families of tests/hypotheses_cases.py (exact ties, duplicate
                        points, all-noise offsets, more clusters than slots) with non-default parameters.
 
-Usage:  python tests/golden/make_golden.py [out_dir [hypotheses]]     (``hypotheses``: only the two f2 recordings)
+Usage:  python tests/golden/make_golden.py [out_dir [hypotheses | offnominal]]
+        (``hypotheses``: only the two f2 recordings; ``offnominal``: only problem_offnominal.npz, with its entry of
+        problem_meta.json written on its own as problem_meta_offnominal.json -- problem_meta.json is not touched)
 """
 from __future__ import annotations
 
@@ -242,6 +247,38 @@ def problem_fixture(cfg_path, K, seed, fd=True):
     return out, meta
 
 
+# every robot constant of the yaml away from mpc_fast.yaml's value of it; no two of the new magnitudes coincide, the
+# acceleration bounds are asymmetric
+OFFNOMINAL = dict(ts=0.15, lin_vel_min=-0.2, lin_vel_max=1.1, ang_vel_max=0.3, lin_acc_min=-1.6, lin_acc_max=0.7,
+                  ang_acc_max=1.9, vehicle_width=0.6, vehicle_margin=0.35, social_margin=0.05)
+
+
+def offnominal_fixture(K=8, seed=20261018):
+    """problem_fixture on a temporary yaml = the reference's mpc_fast.yaml with the constants of OFFNOMINAL."""
+    with open(os.path.join(REF, "config", "mpc_fast.yaml")) as fh:
+        y = yaml.safe_load(fh)
+    assert set(OFFNOMINAL) <= set(y) and all(y[k] != v for k, v in OFFNOMINAL.items())
+    mags = [abs(v) for v in OFFNOMINAL.values()]
+    assert len(set(mags)) == len(mags)
+    y.update(OFFNOMINAL, optimizer_name="navi_offnominal")
+    tmp = os.path.join(tempfile.mkdtemp(), "mpc_offnominal.yaml")
+    with open(tmp, "w") as fh:
+        yaml.safe_dump(y, fh)
+    fx, meta = problem_fixture(tmp, K=K, seed=seed)
+    entry = dict(robot=dict(OFFNOMINAL), umin=[float(v) for v in meta["umin"]], umax=[float(v) for v in meta["umax"]],
+                 cmin=[float(v) for v in meta["cmin"]], cmax=[float(v) for v in meta["cmax"]],
+                 np=meta["np"], n1=meta["n1"], n2=meta["n2"])
+    return fx, entry
+
+
+def write_offnominal():
+    fx, entry = offnominal_fixture()
+    np.savez_compressed(os.path.join(OUT, "problem_offnominal.npz"), **fx)
+    print("problem_offnominal.npz:", fx["P"].shape, "| f range", fx["f"].min(), fx["f"].max(), "| F2>0 in",
+          int((fx["F2"] > 0).any(axis=1).sum()), "cases")
+    return entry
+
+
 def motion_model_fixture(seed=3, K=64):
     rng = np.random.default_rng(seed)
     S = rng.uniform(-4, 4, (K, 3))
@@ -338,6 +375,10 @@ def main(out_dir=None, only=None):
     if only == "hypotheses":
         write_hypotheses()
         return
+    if only == "offnominal":
+        with open(os.path.join(OUT, "problem_meta_offnominal.json"), "w") as fh:
+            json.dump(write_offnominal(), fh, indent=1)
+        return
     ka = known_answers()
     with open(os.path.join(OUT, "known_answers.json"), "w") as fh:
         json.dump(ka, fh, indent=1)
@@ -347,6 +388,7 @@ def main(out_dir=None, only=None):
     np.savez_compressed(os.path.join(OUT, "problem_n20.npz"), **fx)
     print("problem_n20.npz:", fx["P"].shape, "np/n1/n2 =", meta["np"], meta["n1"], meta["n2"],
           "| f range", fx["f"].min(), fx["f"].max(), "| F2>0 in", int((fx["F2"] > 0).any(axis=1).sum()), "cases")
+    meta["offnominal"] = write_offnominal()
     with open(os.path.join(OUT, "problem_meta.json"), "w") as fh:
         json.dump(meta, fh, indent=1)
 
