@@ -121,6 +121,22 @@ class NmpcSnapArgs(C.Structure):
                 [("n_snapped", C.c_void_p), ("n_outside", C.c_void_p)])
 
 
+class NmpcMmpArgs(C.Structure):
+    """Mirror of ``struct nmpc_mmp_args`` (device pointers)."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "H", "n_item", "n_off", "Hm", "Wm", "x_reverse", "y_reverse")] +
+                [(n, C.c_void_p) for n in ("items", "hist", "hcount")] +
+                [(n, C.c_double) for n in ("scale", "offset_x", "offset_y", "x_max", "y_max", "rescale", "sigma")] +
+                [("ref_image", C.c_void_p), ("out", C.c_void_p)])
+
+    def set_transform(self, transform, rescale: float = 1.0, sigma: float = 20.0):
+        """The constants of a :class:`.snap.WorldTransform` (applied backwards: world -> map pixels), ``rescale``, ``sigma``."""
+        self.x_reverse, self.y_reverse = int(bool(transform.x_reverse)), int(bool(transform.y_reverse))
+        self.scale, self.offset_x, self.offset_y = float(transform.scale), float(transform.offsetx_after), float(transform.offsety_after)
+        self.x_max, self.y_max = float(transform.x_max_before), float(transform.y_max_before)
+        self.rescale, self.sigma = float(rescale), float(sigma)
+        return self
+
+
 # every symbol include/nmpc_hip.h declares (checked by the CPU test-suite against the built library)
 EXPORTED_SYMBOLS = (
     "nmpc_default_config", "nmpc_layout", "nmpc_create", "nmpc_destroy", "nmpc_param_len", "nmpc_set_stream", "nmpc_use_own_stream", "nmpc_set_pointer_mode",
@@ -131,6 +147,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_set_map", "nmpc_snap_hypotheses_f32", "nmpc_snap_hypotheses_f64",
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
+    "nmpc_mmp_input_f32", "nmpc_mmp_input_f64",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_last_error",
 )
 
@@ -183,6 +200,7 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
         getattr(lib, "nmpc_loop_post_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
         getattr(lib, "nmpc_kf_predict_" + sfx).argtypes = [vp, C.POINTER(NmpcKfArgs)]
         getattr(lib, "nmpc_dwa_step_" + sfx).argtypes = [vp, C.POINTER(NmpcDwaArgs)]
+        getattr(lib, "nmpc_mmp_input_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpArgs)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     lib.nmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.nmpc_kernel_info.argtypes = [vp] + [C.POINTER(i32)] * 5
@@ -363,6 +381,13 @@ class Handle:
         """``nmpc_dwa_step_*``: the dynamic-window tracker for the running scenarios (window, grid, rollouts, costs, ordered
         arg-min; ``U_c`` = the chosen control repeated ``N_hor`` times), one launch enqueued on the handle's stream."""
         fn = getattr(self._lib, "nmpc_dwa_step_" + _suffix(dtype))
+        _check(fn(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_input(self, dtype, args: "NmpcMmpArgs"):
+        """``nmpc_mmp_input_*``: the float32 input stack ``out[n_item, n_off, 7, Hm, Wm]`` of the multi-hypothesis predictor's
+        network from the pedestrians' ``hist`` / ``hcount`` rows (``dtype``: the element type of ``hist``), one launch enqueued
+        on the handle's stream."""
+        fn = getattr(self._lib, "nmpc_mmp_input_" + _suffix(dtype))
         _check(fn(self._h, C.byref(args) if args is not None else None))
 
     def hypotheses_to_ellipses(self, dtype, hypos, cur, dyn_out, n_obs_out=None, human_size=0.2, eps=1.0, enlarge=2.0,

@@ -24,6 +24,7 @@
 #include "nmpc_kf.h"
 #include "nmpc_dwa.h"
 #include "nmpc_snap.h"
+#include "nmpc_mmp.h"
 
 using namespace nmpc_plan;
 
@@ -1474,6 +1475,58 @@ int kf_predict(nmpc_handle_s* h, const nmpc_kf_args* g)
     return 0;
 }
 
+template <typename T, int V>
+void launch_mmp(nmpc_handle_s* h, nmpc::MmpParams& p, long long groups)
+{
+    p.bpi = (int)((groups / V + nmpc::kMmpThreads - 1) / nmpc::kMmpThreads);
+    hipLaunchKernelGGL((nmpc::mmp_input_kernel<T, V>), dim3((unsigned)((long long)p.n_item * p.bpi)), dim3(nmpc::kMmpThreads), 0, h->stream, p);
+}
+
+template <typename T>
+int mmp_input(nmpc_handle_s* h, const nmpc_mmp_args* g)
+{
+    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if (g->B < 1 || g->H < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: B = %d, H = %d", g->B, g->H);
+    if (g->n_item < 0 || g->n_item > (long long)g->B * g->H)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: n_item = %d outside 0 .. B * H = %lld", g->n_item, (long long)g->B * g->H);
+    if (g->n_off < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: n_off = %d < 1", g->n_off);
+    if (g->Hm < 1 || g->Wm < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: map %d x %d", g->Hm, g->Wm);
+    if (!(g->sigma > 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: sigma = %g", g->sigma);
+    if (!(g->scale != 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: scale = %g", g->scale);
+    if (!g->hist || !g->hcount || !g->ref_image || !g->out) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: a required array is NULL");
+    if (g->n_item == 0) return 0;
+    const long long HW = (long long)g->Hm * g->Wm;
+    // the widest store for which every plane start (a multiple of HW floats behind out) stays aligned
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(g->out);
+    if (addr % 4) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: out is not aligned to float");
+    const int V = (HW % 4 == 0 && addr % 16 == 0) ? 4 : (HW % 2 == 0 && addr % 8 == 0) ? 2 : 1;
+    const long long bpi = (HW / V + nmpc::kMmpThreads - 1) / nmpc::kMmpThreads;
+    if (bpi * g->n_item > 0x7fffffffLL) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_input: %lld workgroups", bpi * g->n_item);
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    // (a host pointer here would fault inside the kernel: three samples of the argument block are looked up)
+    if (h->ptr_mode != NMPC_PTR_DEVICE && (!is_device_ptr(g->hist) || !is_device_ptr(g->ref_image) || !is_device_ptr(g->out)))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: every array must be a device pointer");
+    nmpc::MmpParams p;
+    std::memset(&p, 0, sizeof p);
+    p.n_item = g->n_item, p.n_off = g->n_off, p.H = g->H, p.Hm = g->Hm, p.Wm = g->Wm;
+    p.xr = g->x_reverse != 0, p.yr = g->y_reverse != 0;
+    p.n_ped = (long long)g->B * g->H;
+    p.items = reinterpret_cast<const long long*>(g->items);
+    p.hist = g->hist, p.hcount = reinterpret_cast<const long long*>(g->hcount);
+    p.scale = g->scale, p.offx = g->offset_x, p.offy = g->offset_y, p.xmax = g->x_max, p.ymax = g->y_max, p.rescale = g->rescale;
+    p.s2 = g->sigma * g->sigma;
+    p.k = 1.0 / (2.0 * 3.141592653589793 * g->sigma * g->sigma); // numpy's order: ((2 pi) sigma_x) sigma_y
+    p.ref = g->ref_image, p.out = g->out;
+    if (V == 4)
+        launch_mmp<T, 4>(h, p, HW);
+    else if (V == 2)
+        launch_mmp<T, 2>(h, p, HW);
+    else
+        launch_mmp<T, 1>(h, p, HW);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // largest nv * nw a scenario's window can give: per axis the window is at most min(range, 2 acc ts) wide and np.arange's
 // count is ceil of a quotient that rounding can lift past an integer, so floor(...) + 1 (host only)
 static long long dwa_axis_bound(double range, double acc, double ts, double res)
@@ -1894,6 +1947,8 @@ int nmpc_kf_predict_f32(nmpc_handle h, const nmpc_kf_args* a) { return kf_predic
 int nmpc_kf_predict_f64(nmpc_handle h, const nmpc_kf_args* a) { return kf_predict<double>(h, a); }
 int nmpc_dwa_step_f32(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<float>(h, a); }
 int nmpc_dwa_step_f64(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<double>(h, a); }
+int nmpc_mmp_input_f32(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input<float>(h, a); }
+int nmpc_mmp_input_f64(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input<double>(h, a); }
 
 int nmpc_last_kernel_ms(nmpc_handle h, float* ms)
 {

@@ -28,11 +28,15 @@ scenarios still running:
 1. ``nmpc_loop_pre_*`` (``csrc/nmpc_step.h``): constant-velocity obstacle rows, reference windows, speed reference;
 2. predictor stage, with ``predictor="kfmp"`` only: ``nmpc_kf_predict_*`` (``csrc/nmpc_kf.h``) overwrites the obstacle rows
    (fused path only -- its independent check is tests/kf_reference.py);
+   with ``predictor="mmp"``: ``_mmp_predict`` = ``nmpc_mmp_input_*`` (``csrc/nmpc_mmp.h``) -> the caller's network ->
+   ``nmpc_snap_hypotheses_*`` -> ``nmpc_hypotheses_to_ellipses_*`` (row f2), whose ``Ndynobs`` rows per scenario replace
+   ``loop_pre``'s as the input of f1 (``MainBase.run_wta_prediction``, main_base.py:175-208, ``MmpInterface``,
+   interfaces/mmp_interface.py:20-70; its independent check is tests/mmp_reference.py);
 3. tracker stage: ``_mpc_step`` = f1, the ``on_params`` hook, ``_solve_step`` (warm start, handle by batch size, dispatch
    order, status counts, ``_solve``); or ``_dwa_step`` = ``nmpc_dwa_step_*``;
 4. ``nmpc_loop_post_*``: first action, agent motion, metrics, flags.
 
-A run starts in ``_start_run`` (flags and metrics, one namespace with the ``_loop_args`` / ``_kf_args`` / ``_dwa_args`` buffers)
+A run starts in ``_start_run`` (flags and metrics, one namespace with the ``_loop_args`` / ``_kf_args`` / ``_mmp_args`` / ``_dwa_args`` buffers)
 and ends in ``_finish_run``. ``_run_torch`` (``fused=False``) is stages 1 and 4 written out op by op in torch around the same
 ``_mpc_step`` -- the implementation of rounds 1-2, kept as the independent check of the kernels. Where the reference runs
 ``max_num_run`` scenarios one after another (main_base.py:448-464), this runs them side by side. Pedestrian stagger
@@ -51,6 +55,8 @@ from .trajectory_tracker import TrajectoryTracker
 
 HUMAN_SIZE = 0.2   # main_base.py:75, main_pre.py:18
 HUMAN_VMAX = 1.5   # main_base.py:76
+MMP_SIGMA = 20.0   # pre_load.py:128 (sigmas=[20, 20], pixels)
+MMP_INPUT_BYTES = 1 << 30   # default bound on the network's input tensor of one chunk
 
 
 @dataclass
@@ -65,6 +71,9 @@ class EvaluationResult:
     trajectory: np.ndarray       # [B, T+1, 3] robot states (rows after the end repeat the last state)
     actions: np.ndarray          # [B, T, 2]  raw solver actions
     solve_ms: List[float]        # kernel time of every batched solve
+    n_obs: Optional[np.ndarray] = None       # [T, B] int32, predictor "mmp": clusters found per step (> Ndynobs: the obstacle
+    #                                          list was truncated), -1 where the scenario was not running
+    n_outside: Optional[np.ndarray] = None   # [T, B] int32, predictor "mmp": hypotheses the network put outside the map
 
 
 def action_smoothness(A):
@@ -114,7 +123,8 @@ class BatchEvaluator:
                  tuning: Optional[Sequence[float]] = None, lin_vel_max: float = 1.5, warm_start: bool = False,
                  compact: Optional[bool] = None, fused: bool = True, n_hyp: int = 1, hyp_fan: float = 0.15,
                  hyp_radius_growth: float = 0.05, predictor: Optional[str] = "cvmp", kf_Q=None, kf_R=None, kf_P0=None,
-                 tracker: str = "mpc", dwa_config=None):
+                 tracker: str = "mpc", dwa_config=None, network=None, mmp_hyp: int = 20, mmp_chunk: Optional[int] = None,
+                 ref_image=None, transform=None, rescale: float = 1.0):
         """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
@@ -128,6 +138,16 @@ class BatchEvaluator:
         runs over the whole past trajectory of every pedestrian at every step, so ``run(max_steps)`` keeps all of them on the
         device: ``B * H * (max_steps + 1) * 2`` reals -- 254 MB in fp32 at B = 65 536, H = 4, 120 steps.
 
+        ``predictor="mmp"``: the reference's multi-hypothesis predictor (``main('mpc', 'mmp')``). ``network``: any callable that
+        takes the float32 device tensor ``[M, 7, Hm, Wm]`` (five Gaussian maps of the past positions, the label image, the
+        time offset) and returns ``mmp_hyp`` hypotheses per row in network pixels, ``[M, mmp_hyp * 2]`` or ``[M, mmp_hyp, 2]``,
+        as the reference's ``ConvMultiHypoNet`` does; it is called under ``torch.no_grad()`` in whatever mode the caller left
+        it (no weights are loaded here). ``ref_image`` [Hm, Wm]: the grey label image (255 = free), also the map the
+        hypotheses are snapped on (``255 - ref_image`` is the occupancy, ``Handle.set_map`` once, here). ``transform``: the
+        :class:`.snap.WorldTransform` between map pixels and the world, ``rescale``: ``scale2nn``. ``mmp_chunk``: pedestrians
+        per network call (default: as many as keep the input tensor at or below 1 GiB -- 19 for the warehouse map at
+        N_hor = 20). It needs ``tracker="mpc"``, ``fused=True``, ``n_hyp == 1`` and ``H * mmp_hyp <= 256``.
+
         ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the
         multi-hypothesis obstacle tensor SURVEY.md 8(d) prescribes for BASELINE configs[2] (4 pedestrians x 10
@@ -140,9 +160,16 @@ class BatchEvaluator:
         if tracker not in ("mpc", "dwa"):
             raise ValueError(f"tracker = {tracker!r} (mpc or dwa)")
         if tracker == "mpc" and predictor is None:
-            raise ValueError("tracker = 'mpc' needs a predictor (cvmp or kfmp)")
-        if predictor not in ("cvmp", "kfmp") and not (tracker == "dwa" and predictor is None):
-            raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; None with tracker = 'dwa')")
+            raise ValueError("tracker = 'mpc' needs a predictor (cvmp, kfmp or mmp)")
+        if predictor not in ("cvmp", "kfmp") and not (tracker == "dwa" and predictor is None) and not (tracker == "mpc" and predictor == "mmp"):
+            raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; mmp with tracker = 'mpc'; None with tracker = 'dwa')")
+        if predictor == "mmp":
+            if self.n_hyp != 1 or not fused:
+                raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
+            if not callable(network) or ref_image is None or transform is None:
+                raise ValueError("predictor = 'mmp' needs network (a callable), ref_image and transform")
+            if int(mmp_hyp) < 1 or (mmp_chunk is not None and int(mmp_chunk) < 1) or not float(rescale) != 0.0:
+                raise ValueError(f"mmp_hyp = {mmp_hyp}, mmp_chunk = {mmp_chunk}, rescale = {rescale}")
         if tracker == "dwa" and (self.n_hyp != 1 or not fused):
             raise ValueError("tracker = 'dwa' needs n_hyp = 1 and fused = True")
         self.tracker, self.predictor = tracker, predictor
@@ -160,8 +187,9 @@ class BatchEvaluator:
         self.kf_Q, self.kf_R, self.kf_P0 = eye(kf_Q, 4), eye(kf_R, 2), eye(kf_P0, 4)
         # time_predictor / time_tracker: HIP events around every nmpc_kf_predict / nmpc_dwa_step call; run() leaves the
         # times (ms) in predictor_ms / tracker_ms
-        self.time_predictor, self.time_tracker = False, False
-        self.predictor_ms, self.tracker_ms = [], []
+        # (predictor "mmp": time_predictor_parts adds events around its four parts; predictor_part_ms: name -> ms per step)
+        self.time_predictor, self.time_tracker, self.time_predictor_parts = False, False, False
+        self.predictor_ms, self.tracker_ms, self.predictor_part_ms = [], [], {}
         self.time_solves = True     # record the HIP-event time of every batched solve (one event wait per time step)
         self.dt = np.dtype(dtype)
         self.tdt = torch.float32 if self.dt == np.float32 else torch.float64
@@ -231,6 +259,8 @@ class BatchEvaluator:
             self._init_mpc(tuning)
         else:
             self._init_dwa(robot_paths)
+        if predictor == "mmp":
+            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale)
 
     def _tensor(self, x):
         return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
@@ -290,6 +320,21 @@ class BatchEvaluator:
         self.P = torch.empty(B, self.h.np_, dtype=self.tdt, device=self.dev)
         self._info, self._evals = self._full(B, 8), self._full(B)
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
+
+    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale):
+        """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the chunk."""
+        img = np.ascontiguousarray(ref_image, dtype=np.float32)
+        if img.ndim != 2:
+            raise ValueError(f"ref_image must be [Hm, Wm], got {img.shape}")
+        self.network, self.mmp_hyp, self.mmp_tf, self.mmp_rescale = network, int(mmp_hyp), transform, float(rescale)
+        if self.H * self.mmp_hyp > 256:
+            raise ValueError(f"{self.H} pedestrians x {self.mmp_hyp} hypotheses exceed the 256 points per time offset of the snap and f2 kernels")
+        self.mmp_Hm, self.mmp_Wm = int(img.shape[0]), int(img.shape[1])
+        self.mmp_ref = self.torch.as_tensor(img, device=self.dev)
+        # mmp_interface.py:60 snaps on 255 - ref_image; its grey levels decide the edges (Handle.set_map)
+        self.h.set_map(255.0 - img.astype(np.float64))
+        per_ped = self.N * 7 * self.mmp_Hm * self.mmp_Wm * 4
+        self.mmp_chunk = int(mmp_chunk) if mmp_chunk is not None else max(1, MMP_INPUT_BYTES // per_ped)
 
     def _init_dwa(self, robot_paths):
         """The node paths the deviation term measures against, padded with their last node; no solver state."""
@@ -487,6 +532,65 @@ class BatchEvaluator:
         kf.kf_traj, kf.kf_len, kf.kf_P = r.kf_traj.data_ptr(), r.kf_len.data_ptr(), r.kf_P.data_ptr()
         return kf
 
+    def _mmp_args(self, r, max_steps):
+        """``NmpcMmpArgs`` of a run and the stage's buffers: the network's input tensor of one chunk, the hypotheses (pedestrian
+        major as the network returns them, then per scenario as snap and f2 take them), f2's obstacle rows -- which f1 reads
+        instead of ``loop_pre``'s -- and the per-step counts."""
+        torch, B, N, H, K, z = self.torch, self.B, self.N, self.H, self.mmp_hyp, self._full
+        chunk = min(self.mmp_chunk, B * H)
+        r.mmp_in = torch.empty(chunk, N, 7, self.mmp_Hm, self.mmp_Wm, dtype=torch.float32, device=self.dev)
+        r.mmp_raw_p, r.mmp_hyp = z(B * H, N, K, 2), z(B, N, H * K, 2)
+        r.mmp_dyn = z(B, self.cfg.Ndynobs, N + 1, 6)
+        r.mmp_n_obs, r.mmp_n_out = z(B, dtype=torch.int32, fill=0), z(B, dtype=torch.int32, fill=0)
+        r.mmp_obs_steps = z(max(max_steps, 1), B, dtype=torch.int32, fill=-1)
+        r.mmp_out_steps = z(max(max_steps, 1), B, dtype=torch.int32, fill=-1)
+        r.mmp_all = torch.arange(B * H, dtype=torch.long, device=self.dev)
+        r.mmp_events = []
+        r.dyn_in = r.mmp_dyn
+        m = _capi.NmpcMmpArgs().set_transform(self.mmp_tf, self.mmp_rescale, MMP_SIGMA)
+        m.B, m.H, m.n_off, m.Hm, m.Wm = B, H, N, self.mmp_Hm, self.mmp_Wm
+        m.hist, m.hcount, m.ref_image, m.out = self.hist.data_ptr(), self.hcount.data_ptr(), self.mmp_ref.data_ptr(), r.mmp_in.data_ptr()
+        return m
+
+    def _mmp_predict(self, r, m, kt, idx, nA):
+        """The multi-hypothesis predictor for the ``nA`` running scenarios (``idx``, None = all), MainBase.run_wta_prediction
+        (main_base.py:175-208): per chunk of pedestrians input stack -> network; then, per scenario with its pedestrians'
+        segments concatenated in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]``."""
+        torch, N, H, K = self.torch, self.N, self.H, self.mmp_hyp
+
+        def part(name, call):
+            if not self.time_predictor_parts:
+                return call()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = call()
+            e1.record()
+            r.mmp_events.append((kt, name, e0, e1))
+            return out
+        items = r.mmp_all if idx is None else (idx[:, None] * H + r.mmp_all[None, :H]).reshape(-1).contiguous()
+        n_ped = nA * H
+        for c0 in range(0, n_ped, self.mmp_chunk):
+            n = min(self.mmp_chunk, n_ped - c0)
+            m.n_item, m.items = n, items[c0:].data_ptr()
+            part("input", lambda: self.h.mmp_input(self.dt, m))
+            with torch.no_grad():
+                out = part("network", lambda: self.network(r.mmp_in[:n].view(n * N, 7, self.mmp_Hm, self.mmp_Wm)))
+            if out.numel() != n * N * K * 2:
+                raise ValueError(f"the network returned {tuple(out.shape)} for {n * N} inputs; expected {K} hypotheses (x, y) each")
+            r.mmp_raw_p[c0:c0 + n] = out.reshape(n, N, K, 2)
+        # [pedestrian][offset][K] -> [scenario][offset][H * K]: the pedestrians' segments side by side
+        raw = r.mmp_raw_p[:n_ped].view(nA, H, N, K, 2).permute(0, 2, 1, 3, 4).reshape(nA, N, H * K, 2)
+        hyp = r.mmp_hyp[:nA]
+        part("snap", lambda: self.h.snap_hypotheses(self.dt, raw, hyp, H, K, self.mmp_tf, self.mmp_rescale, n_outside=r.mmp_n_out[:nA]))
+        cur = self.humans if idx is None else self.humans.index_select(0, idx)
+        part("f2", lambda: self.h.hypotheses_to_ellipses(self.dt, hyp, cur, r.mmp_dyn[:nA], r.mmp_n_obs[:nA], human_size=HUMAN_SIZE,
+                                                         eps=1.0, enlarge=2.0, extra_margin=0.0))
+        for steps, now in ((r.mmp_obs_steps, r.mmp_n_obs), (r.mmp_out_steps, r.mmp_n_out)):
+            if idx is None:
+                steps[kt].copy_(now)
+            else:
+                steps[kt].index_copy_(0, idx, now[:nA])
+
     def _dwa_args(self, r):
         """``NmpcDwaArgs`` of a run: the compact buffers ``loop_pre`` fills in, the node paths, the outputs per scenario."""
         B, z, i32 = self.B, self._full, self.torch.int32
@@ -561,7 +665,7 @@ class BatchEvaluator:
         harvesting hook, the solves."""
         Pa = self.P if nA == self.B else self.P[:nA]
         self.h.assemble_params(self.dt, nA, Pa, r.last_u_c, r.state_c, r.refs_c, r.speed_c, self.tuning, self.stcw, self.dynw,
-                               self.polys, r.dyn_c[:nA])
+                               self.polys, getattr(r, "dyn_in", r.dyn_c)[:nA])
         if self.on_params is not None:
             self.on_params(kt, idx, Pa)
         return self._solve_step(kt, idx, nA, Pa, Ua, ya, rec)
@@ -581,8 +685,10 @@ class BatchEvaluator:
         r = self._start_run(torch.uint8)
         a = self._loop_args(r, max_steps)
         kf = self._kf_args(r, max_steps) if self.predictor == "kfmp" else None
+        mm = self._mmp_args(r, max_steps) if self.predictor == "mmp" else None
         dw = self._dwa_args(r) if self.tracker == "dwa" else None
         kf_predict, kf_events = self._timed(self.h.kf_predict, self.time_predictor)
+        mmp_predict, mmp_events = self._timed(self._mmp_predict, self.time_predictor)
         dwa_step, dwa_events = self._timed(self.h.dwa_step, self.time_tracker)
         solve_ms, n_steps_run = [], 0
         for kt in range(max_steps):
@@ -603,7 +709,12 @@ class BatchEvaluator:
             if kf is not None:
                 kf.n_run, kf.run = nA, a.run
                 kf_predict(self.dt, kf)
+            if mm is not None:
+                mmp_predict(r, mm, kt, idx, nA)
             rec = None if record is None else self._record_entry(r.alive)
+            if rec is not None and mm is not None:
+                rec.update(dyn=(r.mmp_dyn if full else torch.zeros_like(r.mmp_dyn).index_copy_(0, idx, r.mmp_dyn[:nA])).cpu().numpy(),
+                           n_obs=r.mmp_obs_steps[kt].cpu().numpy(), n_outside=r.mmp_out_steps[kt].cpu().numpy())
             if dw is not None:
                 dw.n_run, dw.run, dw.U_c = nA, a.run, Ua.data_ptr()
                 hs = self._dwa_step(r, dw, dwa_step, idx, nA, Ua, rec)
@@ -616,11 +727,18 @@ class BatchEvaluator:
                 record.append(rec)
             if hs is not None and self.time_solves:
                 solve_ms.append(hs.last_kernel_ms())
-        for name, events in (("predictor_ms", kf_events), ("tracker_ms", dwa_events)):
+        for name, events in (("predictor_ms", kf_events if kf is not None else mmp_events), ("tracker_ms", dwa_events)):
             if events:
                 torch.cuda.synchronize(self.dev)
                 setattr(self, name, [e0.elapsed_time(e1) for e0, e1 in events])
-        return self._finish_run(r, r.traj[:, :n_steps_run + 1], r.acts[:, :n_steps_run], solve_ms)
+        res = self._finish_run(r, r.traj[:, :n_steps_run + 1], r.acts[:, :n_steps_run], solve_ms)
+        if mm is not None:
+            res.n_obs, res.n_outside = r.mmp_obs_steps[:n_steps_run].cpu().numpy(), r.mmp_out_steps[:n_steps_run].cpu().numpy()
+            self.predictor_part_ms = {}
+            for kt, name, e0, e1 in r.mmp_events:       # (the copy above has waited for the stream)
+                ms = self.predictor_part_ms.setdefault(name, [0.0] * n_steps_run)
+                ms[kt] += e0.elapsed_time(e1)
+        return res
 
     def _run_torch(self, max_steps: int = 120, record: Optional[list] = None) -> EvaluationResult:
         """The same time step written out as torch expressions (rounds 1-2): the independent check of the kernels."""

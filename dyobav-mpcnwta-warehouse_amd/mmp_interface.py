@@ -1,0 +1,97 @@
+"""``MmpInterface``: the multi-hypothesis motion predictor behind the reference's interface.
+
+Mirror of the reference class ``interfaces/mmp_interface.py:14-70`` (the same ``get_motion_prediction`` signature and return
+value), so that ``MainBase.run_wta_prediction`` (main_base.py:175-208) can drive it unchanged. THE DIFFERENCE: the
+reference's constructor takes a configuration file name and loads the trained network (``pre_load.load_net``); this one is
+constructed from the network itself -- any callable that maps the float32 device tensor ``[M, 7, Hm, Wm]`` to ``[M, K * 2]``
+or ``[M, K, 2]`` pixel hypotheses, e.g. a ``ConvMultiHypoNet`` the caller has built and put into ``eval()`` mode. It loads no
+weights and holds no configuration.
+
+What the reference does on the host around the network runs on the device: the input stack (``pre_load.traj_to_input`` and
+the copy per time offset) through ``nmpc_mmp_input_f64`` with one item, ``get_closest_edge_point(...) / rescale`` through
+``nmpc_snap_hypotheses_f64`` with the identity transform. There is no host implementation of either in this package.
+
+For whole batches of scenarios use ``evaluate.BatchEvaluator(predictor="mmp")``, which keeps the pedestrians' histories on
+the device and goes on to the obstacle rows; this class uploads its arguments at every call.
+"""
+from __future__ import annotations
+
+from typing import Callable, List, Optional
+
+import numpy as np
+
+from . import _capi
+from .snap import WorldTransform
+
+SIGMA = 20.0        # pre_load.py:128
+OBSV_LEN = 5        # config.obsv_len of the reference's network configurations
+
+
+class MmpInterface:
+    def __init__(self, network: Callable):
+        if not callable(network):
+            raise TypeError(f"network must be a callable, got {type(network)}")
+        self._prt_name = "MMPInterface"
+        self.network = network
+        self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)
+        self._map_of = {}         # pred_offset -> the ref_image its map was set from
+
+    def _handle(self, pred_offset: int, ref_image, img: np.ndarray) -> _capi.Handle:
+        h = self._handles.get(pred_offset)
+        if h is None:
+            cfg = _capi.default_config_struct()
+            cfg.N_hor = pred_offset
+            h = self._handles[pred_offset] = _capi.Handle(cfg)
+        if self._map_of.get(pred_offset) is not ref_image:
+            h.set_map(255.0 - img.astype(np.float64))          # mmp_interface.py:60: the occupancy is 255 - ref_image
+            self._map_of[pred_offset] = ref_image
+        return h
+
+    def get_motion_prediction(self, input_traj: List[tuple], ref_image, pred_offset: int, rescale: float = 1.0,
+                              batch_size: int = 1) -> Optional[List[np.ndarray]]:
+        """``input_traj``: the past positions (x, y) in map pixels before ``rescale``, oldest first; ``ref_image``: a tensor
+        [Hm, Wm]; ``pred_offset``: the number of time offsets; ``batch_size``: time offsets per network call. Returns a list
+        of ``pred_offset`` float64 arrays [K, 2]: the hypotheses, those inside an obstacle moved to the closest edge pixel
+        and put first, ``/ rescale``."""
+        if input_traj is None:
+            return None
+        import torch
+        if not isinstance(ref_image, torch.Tensor):
+            raise TypeError(f"The reference image should be a tensor, got {type(ref_image)}.")
+        if ref_image.dim() != 2:
+            raise ValueError(f"ref_image must be [Hm, Wm], got {tuple(ref_image.shape)}")
+        traj = np.asarray(input_traj, dtype=np.float64).reshape(-1, 2)
+        N, bs = int(pred_offset), int(batch_size)
+        if traj.shape[0] < 1 or N < 1 or bs < 1 or not float(rescale) != 0.0:
+            raise ValueError(f"{traj.shape[0]} positions, pred_offset = {pred_offset}, batch_size = {batch_size}, rescale = {rescale}")
+        img = np.ascontiguousarray(ref_image.detach().cpu().numpy(), dtype=np.float32)
+        Hm, Wm = img.shape
+        h = self._handle(N, ref_image, img)
+        h.set_stream(torch.cuda.current_stream().cuda_stream)
+        # hist as the evaluator keeps it: the last <= 5 positions, newest last (the rows in front of them are not read)
+        last = traj[-OBSV_LEN:]
+        hist = np.repeat(last[:1], OBSV_LEN, axis=0)
+        hist[OBSV_LEN - len(last):] = last
+        d_hist = torch.from_numpy(hist.reshape(1, 1, OBSV_LEN, 2)).cuda()
+        d_count = torch.full((1, 1), traj.shape[0], dtype=torch.long, device="cuda")
+        d_ref = torch.from_numpy(img).cuda()
+        stack = torch.empty(N, 7, Hm, Wm, dtype=torch.float32, device="cuda")
+        ident = WorldTransform()
+        a = _capi.NmpcMmpArgs().set_transform(ident, rescale, SIGMA)
+        a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = 1, 1, 1, N, Hm, Wm
+        a.hist, a.hcount, a.ref_image, a.out = d_hist.data_ptr(), d_count.data_ptr(), d_ref.data_ptr(), stack.data_ptr()
+        h.mmp_input(np.float64, a)
+        with torch.no_grad():
+            outs = [self.network(stack[i:i + bs]) for i in range(0, N, bs)]
+        raw = torch.cat([o.reshape(o.shape[0], -1, 2) for o in outs], dim=0).to(torch.float64)
+        if raw.shape[0] != N or raw.shape[1] < 1 or raw.shape[1] > 256:
+            raise ValueError(f"the network returned {tuple(raw.shape)} for {N} inputs")
+        K = int(raw.shape[1])
+        raw = raw.reshape(1, N, K, 2).contiguous()
+        h.snap_hypotheses(np.float64, raw, raw, 1, K, ident, rescale)
+        return list(raw[0].cpu().numpy())
+
+    def close(self):
+        for h in self._handles.values():
+            h.close()
+        self._handles, self._map_of = {}, {}
