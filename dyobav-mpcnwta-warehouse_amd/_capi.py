@@ -137,6 +137,13 @@ class NmpcMmpArgs(C.Structure):
         return self
 
 
+class NmpcMmpStemArgs(C.Structure):
+    """Mirror of ``struct nmpc_mmp_stem_args`` (device pointers): the fields of ``nmpc_mmp_args`` down to ``ref_image``, then the
+    first layer's ``C``, ``slope``, ``weight`` [C, 7, 7, 7], ``bn_scale`` / ``bn_shift`` [C] and ``out`` [n_item, n_off, C, Hp, Wp]."""
+    _fields_ = (NmpcMmpArgs._fields_[:-1] + [("C", C.c_int32), ("slope", C.c_float)] +
+                [(n, C.c_void_p) for n in ("weight", "bn_scale", "bn_shift", "out")])
+    set_transform = NmpcMmpArgs.set_transform
+
 # every symbol include/nmpc_hip.h declares (checked by the CPU test-suite against the built library)
 EXPORTED_SYMBOLS = (
     "nmpc_default_config", "nmpc_layout", "nmpc_create", "nmpc_destroy", "nmpc_param_len", "nmpc_set_stream", "nmpc_use_own_stream", "nmpc_set_pointer_mode",
@@ -147,7 +154,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_set_map", "nmpc_snap_hypotheses_f32", "nmpc_snap_hypotheses_f64",
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
-    "nmpc_mmp_input_f32", "nmpc_mmp_input_f64",
+    "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_last_error",
 )
 
@@ -201,6 +208,8 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
         getattr(lib, "nmpc_kf_predict_" + sfx).argtypes = [vp, C.POINTER(NmpcKfArgs)]
         getattr(lib, "nmpc_dwa_step_" + sfx).argtypes = [vp, C.POINTER(NmpcDwaArgs)]
         getattr(lib, "nmpc_mmp_input_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpArgs)]
+        getattr(lib, "nmpc_mmp_stem_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpStemArgs)]
+    lib.nmpc_mmp_stem_shape.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     lib.nmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.nmpc_kernel_info.argtypes = [vp] + [C.POINTER(i32)] * 5
@@ -223,6 +232,13 @@ def default_config_struct() -> NmpcConfigStruct:
     cfg = NmpcConfigStruct()
     _check(load_library().nmpc_default_config(C.byref(cfg)))
     return cfg
+
+
+def mmp_stem_shape(Hm: int, Wm: int):
+    """``nmpc_mmp_stem_shape``: ``(Hp, Wp)`` of the fused first layer's output for an ``Hm x Wm`` map (no device needed)."""
+    hp, wp = C.c_int32(), C.c_int32()
+    _check(load_library().nmpc_mmp_stem_shape(int(Hm), int(Wm), C.byref(hp), C.byref(wp)))
+    return hp.value, wp.value
 
 
 def layout_info(cfg: NmpcConfigStruct) -> NmpcLayoutInfo:
@@ -388,6 +404,13 @@ class Handle:
         network from the pedestrians' ``hist`` / ``hcount`` rows (``dtype``: the element type of ``hist``), one launch enqueued
         on the handle's stream."""
         fn = getattr(self._lib, "nmpc_mmp_input_" + _suffix(dtype))
+        _check(fn(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_stem(self, dtype, args: "NmpcMmpStemArgs"):
+        """``nmpc_mmp_stem_*``: the pooled output ``out[n_item, n_off, C, Hp, Wp]`` of the network's first layer (convolution,
+        folded norm, LeakyReLU, max-pool) straight from the pedestrians' ``hist`` / ``hcount`` rows, the input stack never
+        written (``dtype``: the element type of ``hist``), one launch enqueued on the handle's stream."""
+        fn = getattr(self._lib, "nmpc_mmp_stem_" + _suffix(dtype))
         _check(fn(self._h, C.byref(args) if args is not None else None))
 
     def hypotheses_to_ellipses(self, dtype, hypos, cur, dyn_out, n_obs_out=None, human_size=0.2, eps=1.0, enlarge=2.0,

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +26,7 @@
 #include "nmpc_dwa.h"
 #include "nmpc_snap.h"
 #include "nmpc_mmp.h"
+#include "nmpc_mmp_stem.h"
 
 using namespace nmpc_plan;
 
@@ -1527,6 +1529,49 @@ int mmp_input(nmpc_handle_s* h, const nmpc_mmp_args* g)
     return 0;
 }
 
+template <typename T>
+int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g)
+{
+    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if (g->B < 1 || g->H < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: B = %d, H = %d", g->B, g->H);
+    if (g->n_item < 0 || g->n_item > (long long)g->B * g->H)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: n_item = %d outside 0 .. B * H = %lld", g->n_item, (long long)g->B * g->H);
+    if (g->n_off < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: n_off = %d < 1", g->n_off);
+    if (g->Hm < 1 || g->Wm < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: map %d x %d", g->Hm, g->Wm);
+    if (!(g->sigma > 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: sigma = %g", g->sigma);
+    if (!(g->scale != 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: scale = %g", g->scale);
+    if (g->C < nmpc::kStemCG || g->C % nmpc::kStemCG) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: C = %d is no positive multiple of 8", g->C);
+    if (!std::isfinite(g->slope)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: slope = %g", (double)g->slope);
+    if (!g->hist || !g->hcount || !g->ref_image || !g->weight || !g->bn_scale || !g->bn_shift || !g->out)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: a required array is NULL");
+    if (g->n_item == 0) return 0;
+    if (reinterpret_cast<uintptr_t>(g->out) % 4) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: out is not aligned to float");
+    nmpc::MmpStemParams p;
+    std::memset(&p, 0, sizeof p);
+    p.Ho = (g->Hm - 1) / 2 + 1, p.Wo = (g->Wm - 1) / 2 + 1;
+    p.Hp = nmpc::mmp_stem_out(g->Hm), p.Wp = nmpc::mmp_stem_out(g->Wm);
+    p.ty = (p.Hp + nmpc::kStemTPH - 1) / nmpc::kStemTPH, p.tx = (p.Wp + nmpc::kStemTPW - 1) / nmpc::kStemTPW;
+    const long long groups = (long long)p.ty * p.tx * g->n_item;
+    if ((long long)p.ty * p.tx > 0x7fffffffLL || groups > 0x7fffffffLL) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_stem: %lld workgroups", groups);
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    // (a host pointer here would fault inside the kernel: samples of the argument block are looked up)
+    if (h->ptr_mode != NMPC_PTR_DEVICE && (!is_device_ptr(g->hist) || !is_device_ptr(g->ref_image) || !is_device_ptr(g->weight) || !is_device_ptr(g->out)))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: every array must be a device pointer");
+    p.n_item = g->n_item, p.n_off = g->n_off, p.Hm = g->Hm, p.Wm = g->Wm, p.C = g->C;
+    p.xr = g->x_reverse != 0, p.yr = g->y_reverse != 0;
+    p.mono = g->slope >= 0.0f;
+    p.n_ped = (long long)g->B * g->H;
+    p.items = reinterpret_cast<const long long*>(g->items);
+    p.hist = g->hist, p.hcount = reinterpret_cast<const long long*>(g->hcount);
+    p.scale = g->scale, p.offx = g->offset_x, p.offy = g->offset_y, p.xmax = g->x_max, p.ymax = g->y_max, p.rescale = g->rescale;
+    p.s2 = g->sigma * g->sigma;
+    p.k = 1.0 / (2.0 * 3.141592653589793 * g->sigma * g->sigma); // as in mmp_input: the planes must be the same floats
+    p.ref = g->ref_image, p.weight = g->weight, p.bn_scale = g->bn_scale, p.bn_shift = g->bn_shift, p.slope = g->slope, p.out = g->out;
+    hipLaunchKernelGGL(nmpc::mmp_stem_kernel<T>, dim3((unsigned)groups), dim3(nmpc::kStemThreads), 0, h->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // largest nv * nw a scenario's window can give: per axis the window is at most min(range, 2 acc ts) wide and np.arange's
 // count is ceil of a quotient that rounding can lift past an integer, so floor(...) + 1 (host only)
 static long long dwa_axis_bound(double range, double acc, double ts, double res)
@@ -1949,6 +1994,14 @@ int nmpc_dwa_step_f32(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<f
 int nmpc_dwa_step_f64(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<double>(h, a); }
 int nmpc_mmp_input_f32(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input<float>(h, a); }
 int nmpc_mmp_input_f64(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input<double>(h, a); }
+int nmpc_mmp_stem_f32(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<float>(h, a); }
+int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<double>(h, a); }
+int nmpc_mmp_stem_shape(int32_t Hm, int32_t Wm, int32_t* Hp, int32_t* Wp)
+{
+    if (Hm < 1 || Wm < 1 || !Hp || !Wp) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem_shape: map %d x %d or a NULL output", Hm, Wm);
+    *Hp = nmpc::mmp_stem_out(Hm), *Wp = nmpc::mmp_stem_out(Wm);
+    return 0;
+}
 
 int nmpc_last_kernel_ms(nmpc_handle h, float* ms)
 {

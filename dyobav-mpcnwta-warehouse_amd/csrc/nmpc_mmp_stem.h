@@ -1,0 +1,248 @@
+// nmpc_mmp_stem.h -- the first layer of the multi-hypothesis predictor's network, fused with the input stack in front of it
+// ("next" row f3, predictor `mmp`, opt-in): 7 x 7 / stride 2 / padding 3 convolution of the 7-channel stack -> per-channel
+// affine (a folded BatchNorm2d) -> LeakyReLU -> 3 x 3 / stride 2 / padding 1 max-pool, for all n_off time offsets of a
+// pedestrian, WITHOUT the stack [n_off][7][Hm][Wm] or the pre-pool activations ever being in memory. The shapes are those
+// of the reference's ConvMultiHypoNet(lite=True) (net_module/net.py:24-43, submodules.py:21-27); the trunk behind the pool
+// stays the caller's PyTorch.
+//
+// Identity: channels 0 .. 5 of the stack (nmpc_mmp.h) are the same in all n_off copies and channel 6 is the constant
+// t = off + 1, and a convolution is linear, so
+//   pre[off][c][oy][ox] = base[c][oy][ox] + t E[c][oy][ox]
+//   base = the convolution of channels 0 .. 5 (zero outside the map), once per pedestrian instead of n_off times
+//   E    = the sum of the channel-6 weights over the taps that fall inside the map (a constant away from the border)
+//   out[off][c][py][px] = max over the pool window, clipped to the conv grid, of leaky(scale[c] pre + shift[c])
+// evaluated as z = fma(t, B, A) with A = fma(scale, base, shift) and B = scale * E, both formed once per conv output. Where
+// slope >= 0 leaky is non-decreasing, so max(leaky(z_i)) == leaky(max(z_i)) bit for bit and leaky is applied once per
+// pooled output (MmpStemParams::mono, workgroup-uniform); a negative slope takes the element-wise form.
+//
+// The six planes are the float values nmpc_mmp_input_* writes: mmp_gauss / mmp_nearest and the centre arithmetic of
+// nmpc_mmp.h in float64, rounded once to float, per pixel (no separable shortcut). fp32 accumulation in a fixed order (per
+// output: input channel, then ky, then kx, one fma chain per output channel), so an item's bits depend on its own hist /
+// hcount rows, the map and the weights only: not on the item list, the chunk, n_off or the alignment of out.
+//
+// Instructions: plain v_fma_f32. K = 294 per output and no reuse of an input value across more than 8 output channels per
+// pass: v_mfma_f32_32x32x2_f32 runs at the vector fp32 rate on gfx950 (no gain in FLOP/s), would need the im2col operand
+// built in LDS (one more write + read per tap), and packed v_pk_fma_f32 issues at half rate (build.py). So: one conv output
+// per thread, 8 output channels per pass = 8 independent fma chains, the 8 weights of a tap read from LDS as two
+// broadcast ds_read_b128, the input value as one ds_read_b32. (Tried and measured slower, 1.52 ms against 1.40 ms for 34
+// pedestrians: the weights as scalar fma operands, s_load through the constant address space in stages of 28 with the next
+// stage's loads issued behind each wait. Scalar loads return out of order, so every wait is for all of them.)
+//
+// Mapping: 256 threads per workgroup; workgroup = [item][tile row][tile column] flattened in x, a tile = 2 x 24 pooled
+// outputs = 5 x 49 conv outputs (245 of 256 threads) = 15 x 103 input pixels.
+//   1. threads 0 .. 4: centre and grid maximum of one Gaussian each (float64) -> LDS
+//   2. all: the 15 x 103 x 6 input tile -> LDS, ONCE per workgroup, zero outside the map; even and odd columns in separate
+//      halves of a row, so that the stride-2 taps of neighbouring lanes are consecutive dwords (no bank conflict)
+//   3. per group of 8 output channels (C / 8 groups):
+//      a. the group's 8 x 7 x 49 weights -> LDS, transposed to [input channel][ky][kx][8]
+//      b. base and E of the thread's conv output for the 8 channels (294 + 49 taps x 8 fma; E from a 0 / 1 mask of the taps
+//         inside the map), then A, B -> LDS over the weights (A = -inf, B = 0 outside the conv grid: what PyTorch's max-pool
+//         pads with)
+//      c. 2 x 24 x 8 = 384 pooled outputs over 256 threads: the 9 (A, B) pairs of the window -> registers, then the walk over
+//         the n_off offsets: 9 fma, max, leaky, ONE dword store each -- compute once, store n_off times (mmp_input_kernel)
+// Stores: a wave-instruction writes runs of 24 consecutive floats (96 bytes) along px, 2 2/3 runs per instruction; dword
+// stores only, so any float-aligned out works and gives the same bits. No atomics.
+// LDS (static): 37 440 B input tile + 15 680 B weights / (A, B) + 120 B centres = 53 240 B: three workgroups per CU.
+// Compiler (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage): mmp_stem_kernel<float> and <double>
+// 132 VGPRs, 0 AGPRs, 94 SGPRs, no spills, no scratch, 53 240 B LDS, occupancy 3 waves per SIMD (registers and LDS agree).
+// Not at a hardware bound: 0.77 TB/s stored, 13.1 T fma/s; the halo makes a workgroup compute 1 545
+// input pixels (five float64 exp and fifteen float64 divisions each) for 768 it owns.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "nmpc_mmp.h"
+
+namespace nmpc {
+
+struct MmpStemParams {
+    int n_item, n_off, Hm, Wm, xr, yr, C, Ho, Wo, Hp, Wp, tx, ty, mono; // tx, ty: tiles per item along px, py
+    long long n_ped;                                                  // B * H: rows of hist / hcount
+    const long long* items;                                           // [n_item] or nullptr = 0 .. n_item - 1
+    const void* hist;                                                 // [B][H][5][2]
+    const long long* hcount;                                          // [B][H]
+    double scale, offx, offy, xmax, ymax, rescale, s2, k;
+    const float* ref;                                                 // [Hm][Wm]
+    const float* weight;                                              // [C][7][7][7]
+    const float* bn_scale;                                            // [C]
+    const float* bn_shift;                                            // [C]
+    float slope;
+    float* out;                                                       // [n_item][n_off][C][Hp][Wp]
+};
+
+constexpr int kStemThreads = 256;
+constexpr int kStemTPH = 2, kStemTPW = 24;                            // pooled tile
+constexpr int kStemCH = 2 * kStemTPH + 1, kStemCW = 2 * kStemTPW + 1; // conv tile: 5 x 49
+constexpr int kStemIH = 2 * kStemCH + 5, kStemIW = 2 * kStemCW + 5;   // input tile: 15 x 103
+constexpr int kStemIW2 = (kStemIW + 1) / 2;                           // columns of one parity: 52
+constexpr int kStemNP = kStemCH * kStemCW;                            // conv outputs per tile: 245
+constexpr int kStemCG = 8;                                            // output channels per pass
+constexpr int kStemTaps = 7 * 49;                                     // weights per output channel
+constexpr int kStemXs = 6 * kStemIH * 2 * kStemIW2;                   // floats of the input tile
+constexpr int kStemWab = 2 * kStemCG * kStemNP;                       // floats of (A, B); the weights (8 x 343) fit inside
+static_assert(kStemNP <= kStemThreads && kStemCG * kStemTaps <= kStemWab, "tile does not fit the workgroup");
+static_assert((kStemXs + kStemWab) * 4 + 5 * 3 * 8 <= 64 * 1024, "static LDS over 64 KB");
+
+__host__ __device__ inline int mmp_stem_out(int n) { return (((n - 1) / 2 + 1) - 1) / 2 + 1; } // conv 7/2/3, then pool 3/2/1
+
+template <typename T>
+__global__ __launch_bounds__(kStemThreads) void mmp_stem_kernel(MmpStemParams p)
+{
+    __shared__ __attribute__((aligned(16))) float xs[kStemXs];   // [6][IH][parity][IW2]
+    __shared__ __attribute__((aligned(16))) float wab[kStemWab]; // weights [7 * 49][8], then A [8][NP], B [8][NP]
+    __shared__ double cen[5][3];                                 // cx, cy, zmax
+
+    const int tid = threadIdx.x;
+    const int tiles = p.tx * p.ty;
+    const int item = blockIdx.x / tiles, tile = blockIdx.x - item * tiles;
+    if (item >= p.n_item) return;
+    const long long ped = p.items ? p.items[item] : item;
+    if (ped < 0 || ped >= p.n_ped) return; // (workgroup-uniform, in front of every barrier)
+    const int tyi = tile / p.tx, txi = tile - tyi * p.tx;
+    const int py0 = tyi * kStemTPH, px0 = txi * kStemTPW;
+    const int oy0 = 2 * py0 - 1, ox0 = 2 * px0 - 1; // conv grid
+    const int iy0 = 2 * oy0 - 3, ix0 = 2 * ox0 - 3; // map
+
+    const long long cnt = p.hcount[ped];
+    const int n = cnt < 1 ? 1 : cnt > 5 ? 5 : (int)cnt; // distinct entries: channels n - 1 .. 4 all show the newest one
+    if (tid < 5) {
+        const T* hist = static_cast<const T*>(p.hist) + ped * 10;
+        const int e = 5 - n + (tid < n - 1 ? tid : n - 1);
+        double cx = ((double)hist[2 * e] - p.offx) / p.scale, cy = ((double)hist[2 * e + 1] - p.offy) / p.scale;
+        if (p.xr) cx = p.xmax - cx;
+        if (p.yr) cy = p.ymax - cy;
+        cx *= p.rescale, cy *= p.rescale;
+        cen[tid][0] = cx, cen[tid][1] = cy;
+        cen[tid][2] = mmp_gauss(mmp_nearest(cx, p.Wm), mmp_nearest(cy, p.Hm), cx, cy, p.s2, p.k);
+    }
+    __syncthreads();
+
+    // ---- 2. the input tile, once
+    for (int pix = tid; pix < kStemIH * kStemIW; pix += kStemThreads) {
+        const int r = pix / kStemIW, j = pix - r * kStemIW;
+        const int gy = iy0 + r, gx = ix0 + j;
+        float v[6];
+        if (gy >= 0 && gy < p.Hm && gx >= 0 && gx < p.Wm) {
+#pragma unroll
+            for (int c = 0; c < 5; ++c) {
+                if (c >= n) { // workgroup-uniform; c >= n >= 1
+                    v[c] = v[c > 0 ? c - 1 : 0];
+                    continue;
+                }
+                v[c] = (float)(mmp_gauss((double)gx, (double)gy, cen[c][0], cen[c][1], p.s2, p.k) / cen[c][2]);
+            }
+            v[5] = p.ref[(long long)gy * p.Wm + gx];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) v[c] = 0.0f;
+        }
+        float* dst = xs + (r * 2 + (j & 1)) * kStemIW2 + (j >> 1);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) dst[c * (kStemIH * 2 * kStemIW2)] = v[c];
+    }
+
+    // the thread's conv output
+    const bool has = tid < kStemNP;
+    const int oyl = has ? tid / kStemCW : 0, oxl = has ? tid - oyl * kStemCW : 0;
+    const int oy = oy0 + oyl, ox = ox0 + oxl;
+    const bool valid = has && oy >= 0 && oy < p.Ho && ox >= 0 && ox < p.Wo;
+    float cm[7]; // 1 where the tap's column lies inside the map
+#pragma unroll
+    for (int kx = 0; kx < 7; ++kx) {
+        const int gx = ix0 + 2 * oxl + kx;
+        cm[kx] = gx >= 0 && gx < p.Wm ? 1.0f : 0.0f;
+    }
+    const size_t plane = (size_t)p.Hp * p.Wp;
+    const float ninf = -__builtin_huge_valf();
+
+    for (int g = 0; g < p.C / kStemCG; ++g) {
+        __syncthreads(); // the input tile is written; the previous group's (A, B) have been read
+        // ---- 3a. weights [8][343] -> [343][8]
+        const float* wg = p.weight + (size_t)g * kStemCG * kStemTaps;
+        for (int i = tid; i < kStemCG * kStemTaps; i += kStemThreads) {
+            const int j = i / kStemTaps, r = i - j * kStemTaps;
+            wab[r * kStemCG + j] = wg[i];
+        }
+        __syncthreads();
+        // ---- 3b. base and E
+        float acc[kStemCG], e[kStemCG];
+#pragma unroll
+        for (int j = 0; j < kStemCG; ++j) acc[j] = 0.0f, e[j] = 0.0f;
+        if (has) {
+            for (int ck = 0; ck < 6 * 7; ++ck) { // (input channel, ky)
+                const int ch = ck / 7, ky = ck - ch * 7;
+                const float* xr = xs + ((ch * kStemIH + 2 * oyl + ky) * 2) * kStemIW2 + oxl;
+                const float* w = wab + ck * 7 * kStemCG;
+#pragma unroll
+                for (int kx = 0; kx < 7; ++kx) {
+                    const float x = xr[(kx & 1) * kStemIW2 + (kx >> 1)];
+#pragma unroll
+                    for (int j = 0; j < kStemCG; ++j) acc[j] = fmaf(w[kx * kStemCG + j], x, acc[j]);
+                }
+            }
+            for (int ky = 0; ky < 7; ++ky) {
+                const int gy = iy0 + 2 * oyl + ky;
+                const float rm = gy >= 0 && gy < p.Hm ? 1.0f : 0.0f;
+                const float* w = wab + (6 * 7 + ky) * 7 * kStemCG;
+#pragma unroll
+                for (int kx = 0; kx < 7; ++kx) {
+                    const float m = rm * cm[kx];
+#pragma unroll
+                    for (int j = 0; j < kStemCG; ++j) e[j] = fmaf(w[kx * kStemCG + j], m, e[j]);
+                }
+            }
+        }
+        __syncthreads(); // every weight has been read: (A, B) go over them
+        if (has) {
+#pragma unroll
+            for (int j = 0; j < kStemCG; ++j) {
+                const float s = p.bn_scale[g * kStemCG + j], sh = p.bn_shift[g * kStemCG + j];
+                wab[j * kStemNP + tid] = valid ? fmaf(s, acc[j], sh) : ninf;
+                wab[(kStemCG + j) * kStemNP + tid] = valid ? s * e[j] : 0.0f;
+            }
+        }
+        __syncthreads();
+        // ---- 3c. pool and store, n_off times
+        for (int it = tid; it < kStemCG * kStemTPH * kStemTPW; it += kStemThreads) {
+            const int j = it / (kStemTPH * kStemTPW), q = it - j * (kStemTPH * kStemTPW);
+            const int pyl = q / kStemTPW, pxl = q - pyl * kStemTPW;
+            const int py = py0 + pyl, px = px0 + pxl;
+            if (py >= p.Hp || px >= p.Wp) continue;
+            float a[9], b[9];
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) {
+                    const int pos = (2 * pyl + dy) * kStemCW + 2 * pxl + dx;
+                    a[dy * 3 + dx] = wab[j * kStemNP + pos];
+                    b[dy * 3 + dx] = wab[(kStemCG + j) * kStemNP + pos];
+                }
+            float* dst = p.out + ((size_t)item * p.n_off * p.C + (size_t)(g * kStemCG + j)) * plane + (size_t)py * p.Wp + px;
+            if (p.mono) {
+                for (int off = 0; off < p.n_off; ++off) {
+                    const float t = (float)(off + 1);
+                    float m = fmaf(t, b[0], a[0]);
+#pragma unroll
+                    for (int i = 1; i < 9; ++i) m = fmaxf(m, fmaf(t, b[i], a[i]));
+                    *dst = m > 0.0f ? m : m * p.slope;
+                    dst += (size_t)p.C * plane;
+                }
+            } else {
+                for (int off = 0; off < p.n_off; ++off) {
+                    const float t = (float)(off + 1);
+                    float m = ninf;
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) {
+                        const float z = fmaf(t, b[i], a[i]);
+                        const float v = z > 0.0f ? z : z * p.slope;
+                        m = fmaxf(m, a[i] > ninf ? v : ninf);
+                    }
+                    *dst = m;
+                    dst += (size_t)p.C * plane;
+                }
+            }
+        }
+    }
+}
+
+} // namespace nmpc

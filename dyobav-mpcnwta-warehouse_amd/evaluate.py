@@ -124,7 +124,7 @@ class BatchEvaluator:
                  compact: Optional[bool] = None, fused: bool = True, n_hyp: int = 1, hyp_fan: float = 0.15,
                  hyp_radius_growth: float = 0.05, predictor: Optional[str] = "cvmp", kf_Q=None, kf_R=None, kf_P0=None,
                  tracker: str = "mpc", dwa_config=None, network=None, mmp_hyp: int = 20, mmp_chunk: Optional[int] = None,
-                 ref_image=None, transform=None, rescale: float = 1.0):
+                 ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None):
         """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
@@ -146,7 +146,11 @@ class BatchEvaluator:
         hypotheses are snapped on (``255 - ref_image`` is the occupancy, ``Handle.set_map`` once, here). ``transform``: the
         :class:`.snap.WorldTransform` between map pixels and the world, ``rescale``: ``scale2nn``. ``mmp_chunk``: pedestrians
         per network call (default: as many as keep the input tensor at or below 1 GiB -- 19 for the warehouse map at
-        N_hor = 20). It needs ``tracker="mpc"``, ``fused=True``, ``n_hyp == 1`` and ``H * mmp_hyp <= 256``.
+        N_hor = 20). It needs ``tracker="mpc"``, ``fused=True``, ``n_hyp == 1`` and ``H * mmp_hyp <= 256``. ``mmp_stem``: a
+        :class:`.mmp_stem.StemSpec` (``mmp_stem.split_network`` / ``fold_stem``) = the network's first layer, computed by the
+        device stage itself (``nmpc_mmp_stem_*``, csrc/nmpc_mmp_stem.h) without the input stack ever being written; ``network``
+        is then the trunk behind it, called on ``[M, C, Hp, Wp]``, and the chunk is sized from that tensor (34 pedestrians for
+        the warehouse map at N_hor = 20 and C = 64). ``None`` (default): the stage as described above.
 
         ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the
@@ -163,6 +167,11 @@ class BatchEvaluator:
             raise ValueError("tracker = 'mpc' needs a predictor (cvmp, kfmp or mmp)")
         if predictor not in ("cvmp", "kfmp") and not (tracker == "dwa" and predictor is None) and not (tracker == "mpc" and predictor == "mmp"):
             raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; mmp with tracker = 'mpc'; None with tracker = 'dwa')")
+        if mmp_stem is not None:
+            if predictor != "mmp":
+                raise ValueError("mmp_stem needs predictor = 'mmp'")
+            from .mmp_stem import check_spec
+            mmp_stem = check_spec(mmp_stem)
         if predictor == "mmp":
             if self.n_hyp != 1 or not fused:
                 raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
@@ -260,7 +269,7 @@ class BatchEvaluator:
         else:
             self._init_dwa(robot_paths)
         if predictor == "mmp":
-            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale)
+            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_stem)
 
     def _tensor(self, x):
         return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
@@ -321,8 +330,10 @@ class BatchEvaluator:
         self._info, self._evals = self._full(B, 8), self._full(B)
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
 
-    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale):
-        """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the chunk."""
+    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem):
+        """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the shape of
+        one row of the network's input -- the stack's [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp] -- and the
+        chunk."""
         img = np.ascontiguousarray(ref_image, dtype=np.float32)
         if img.ndim != 2:
             raise ValueError(f"ref_image must be [Hm, Wm], got {img.shape}")
@@ -333,7 +344,12 @@ class BatchEvaluator:
         self.mmp_ref = self.torch.as_tensor(img, device=self.dev)
         # mmp_interface.py:60 snaps on 255 - ref_image; its grey levels decide the edges (Handle.set_map)
         self.h.set_map(255.0 - img.astype(np.float64))
-        per_ped = self.N * 7 * self.mmp_Hm * self.mmp_Wm * 4
+        self.mmp_stem, self.mmp_row = None, (7, self.mmp_Hm, self.mmp_Wm)
+        if stem is not None:
+            self.mmp_stem = stem._replace(weight=self.torch.as_tensor(stem.weight, device=self.dev), scale=self.torch.as_tensor(stem.scale, device=self.dev),
+                                          shift=self.torch.as_tensor(stem.shift, device=self.dev))
+            self.mmp_row = (int(stem.weight.shape[0]),) + _capi.mmp_stem_shape(self.mmp_Hm, self.mmp_Wm)
+        per_ped = self.N * int(np.prod(self.mmp_row)) * 4
         self.mmp_chunk = int(mmp_chunk) if mmp_chunk is not None else max(1, MMP_INPUT_BYTES // per_ped)
 
     def _init_dwa(self, robot_paths):
@@ -533,12 +549,12 @@ class BatchEvaluator:
         return kf
 
     def _mmp_args(self, r, max_steps):
-        """``NmpcMmpArgs`` of a run and the stage's buffers: the network's input tensor of one chunk, the hypotheses (pedestrian
+        """``NmpcMmpArgs`` (``NmpcMmpStemArgs`` with a fused first layer) of a run and the stage's buffers: the network's input tensor of one chunk, the hypotheses (pedestrian
         major as the network returns them, then per scenario as snap and f2 take them), f2's obstacle rows -- which f1 reads
         instead of ``loop_pre``'s -- and the per-step counts."""
         torch, B, N, H, K, z = self.torch, self.B, self.N, self.H, self.mmp_hyp, self._full
         chunk = min(self.mmp_chunk, B * H)
-        r.mmp_in = torch.empty(chunk, N, 7, self.mmp_Hm, self.mmp_Wm, dtype=torch.float32, device=self.dev)
+        r.mmp_in = torch.empty(chunk, N, *self.mmp_row, dtype=torch.float32, device=self.dev)
         r.mmp_raw_p, r.mmp_hyp = z(B * H, N, K, 2), z(B, N, H * K, 2)
         r.mmp_dyn = z(B, self.cfg.Ndynobs, N + 1, 6)
         r.mmp_n_obs, r.mmp_n_out = z(B, dtype=torch.int32, fill=0), z(B, dtype=torch.int32, fill=0)
@@ -547,14 +563,19 @@ class BatchEvaluator:
         r.mmp_all = torch.arange(B * H, dtype=torch.long, device=self.dev)
         r.mmp_events = []
         r.dyn_in = r.mmp_dyn
-        m = _capi.NmpcMmpArgs().set_transform(self.mmp_tf, self.mmp_rescale, MMP_SIGMA)
+        st = self.mmp_stem
+        m = (_capi.NmpcMmpArgs() if st is None else _capi.NmpcMmpStemArgs()).set_transform(self.mmp_tf, self.mmp_rescale, MMP_SIGMA)
+        if st is not None:
+            m.C, m.slope = self.mmp_row[0], st.slope
+            m.weight, m.bn_scale, m.bn_shift = st.weight.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr()
+        r.mmp_fill = self.h.mmp_input if st is None else self.h.mmp_stem     # what writes the network's input
         m.B, m.H, m.n_off, m.Hm, m.Wm = B, H, N, self.mmp_Hm, self.mmp_Wm
         m.hist, m.hcount, m.ref_image, m.out = self.hist.data_ptr(), self.hcount.data_ptr(), self.mmp_ref.data_ptr(), r.mmp_in.data_ptr()
         return m
 
     def _mmp_predict(self, r, m, kt, idx, nA):
         """The multi-hypothesis predictor for the ``nA`` running scenarios (``idx``, None = all), MainBase.run_wta_prediction
-        (main_base.py:175-208): per chunk of pedestrians input stack -> network; then, per scenario with its pedestrians'
+        (main_base.py:175-208): per chunk of pedestrians input stack (or the fused first layer's output) -> network; then, per scenario with its pedestrians'
         segments concatenated in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]``."""
         torch, N, H, K = self.torch, self.N, self.H, self.mmp_hyp
 
@@ -572,9 +593,9 @@ class BatchEvaluator:
         for c0 in range(0, n_ped, self.mmp_chunk):
             n = min(self.mmp_chunk, n_ped - c0)
             m.n_item, m.items = n, items[c0:].data_ptr()
-            part("input", lambda: self.h.mmp_input(self.dt, m))
+            part("input", lambda: r.mmp_fill(self.dt, m))
             with torch.no_grad():
-                out = part("network", lambda: self.network(r.mmp_in[:n].view(n * N, 7, self.mmp_Hm, self.mmp_Wm)))
+                out = part("network", lambda: self.network(r.mmp_in[:n].view(n * N, *self.mmp_row)))
             if out.numel() != n * N * K * 2:
                 raise ValueError(f"the network returned {tuple(out.shape)} for {n * N} inputs; expected {K} hypotheses (x, y) each")
             r.mmp_raw_p[c0:c0 + n] = out.reshape(n, N, K, 2)

@@ -8,7 +8,8 @@ or ``[M, K, 2]`` pixel hypotheses, e.g. a ``ConvMultiHypoNet`` the caller has bu
 weights and holds no configuration.
 
 What the reference does on the host around the network runs on the device: the input stack (``pre_load.traj_to_input`` and
-the copy per time offset) through ``nmpc_mmp_input_f64`` with one item, ``get_closest_edge_point(...) / rescale`` through
+the copy per time offset) through ``nmpc_mmp_input_f64`` with one item (with ``stem=``, a :class:`.mmp_stem.StemSpec`, the
+stack and the network's first layer in one kernel, ``nmpc_mmp_stem_f64``, and ``network`` = the trunk), ``get_closest_edge_point(...) / rescale`` through
 ``nmpc_snap_hypotheses_f64`` with the identity transform. There is no host implementation of either in this package.
 
 For whole batches of scenarios use ``evaluate.BatchEvaluator(predictor="mmp")``, which keeps the pedestrians' histories on
@@ -28,11 +29,17 @@ OBSV_LEN = 5        # config.obsv_len of the reference's network configurations
 
 
 class MmpInterface:
-    def __init__(self, network: Callable):
+    def __init__(self, network: Callable, stem=None):
+        """``stem``: a :class:`.mmp_stem.StemSpec` = the network's first layer, computed on the device without the input stack
+        (``nmpc_mmp_stem_f64``); ``network`` is then the trunk behind it, a callable on ``[M, C, Hp, Wp]``."""
         if not callable(network):
             raise TypeError(f"network must be a callable, got {type(network)}")
         self._prt_name = "MMPInterface"
         self.network = network
+        self.stem, self._stem_dev = None, None
+        if stem is not None:
+            from .mmp_stem import check_spec
+            self.stem = check_spec(stem)
         self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)
         self._map_of = {}         # pred_offset -> the ref_image its map was set from
 
@@ -75,12 +82,20 @@ class MmpInterface:
         d_hist = torch.from_numpy(hist.reshape(1, 1, OBSV_LEN, 2)).cuda()
         d_count = torch.full((1, 1), traj.shape[0], dtype=torch.long, device="cuda")
         d_ref = torch.from_numpy(img).cuda()
-        stack = torch.empty(N, 7, Hm, Wm, dtype=torch.float32, device="cuda")
         ident = WorldTransform()
-        a = _capi.NmpcMmpArgs().set_transform(ident, rescale, SIGMA)
+        if self.stem is None:
+            stack = torch.empty(N, 7, Hm, Wm, dtype=torch.float32, device="cuda")
+            a, fill = _capi.NmpcMmpArgs().set_transform(ident, rescale, SIGMA), h.mmp_input
+        else:
+            if self._stem_dev is None:
+                self._stem_dev = tuple(torch.from_numpy(v).cuda() for v in self.stem[:3])
+            w, sc, sh = self._stem_dev
+            stack = torch.empty(N, w.shape[0], *_capi.mmp_stem_shape(Hm, Wm), dtype=torch.float32, device="cuda")
+            a, fill = _capi.NmpcMmpStemArgs().set_transform(ident, rescale, SIGMA), h.mmp_stem
+            a.C, a.slope, a.weight, a.bn_scale, a.bn_shift = w.shape[0], self.stem.slope, w.data_ptr(), sc.data_ptr(), sh.data_ptr()
         a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = 1, 1, 1, N, Hm, Wm
         a.hist, a.hcount, a.ref_image, a.out = d_hist.data_ptr(), d_count.data_ptr(), d_ref.data_ptr(), stack.data_ptr()
-        h.mmp_input(np.float64, a)
+        fill(np.float64, a)
         with torch.no_grad():
             outs = [self.network(stack[i:i + bs]) for i in range(0, N, bs)]
         raw = torch.cat([o.reshape(o.shape[0], -1, 2) for o in outs], dim=0).to(torch.float64)

@@ -9,7 +9,14 @@ The network is a randomly initialised module with the layer shapes of the refere
 stem with 64 channels, 3 x 3 max-pool, residual stages of 3 / 4 / 6 / 3 basic blocks with 16 / 32 / 64 / 128 channels, 2 x 2
 average pool, 3200 -> 128 -> 2 K), written here: the trained weights are not available, so its hypotheses mean nothing and
 only its cost is of interest. The map is the warehouse label image of tests/golden/snap_map.npz.
-   usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]        (defaults 256 3 f32 4 20)"""
+
+``--fused-stem``: the same network split by hand into its first layer (``mmp_stem.fold_stem``: convolution, norm, LeakyReLU,
+max-pool -> ``nmpc_mmp_stem_*``) and the trunk behind it; the parent path (input stack + whole network) and the fused path
+(fused first layer + trunk) run in the same process on the same device, alternately, with HIP events around ``input``,
+``network`` and the whole stage of every lock-step; the medians over the alternated repetitions are compared. Beside them: the
+fused kernel alone on one chunk as bytes stored per second against the float4 copy rate, and torch's own first layer alone on
+one chunk of the parent path -- the share of the network's time that the first layer is.
+   usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp] [--fused-stem [REPS]]   (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
 import sys
@@ -78,7 +85,122 @@ def input_kernel_rate(ev, n_item, reps=20):
             "write_GBps_best": nbytes / min(ms) * 1e-6, "share_of_copy_rate": nbytes / med * 1e-9 / COPY_TBS, "share_of_f1_rate": nbytes / med * 1e-9 / F1_TBS}
 
 
+def stem_kernel_rate(ev, n_item, reps=20):
+    """ms and GB/s stored of nmpc_mmp_stem_* alone on ``n_item`` pedestrians of the evaluator's start state."""
+    st = ev.mmp_stem
+    out = torch.empty(n_item, ev.N, *ev.mmp_row, dtype=torch.float32, device=ev.dev)
+    a = nm._capi.NmpcMmpStemArgs().set_transform(ev.mmp_tf, ev.mmp_rescale, MMP_SIGMA)
+    a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = ev.B, ev.H, n_item, ev.N, ev.mmp_Hm, ev.mmp_Wm
+    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
+    a.hist, a.hcount, a.ref_image, a.out = hist.data_ptr(), hcount.data_ptr(), ev.mmp_ref.data_ptr(), out.data_ptr()
+    a.C, a.slope, a.weight, a.bn_scale, a.bn_shift = ev.mmp_row[0], st.slope, st.weight.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr()
+    ms = []
+    for i in range(5 + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ev.h.mmp_stem(ev.dt, a)
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= 5:
+            ms.append(e0.elapsed_time(e1))
+    nbytes, med = out.numel() * 4, float(np.median(ms))
+    fma = n_item * ev.mmp_row[0] * ((ev.mmp_Hm - 1) // 2 + 1) * ((ev.mmp_Wm - 1) // 2 + 1) * 343        # base and E, once per pedestrian
+    return {"items": n_item, "bytes_stored": nbytes, "ms_median": med, "ms_min": float(min(ms)), "store_GBps_median": nbytes / med * 1e-6,
+            "share_of_copy_rate": nbytes / med * 1e-9 / COPY_TBS, "conv_fma": fma, "conv_TFMAps_median": fma / med * 1e-9}
+
+
+def torch_stem_alone(ev, stem_modules, n_item, reps=5):
+    """ms of torch's own first layer (the four modules, eager) on the input stack of ``n_item`` pedestrians: one chunk of the parent path."""
+    x = torch.empty(n_item * ev.N, 7, ev.mmp_Hm, ev.mmp_Wm, dtype=torch.float32, device=ev.dev)
+    a = nm._capi.NmpcMmpArgs().set_transform(ev.mmp_tf, ev.mmp_rescale, MMP_SIGMA)
+    a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = ev.B, ev.H, n_item, ev.N, ev.mmp_Hm, ev.mmp_Wm
+    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
+    a.hist, a.hcount, a.ref_image, a.out = hist.data_ptr(), hcount.data_ptr(), ev.mmp_ref.data_ptr(), x.data_ptr()
+    ev.h.mmp_input(ev.dt, a)
+    ms = []
+    with torch.no_grad():
+        for i in range(2 + reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            y = stem_modules(x)
+            e1.record()
+            torch.cuda.synchronize()
+            del y
+            if i >= 2:
+                ms.append(e0.elapsed_time(e1))
+    return {"items": n_item, "samples": n_item * ev.N, "ms_median": float(np.median(ms)), "ms_min": float(min(ms))}
+
+
+def fused_stem_main(out_path, B, steps, dt, n_ped, K, reps):
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import fold_stem
+    z = np.load(os.path.join(ROOT, "tests", "golden", "snap_map.npz"))
+    Hm, Wm = (int(v) for v in z["shape"])
+    occupied = np.unpackbits(z["occupied_bits"])[:Hm * Wm].reshape(Hm, Wm).astype(bool)
+    ref = np.where(occupied, 0.0, 255.0).astype(np.float32)
+    tf = WorldTransform(scale=0.1, offsetx_after=-15.0, offsety_after=-15.0, y_reverse=True, y_max_before=float(Hm))
+    sc = nm.scenarios.make_reference_scenarios(B, n_ped=n_ped)
+    sc.pop("scenario_index")
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    # the split, by hand: net[0] = Sequential(Conv2d, BatchNorm2d, LeakyReLU), net[1] = MaxPool2d, the rest is the trunk
+    spec = fold_stem(net[0][0], net[0][1], net[0][2], net[1])
+    stem_modules, trunk = torch.nn.Sequential(net[0], net[1]), torch.nn.Sequential(*list(net)[2:])
+    paths = {"parent": dict(network=lambda x: net(x) + 150.0), "fused": dict(network=lambda x: trunk(x) + 150.0, mmp_stem=spec)}
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage: the parent path (input stack + whole "
+                   "network) and the fused first layer + trunk, alternated in one process; random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS}, "chunk_pedestrians": {}, "runs": {"parent": [], "fused": []}}
+    for path in paths:                                      # warm-up: code objects, library algorithm choice, allocator
+        ev = evaluator(path)
+        rec["chunk_pedestrians"][path] = ev.mmp_chunk
+        try:
+            if path == "fused":
+                rec["stem_kernel"] = stem_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped))
+            else:
+                rec["torch_stem_alone"] = torch_stem_alone(ev, stem_modules, min(ev.mmp_chunk, B * n_ped))
+            ev.run(max_steps=1)
+        finally:
+            ev.close()
+        print(json.dumps({k: rec[k] for k in ("stem_kernel", "torch_stem_alone") if k in rec}), flush=True)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    both = lambda s: s["input"] + s["network"]
+    rec["median_per_lock_step_ms"] = {p: {"input": med(p, lambda s: s["input"]), "network": med(p, lambda s: s["network"]),
+                                          "input_plus_network": med(p, both), "stage": med(p, lambda s: s["stage_ms"])} for p in paths}
+    m = rec["median_per_lock_step_ms"]
+    rec["fused_over_parent"] = m["fused"]["input_plus_network"] / m["parent"]["input_plus_network"]
+    # torch's first layer alone on one chunk, scaled to the pedestrians of a lock-step: its share of the parent's network time
+    ts = rec["torch_stem_alone"]
+    rec["torch_stem_share_of_parent_network"] = ts["ms_median"] * (B * n_ped / ts["items"]) / m["parent"]["network"]
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "fused_over_parent", "torch_stem_share_of_parent_network")}))
+
+
 def main():
+    if "--fused-stem" in sys.argv:
+        i = sys.argv.index("--fused-stem")
+        reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
+        argv = sys.argv[1:i]
+        B, steps, dt, n_ped, K = (argv[1:] + ["256", "3", "f32", "4", "20"][len(argv) - 1:])[:5]
+        return fused_stem_main(argv[0], int(B), int(steps), dt, int(n_ped), int(K), reps)
     out_path = sys.argv[1]
     B, steps, dt, n_ped, K = (sys.argv[2:] + ["256", "3", "f32", "4", "20"][len(sys.argv) - 2:])[:5]
     B, steps, n_ped, K = int(B), int(steps), int(n_ped), int(K)
