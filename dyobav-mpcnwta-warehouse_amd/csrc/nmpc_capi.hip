@@ -27,6 +27,7 @@
 #include "nmpc_snap.h"
 #include "nmpc_mmp.h"
 #include "nmpc_mmp_stem.h"
+#include "nmpc_mmp_block.h"
 
 using namespace nmpc_plan;
 
@@ -1572,6 +1573,51 @@ int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g)
     return 0;
 }
 
+int mmp_block(nmpc_handle_s* h, const nmpc_mmp_block_args* g)
+{
+    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if (g->M < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: M = %d < 0", g->M);
+    if (g->H < 1 || g->W < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: plane %d x %d", g->H, g->W);
+    if (g->Cin < 8 || g->Cin > 256 || g->Cin % nmpc::kBlkCC)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: Cin = %d is no multiple of 8 from 8 to 256", g->Cin);
+    if (!g->wd && g->Cin != nmpc::kBlkC)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: Cin = %d without a projection (the identity needs Cin = 16)", g->Cin);
+    if (!std::isfinite(g->slope_mid) || !std::isfinite(g->slope_out))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: slope_mid = %g, slope_out = %g", (double)g->slope_mid, (double)g->slope_out);
+    if (!g->x || !g->w1 || !g->s1 || !g->b1 || !g->w2 || !g->s2 || !g->b2 || (g->wd && (!g->sd || !g->bd)) || !g->out)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: a required array is NULL");
+    if (reinterpret_cast<uintptr_t>(g->out) % 4 || reinterpret_cast<uintptr_t>(g->x) % 4)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: x or out is not aligned to float");
+    if (g->M == 0) return 0;
+    nmpc::MmpBlockParams p;
+    std::memset(&p, 0, sizeof p);
+    const long long ty = ((long long)g->H + nmpc::kBlkTH - 1) / nmpc::kBlkTH, tx = ((long long)g->W + nmpc::kBlkTW - 1) / nmpc::kBlkTW;
+    const long long tiles = ty * tx; // < 2^56
+    if (tiles > 0x7fffffffLL || tiles * g->M > 0x7fffffffLL) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block: %lld x %d workgroups", tiles, g->M);
+    const long long groups = tiles * g->M;
+    p.ty = (int)ty, p.tx = (int)tx;
+    // out must not overlap x: a tile's halo is read after the neighbouring tiles have been written
+    const unsigned long long hw = (unsigned long long)g->H * g->W * g->M * 4; // < 2^31 * 420 * 4 after the test above
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(g->x), o0 = reinterpret_cast<uintptr_t>(g->out);
+    if (x0 < o0 + hw * nmpc::kBlkC && o0 < x0 + hw * g->Cin) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: out overlaps x");
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    // (a host pointer here would fault inside the kernel)
+    if (h->ptr_mode != NMPC_PTR_DEVICE) {
+        const void* ptrs[] = {g->x, g->w1, g->s1, g->b1, g->w2, g->s2, g->b2, g->out, g->wd, g->sd, g->bd};
+        for (int i = 0; i < (g->wd ? 11 : 8); ++i)
+            if (!is_device_ptr(ptrs[i])) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block: every array must be a device pointer");
+    }
+    p.M = g->M, p.Cin = g->Cin, p.H = g->H, p.W = g->W;
+    p.x = g->x, p.w1 = g->w1, p.s1 = g->s1, p.b1 = g->b1, p.w2 = g->w2, p.s2 = g->s2, p.b2 = g->b2;
+    p.wd = g->wd, p.sd = g->sd, p.bd = g->bd, p.slope_mid = g->slope_mid, p.slope_out = g->slope_out, p.out = g->out;
+    if (g->wd)
+        hipLaunchKernelGGL(nmpc::mmp_block_kernel<true>, dim3((unsigned)groups), dim3(nmpc::kBlkThreads), 0, h->stream, p);
+    else
+        hipLaunchKernelGGL(nmpc::mmp_block_kernel<false>, dim3((unsigned)groups), dim3(nmpc::kBlkThreads), 0, h->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // largest nv * nw a scenario's window can give: per axis the window is at most min(range, 2 acc ts) wide and np.arange's
 // count is ceil of a quotient that rounding can lift past an integer, so floor(...) + 1 (host only)
 static long long dwa_axis_bound(double range, double acc, double ts, double res)
@@ -1996,6 +2042,7 @@ int nmpc_mmp_input_f32(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input
 int nmpc_mmp_input_f64(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input<double>(h, a); }
 int nmpc_mmp_stem_f32(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<float>(h, a); }
 int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<double>(h, a); }
+int nmpc_mmp_block_f32(nmpc_handle h, const nmpc_mmp_block_args* a) { return mmp_block(h, a); }
 int nmpc_mmp_stem_shape(int32_t Hm, int32_t Wm, int32_t* Hp, int32_t* Wp)
 {
     if (Hm < 1 || Wm < 1 || !Hp || !Wp) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem_shape: map %d x %d or a NULL output", Hm, Wm);

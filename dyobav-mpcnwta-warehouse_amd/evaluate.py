@@ -124,7 +124,7 @@ class BatchEvaluator:
                  compact: Optional[bool] = None, fused: bool = True, n_hyp: int = 1, hyp_fan: float = 0.15,
                  hyp_radius_growth: float = 0.05, predictor: Optional[str] = "cvmp", kf_Q=None, kf_R=None, kf_P0=None,
                  tracker: str = "mpc", dwa_config=None, network=None, mmp_hyp: int = 20, mmp_chunk: Optional[int] = None,
-                 ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None):
+                 ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None, mmp_blocks=None):
         """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
@@ -150,7 +150,14 @@ class BatchEvaluator:
         :class:`.mmp_stem.StemSpec` (``mmp_stem.split_network`` / ``fold_stem``) = the network's first layer, computed by the
         device stage itself (``nmpc_mmp_stem_*``, csrc/nmpc_mmp_stem.h) without the input stack ever being written; ``network``
         is then the trunk behind it, called on ``[M, C, Hp, Wp]``, and the chunk is sized from that tensor (34 pedestrians for
-        the warehouse map at N_hor = 20 and C = 64). ``None`` (default): the stage as described above.
+        the warehouse map at N_hor = 20 and C = 64). ``None`` (default): the stage as described above. ``mmp_blocks`` (needs
+        ``mmp_stem``): the :class:`.mmp_stem.BlockSpec` s of the network's first residual stage (``mmp_stem.split_network_layer1``:
+        three for the reference's ``resnet34.layer1``; the first takes the stem's C channels, each later one 16), run by the device
+        stage as one fused kernel per block (``nmpc_mmp_block_f32``, csrc/nmpc_mmp_block.h) between two 16-channel buffers;
+        ``network`` is then the trunk from ``layer2`` on, called on ``[M, 16, Hp, Wp]``, and the chunk keeps the stem's output plus
+        both buffers at or below 1 GiB (22 pedestrians for the warehouse map at N_hor = 20 and C = 64). Measured on an MI355X at
+        B = 256, 4 pedestrians, K = 20 (``profiles/mmp_layer1_evaluate.json``): the stage takes 524 ms per
+        lock-step against 685 ms with ``mmp_stem`` alone; the three block launches 88 ms where torch's own layer1 took 232.
 
         ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the
@@ -172,6 +179,11 @@ class BatchEvaluator:
                 raise ValueError("mmp_stem needs predictor = 'mmp'")
             from .mmp_stem import check_spec
             mmp_stem = check_spec(mmp_stem)
+        if mmp_blocks is not None:
+            if mmp_stem is None:
+                raise ValueError("mmp_blocks needs mmp_stem (the blocks run on the fused first layer's output)")
+            from .mmp_stem import check_blocks
+            mmp_blocks = check_blocks(mmp_stem, mmp_blocks)
         if predictor == "mmp":
             if self.n_hyp != 1 or not fused:
                 raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
@@ -196,7 +208,8 @@ class BatchEvaluator:
         self.kf_Q, self.kf_R, self.kf_P0 = eye(kf_Q, 4), eye(kf_R, 2), eye(kf_P0, 4)
         # time_predictor / time_tracker: HIP events around every nmpc_kf_predict / nmpc_dwa_step call; run() leaves the
         # times (ms) in predictor_ms / tracker_ms
-        # (predictor "mmp": time_predictor_parts adds events around its four parts; predictor_part_ms: name -> ms per step)
+        # (predictor "mmp": time_predictor_parts adds events around its four parts -- five with mmp_blocks: "layer1" --;
+        # predictor_part_ms: name -> ms per step)
         self.time_predictor, self.time_tracker, self.time_predictor_parts = False, False, False
         self.predictor_ms, self.tracker_ms, self.predictor_part_ms = [], [], {}
         self.time_solves = True     # record the HIP-event time of every batched solve (one event wait per time step)
@@ -269,7 +282,7 @@ class BatchEvaluator:
         else:
             self._init_dwa(robot_paths)
         if predictor == "mmp":
-            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_stem)
+            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_stem, mmp_blocks)
 
     def _tensor(self, x):
         return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
@@ -330,10 +343,10 @@ class BatchEvaluator:
         self._info, self._evals = self._full(B, 8), self._full(B)
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
 
-    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem):
+    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem, blocks=None):
         """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the shape of
-        one row of the network's input -- the stack's [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp] -- and the
-        chunk."""
+        one row of the network's input -- the stack's [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind
+        fused blocks [16, Hp, Wp] -- and the chunk."""
         img = np.ascontiguousarray(ref_image, dtype=np.float32)
         if img.ndim != 2:
             raise ValueError(f"ref_image must be [Hm, Wm], got {img.shape}")
@@ -349,7 +362,14 @@ class BatchEvaluator:
             self.mmp_stem = stem._replace(weight=self.torch.as_tensor(stem.weight, device=self.dev), scale=self.torch.as_tensor(stem.scale, device=self.dev),
                                           shift=self.torch.as_tensor(stem.shift, device=self.dev))
             self.mmp_row = (int(stem.weight.shape[0]),) + _capi.mmp_stem_shape(self.mmp_Hm, self.mmp_Wm)
+        self.mmp_fill_row, self.mmp_blocks = self.mmp_row, None    # a row of what nmpc_mmp_input_* / nmpc_mmp_stem_* write
         per_ped = self.N * int(np.prod(self.mmp_row)) * 4
+        if blocks is not None:
+            dev = lambda v: None if v is None else self.torch.as_tensor(v, device=self.dev)
+            self.mmp_blocks = tuple(b._replace(**{n: dev(getattr(b, n)) for n in ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")}) for b in blocks)
+            C, Hp, Wp = self.mmp_row
+            self.mmp_row = (16, Hp, Wp)
+            per_ped = self.N * (C + 32) * Hp * Wp * 4           # the stem's output and the two buffers the blocks alternate between
         self.mmp_chunk = int(mmp_chunk) if mmp_chunk is not None else max(1, MMP_INPUT_BYTES // per_ped)
 
     def _init_dwa(self, robot_paths):
@@ -554,7 +574,21 @@ class BatchEvaluator:
         instead of ``loop_pre``'s -- and the per-step counts."""
         torch, B, N, H, K, z = self.torch, self.B, self.N, self.H, self.mmp_hyp, self._full
         chunk = min(self.mmp_chunk, B * H)
-        r.mmp_in = torch.empty(chunk, N, *self.mmp_row, dtype=torch.float32, device=self.dev)
+        r.mmp_in = torch.empty(chunk, N, *self.mmp_fill_row, dtype=torch.float32, device=self.dev)
+        r.mmp_net_in, r.mmp_block_args = r.mmp_in, ()
+        if self.mmp_blocks is not None:
+            r.mmp_pp = torch.empty(2, chunk, N, *self.mmp_row, dtype=torch.float32, device=self.dev)
+            args, src = [], r.mmp_in
+            for i, b in enumerate(self.mmp_blocks):
+                a = _capi.NmpcMmpBlockArgs()
+                a.Cin, a.H, a.W = int(b.w1.shape[1]), self.mmp_row[1], self.mmp_row[2]
+                for name in ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd"):
+                    setattr(a, name, None if getattr(b, name) is None else getattr(b, name).data_ptr())
+                a.slope_mid, a.slope_out = b.slope_mid, b.slope_out
+                a.x, a.out = src.data_ptr(), r.mmp_pp[i % 2].data_ptr()
+                src = r.mmp_pp[i % 2]
+                args.append(a)
+            r.mmp_net_in, r.mmp_block_args = src, tuple(args)
         r.mmp_raw_p, r.mmp_hyp = z(B * H, N, K, 2), z(B, N, H * K, 2)
         r.mmp_dyn = z(B, self.cfg.Ndynobs, N + 1, 6)
         r.mmp_n_obs, r.mmp_n_out = z(B, dtype=torch.int32, fill=0), z(B, dtype=torch.int32, fill=0)
@@ -566,7 +600,7 @@ class BatchEvaluator:
         st = self.mmp_stem
         m = (_capi.NmpcMmpArgs() if st is None else _capi.NmpcMmpStemArgs()).set_transform(self.mmp_tf, self.mmp_rescale, MMP_SIGMA)
         if st is not None:
-            m.C, m.slope = self.mmp_row[0], st.slope
+            m.C, m.slope = self.mmp_fill_row[0], st.slope
             m.weight, m.bn_scale, m.bn_shift = st.weight.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr()
         r.mmp_fill = self.h.mmp_input if st is None else self.h.mmp_stem     # what writes the network's input
         m.B, m.H, m.n_off, m.Hm, m.Wm = B, H, N, self.mmp_Hm, self.mmp_Wm
@@ -575,7 +609,7 @@ class BatchEvaluator:
 
     def _mmp_predict(self, r, m, kt, idx, nA):
         """The multi-hypothesis predictor for the ``nA`` running scenarios (``idx``, None = all), MainBase.run_wta_prediction
-        (main_base.py:175-208): per chunk of pedestrians input stack (or the fused first layer's output) -> network; then, per scenario with its pedestrians'
+        (main_base.py:175-208): per chunk of pedestrians input stack (or the fused first layer's output, then the fused blocks of layer1) -> network; then, per scenario with its pedestrians'
         segments concatenated in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]``."""
         torch, N, H, K = self.torch, self.N, self.H, self.mmp_hyp
 
@@ -588,14 +622,21 @@ class BatchEvaluator:
             e1.record()
             r.mmp_events.append((kt, name, e0, e1))
             return out
+
+        def layer1(rows):
+            for a in r.mmp_block_args:
+                a.M = rows
+                self.h.mmp_block(a)
         items = r.mmp_all if idx is None else (idx[:, None] * H + r.mmp_all[None, :H]).reshape(-1).contiguous()
         n_ped = nA * H
         for c0 in range(0, n_ped, self.mmp_chunk):
             n = min(self.mmp_chunk, n_ped - c0)
             m.n_item, m.items = n, items[c0:].data_ptr()
             part("input", lambda: r.mmp_fill(self.dt, m))
+            if r.mmp_block_args:
+                part("layer1", lambda: layer1(n * N))
             with torch.no_grad():
-                out = part("network", lambda: self.network(r.mmp_in[:n].view(n * N, *self.mmp_row)))
+                out = part("network", lambda: self.network(r.mmp_net_in[:n].view(n * N, *self.mmp_row)))
             if out.numel() != n * N * K * 2:
                 raise ValueError(f"the network returned {tuple(out.shape)} for {n * N} inputs; expected {K} hypotheses (x, y) each")
             r.mmp_raw_p[c0:c0 + n] = out.reshape(n, N, K, 2)

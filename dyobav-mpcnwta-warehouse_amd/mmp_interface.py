@@ -9,7 +9,8 @@ weights and holds no configuration.
 
 What the reference does on the host around the network runs on the device: the input stack (``pre_load.traj_to_input`` and
 the copy per time offset) through ``nmpc_mmp_input_f64`` with one item (with ``stem=``, a :class:`.mmp_stem.StemSpec`, the
-stack and the network's first layer in one kernel, ``nmpc_mmp_stem_f64``, and ``network`` = the trunk), ``get_closest_edge_point(...) / rescale`` through
+stack and the network's first layer in one kernel, ``nmpc_mmp_stem_f64``, and ``network`` = the trunk; with ``blocks=`` as well, the
+first residual stage behind it, one ``nmpc_mmp_block_f32`` per block), ``get_closest_edge_point(...) / rescale`` through
 ``nmpc_snap_hypotheses_f64`` with the identity transform. There is no host implementation of either in this package.
 
 For whole batches of scenarios use ``evaluate.BatchEvaluator(predictor="mmp")``, which keeps the pedestrians' histories on
@@ -29,9 +30,11 @@ OBSV_LEN = 5        # config.obsv_len of the reference's network configurations
 
 
 class MmpInterface:
-    def __init__(self, network: Callable, stem=None):
+    def __init__(self, network: Callable, stem=None, blocks=None):
         """``stem``: a :class:`.mmp_stem.StemSpec` = the network's first layer, computed on the device without the input stack
-        (``nmpc_mmp_stem_f64``); ``network`` is then the trunk behind it, a callable on ``[M, C, Hp, Wp]``."""
+        (``nmpc_mmp_stem_f64``); ``network`` is then the trunk behind it, a callable on ``[M, C, Hp, Wp]``. ``blocks`` (needs
+        ``stem``): the :class:`.mmp_stem.BlockSpec` s of the residual stage behind the stem (``mmp_stem.split_network_layer1``),
+        one fused kernel each (``nmpc_mmp_block_f32``); ``network`` is then called on ``[M, 16, Hp, Wp]``."""
         if not callable(network):
             raise TypeError(f"network must be a callable, got {type(network)}")
         self._prt_name = "MMPInterface"
@@ -40,6 +43,12 @@ class MmpInterface:
         if stem is not None:
             from .mmp_stem import check_spec
             self.stem = check_spec(stem)
+        self.blocks, self._blocks_dev = None, None
+        if blocks is not None:
+            if self.stem is None:
+                raise ValueError("blocks needs stem (the blocks run on the fused first layer's output)")
+            from .mmp_stem import check_blocks
+            self.blocks = check_blocks(self.stem, blocks)
         self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)
         self._map_of = {}         # pred_offset -> the ref_image its map was set from
 
@@ -96,6 +105,19 @@ class MmpInterface:
         a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = 1, 1, 1, N, Hm, Wm
         a.hist, a.hcount, a.ref_image, a.out = d_hist.data_ptr(), d_count.data_ptr(), d_ref.data_ptr(), stack.data_ptr()
         fill(np.float64, a)
+        if self.blocks is not None:
+            if self._blocks_dev is None:
+                self._blocks_dev = [{n: torch.from_numpy(getattr(b, n)).cuda() for n in ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
+                                     if getattr(b, n) is not None} for b in self.blocks]
+            for b, dev in zip(self.blocks, self._blocks_dev):
+                out = torch.empty(N, 16, *stack.shape[2:], dtype=torch.float32, device="cuda")
+                g = _capi.NmpcMmpBlockArgs()
+                g.M, g.Cin, g.H, g.W = N, int(b.w1.shape[1]), int(stack.shape[2]), int(stack.shape[3])
+                for name, t in dev.items():
+                    setattr(g, name, t.data_ptr())
+                g.slope_mid, g.slope_out, g.x, g.out = b.slope_mid, b.slope_out, stack.data_ptr(), out.data_ptr()
+                h.mmp_block(g)
+                stack = out
         with torch.no_grad():
             outs = [self.network(stack[i:i + bs]) for i in range(0, N, bs)]
         raw = torch.cat([o.reshape(o.shape[0], -1, 2) for o in outs], dim=0).to(torch.float64)

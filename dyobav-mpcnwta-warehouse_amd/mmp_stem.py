@@ -9,10 +9,18 @@ shape, ``fold_stem`` for the four modules alone. ``BatchEvaluator(predictor="mmp
 
 The fold is done in float64 and rounded once to float: ``scale = gamma / sqrt(var + eps)``, ``shift = beta - mean * scale``
 (+ ``scale * bias`` for a convolution with a bias). It is only valid for a norm in inference mode: batch statistics couple the
-rows of a batch, which a per-pedestrian kernel cannot reproduce."""
+rows of a batch, which a per-pedestrian kernel cannot reproduce.
+
+The first residual stage behind the stem, ``resnet34.layer1`` = three ``BasicBlock`` s at 16 channels on the stem's
+resolution (net_module/net.py:45-61), can go the same way (``nmpc_mmp_block_f32``, csrc/nmpc_mmp_block.h): ``BlockSpec`` = both
+3 x 3 convolutions with their folded norms, the 1 x 1 projection of the first block (``None`` for the other two) and the two
+slopes -- 0.1 inside the block (``compact_conv_layer``), 0.01 behind the addition (a default ``nn.LeakyReLU``).
+``fold_block`` folds one block, ``split_network_layer1(net)`` returns the stem, the three blocks and the trunk from
+``layer2`` on, for ``BatchEvaluator(..., mmp_stem=spec, mmp_blocks=blocks, network=trunk)`` and
+``MmpInterface(trunk, stem=spec, blocks=blocks)``."""
 from __future__ import annotations
 
-from typing import Callable, NamedTuple, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -22,6 +30,23 @@ class StemSpec(NamedTuple):
     scale: np.ndarray       # [C] float32
     shift: np.ndarray       # [C] float32
     slope: float
+
+
+class BlockSpec(NamedTuple):
+    w1: np.ndarray                  # [16, Cin, 3, 3] float32
+    s1: np.ndarray                  # [16] float32
+    b1: np.ndarray                  # [16] float32
+    slope_mid: float
+    w2: np.ndarray                  # [16, 16, 3, 3] float32
+    s2: np.ndarray                  # [16]
+    b2: np.ndarray                  # [16]
+    wd: Optional[np.ndarray]        # [16, Cin] float32, or None: the identity (Cin == 16)
+    sd: Optional[np.ndarray]        # [16] or None
+    bd: Optional[np.ndarray]        # [16] or None
+    slope_out: float
+
+
+BLOCK_CHANNELS = 16                 # output channels of the fused block (csrc/nmpc_mmp_block.h)
 
 
 def _pair(v):
@@ -107,3 +132,134 @@ def split_network(net) -> Tuple[StemSpec, Callable]:
             x = layer(x)
         return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
     return spec, trunk
+
+
+def _conv_norm(name, seq, n_parts):
+    import torch
+    try:
+        parts = list(seq)
+    except TypeError:
+        parts = []
+    if len(parts) != n_parts or not isinstance(parts[0], torch.nn.Conv2d) or not isinstance(parts[1], torch.nn.BatchNorm2d):
+        raise ValueError(f"fold_block: '{name}' is not Sequential(Conv2d, BatchNorm2d{', LeakyReLU' if n_parts == 3 else ''})")
+    conv, bn = parts[0], parts[1]
+    if bn.num_features != conv.out_channels:
+        raise ValueError(f"fold_block: the norm of '{name}' has {bn.num_features} channels, its convolution {conv.out_channels}")
+    if bn.training or bn.running_mean is None or bn.running_var is None:
+        raise ValueError(f"fold_block: the BatchNorm2d of '{name}' must be in eval() mode with running statistics: batch statistics "
+                         "couple the rows of a batch, which the fused block cannot reproduce")
+    return parts
+
+
+def _conv_is(name, conv, kernel, padding):
+    if (_pair(conv.kernel_size) != (kernel, kernel) or _pair(conv.stride) != (1, 1) or _pair(conv.padding) != (padding, padding)
+            or conv.groups != 1 or _pair(conv.dilation) != (1, 1) or conv.padding_mode != "zeros"):
+        raise ValueError(f"fold_block: '{name}' must have kernel {kernel}, stride 1, padding {padding}, groups 1, dilation 1 and "
+                         f"zero padding; got {conv}")
+
+
+def _slope(name, act) -> float:
+    import torch
+    if not isinstance(act, torch.nn.LeakyReLU):
+        raise ValueError(f"fold_block: the activation '{name}' must be a LeakyReLU, got {type(act).__name__}")
+    slope = float(act.negative_slope)
+    if not np.isfinite(slope) or abs(slope) > 1.0:
+        raise ValueError(f"fold_block: the slope of '{name}' is {slope}; it must be finite with |slope| <= 1")
+    return slope
+
+
+def fold_block(block) -> BlockSpec:
+    """A module shaped like the reference's ``BasicBlock`` at stride 1 -- ``conv1 = Sequential(Conv2d 3 x 3, BatchNorm2d,
+    LeakyReLU)``, ``conv2 = Sequential(Conv2d 3 x 3, BatchNorm2d)``, ``downsample = None | Sequential(Conv2d 1 x 1, BatchNorm2d)``,
+    ``leaky = LeakyReLU`` -- -> :class:`BlockSpec`; ``ValueError`` for anything the kernel does not compute."""
+    for name in ("conv1", "conv2", "downsample", "leaky"):
+        if not hasattr(block, name):
+            raise ValueError(f"fold_block: the module has no {name!r}")
+    c1, n1, act = _conv_norm("conv1", block.conv1, 3)
+    c2, n2 = _conv_norm("conv2", block.conv2, 2)
+    _conv_is("conv1", c1, 3, 1)
+    _conv_is("conv2", c2, 3, 1)
+    Cin = int(c1.in_channels)
+    if c1.out_channels != BLOCK_CHANNELS or c2.in_channels != BLOCK_CHANNELS or c2.out_channels != BLOCK_CHANNELS:
+        raise ValueError(f"fold_block: the block must have {BLOCK_CHANNELS} output channels, got {c1.out_channels} and "
+                         f"{c2.in_channels} -> {c2.out_channels}")
+    if Cin < 8 or Cin > 256 or Cin % 8:
+        raise ValueError(f"fold_block: the block must have a multiple of 8 input channels from 8 to 256, got {Cin}")
+    slope_mid, slope_out = _slope("conv1[2]", act), _slope("leaky", block.leaky)
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    wd = sd = bd = None
+    if block.downsample is not None:
+        cd, nd = _conv_norm("downsample", block.downsample, 2)
+        _conv_is("downsample", cd, 1, 0)
+        if cd.in_channels != Cin or cd.out_channels != BLOCK_CHANNELS:
+            raise ValueError(f"fold_block: 'downsample' must be {Cin} -> {BLOCK_CHANNELS}, got {cd.in_channels} -> {cd.out_channels}")
+        wd, sd, bd = fold_doubles(cd, nd)
+        wd, sd, bd = f32(wd.reshape(BLOCK_CHANNELS, Cin)), f32(sd), f32(bd)
+    elif Cin != BLOCK_CHANNELS:
+        raise ValueError(f"fold_block: a block {Cin} -> {BLOCK_CHANNELS} without 'downsample' has no identity to add")
+    w1, s1, b1 = fold_doubles(c1, n1)
+    w2, s2, b2 = fold_doubles(c2, n2)
+    return BlockSpec(f32(w1), f32(s1), f32(b1), slope_mid, f32(w2), f32(s2), f32(b2), wd, sd, bd, slope_out)
+
+
+def check_block(spec) -> BlockSpec:
+    """``spec`` with contiguous float32 arrays of consistent shapes (``ValueError`` otherwise)."""
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    C = BLOCK_CHANNELS
+    w1, s1, b1, w2, s2, b2 = (f32(v) for v in (spec.w1, spec.s1, spec.b1, spec.w2, spec.s2, spec.b2))
+    Cin = w1.shape[1] if w1.ndim == 4 else -1
+    ok = (w1.ndim == 4 and w1.shape == (C, Cin, 3, 3) and 8 <= Cin <= 256 and Cin % 8 == 0 and w2.shape == (C, C, 3, 3)
+          and all(v.shape == (C,) for v in (s1, b1, s2, b2)))
+    proj = [v is not None for v in (spec.wd, spec.sd, spec.bd)]
+    wd = sd = bd = None
+    if ok and all(proj):
+        wd, sd, bd = f32(spec.wd), f32(spec.sd), f32(spec.bd)
+        ok = wd.shape == (C, Cin) and sd.shape == (C,) and bd.shape == (C,)
+    elif ok:
+        ok = not any(proj) and Cin == C
+    if not ok:
+        shp = lambda v: None if v is None else np.shape(v)
+        raise ValueError(f"BlockSpec: w1 {w1.shape}, s1 {s1.shape}, b1 {b1.shape}, w2 {w2.shape}, s2 {s2.shape}, b2 {b2.shape}, wd {shp(spec.wd)}, "
+                         f"sd {shp(spec.sd)}, bd {shp(spec.bd)}; expected [16, Cin, 3, 3], [16], [16], [16, 16, 3, 3], [16], [16] with Cin a "
+                         "multiple of 8 from 8 to 256, and [16, Cin], [16], [16] or three None (Cin = 16)")
+    for name in ("slope_mid", "slope_out"):
+        if not np.isfinite(float(getattr(spec, name))) or abs(float(getattr(spec, name))) > 1.0:
+            raise ValueError(f"BlockSpec: {name} = {getattr(spec, name)}")
+    return BlockSpec(w1, s1, b1, float(spec.slope_mid), w2, s2, b2, wd, sd, bd, float(spec.slope_out))
+
+
+def check_blocks(stem: StemSpec, blocks) -> Tuple[BlockSpec, ...]:
+    """The blocks behind ``stem`` as a tuple of checked specs: the first takes the stem's channels, each later one is 16 -> 16."""
+    blocks = tuple(check_block(b) for b in blocks)
+    if not blocks:
+        raise ValueError("mmp_blocks: at least one BlockSpec is needed")
+    cin = int(stem.weight.shape[0])
+    for i, b in enumerate(blocks):
+        if b.w1.shape[1] != cin:
+            raise ValueError(f"mmp_blocks: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive "
+                             f"({'the stem has C = ' + str(cin) if i == 0 else 'every block gives 16'})")
+        cin = BLOCK_CHANNELS
+    return blocks
+
+
+def split_network_layer1(net) -> Tuple[StemSpec, Tuple[BlockSpec, BlockSpec, BlockSpec], Callable]:
+    """As ``split_network``, with ``resnet34.layer1`` (three blocks, ``fold_block``) taken off the trunk as well:
+    ``(StemSpec, (BlockSpec, BlockSpec, BlockSpec), trunk)``; the trunk, a callable on ``[M, 16, Hp, Wp]``, is ``layer2 .. layer4``,
+    ``apool``, flatten, ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
+    spec, _ = split_network(net)
+    body = net.resnet34
+    try:
+        l1 = list(body.layer1)
+    except TypeError:
+        l1 = []
+    if len(l1) != 3:
+        raise ValueError("split_network_layer1: 'resnet34.layer1' is not a Sequential of three blocks")
+    blocks = check_blocks(spec, [fold_block(b) for b in l1])
+    layers = [getattr(body, n) for n in ("layer2", "layer3", "layer4", "apool")]
+    fc1, leaky, swarm = net.fc1, net.leaky, net.swarm
+
+    def trunk(x):
+        for layer in layers:
+            x = layer(x)
+        return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
+    return spec, blocks, trunk

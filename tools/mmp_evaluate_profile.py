@@ -16,7 +16,15 @@ max-pool -> ``nmpc_mmp_stem_*``) and the trunk behind it; the parent path (input
 ``network`` and the whole stage of every lock-step; the medians over the alternated repetitions are compared. Beside them: the
 fused kernel alone on one chunk as bytes stored per second against the float4 copy rate, and torch's own first layer alone on
 one chunk of the parent path -- the share of the network's time that the first layer is.
-   usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp] [--fused-stem [REPS]]   (defaults 256 3 f32 4 20; 3)"""
+
+``--fused-layer1``: one step further. The parent path is the fused first layer with the whole trunk in torch (the fused path of
+``--fused-stem``); the new path hands the first residual stage (three blocks at 16 channels, ``mmp_stem.fold_block`` ->
+``nmpc_mmp_block_f32``) to the device stage as well and keeps the trunk from the second stage on. Alternated as above, with HIP
+events around ``input``, ``layer1``, ``network`` and the whole stage. Beside them: torch's own layer1, eager, alone on one chunk
+of the parent path's stem output (the time the three block launches have to beat, and its share of the parent's network time),
+and the block kernels alone on one chunk as fma per second against the fp32 peak and bytes per second against the copy rate.
+   usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp] [--fused-stem [REPS] | --fused-layer1 [REPS]]
+          (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
 import sys
@@ -33,6 +41,7 @@ from dyobav_mpcnwta_warehouse_amd.evaluate import MMP_SIGMA, BatchEvaluator  # n
 from dyobav_mpcnwta_warehouse_amd.snap import WorldTransform  # noqa: E402
 
 COPY_TBS, F1_TBS = 6.29, 5.6
+PEAK_TFMAS = 78.6            # fp32 fma per second of the device (vector and v_mfma_f32_16x16x4_f32 alike), in 1e12
 
 
 def conv(cin, cout, k, stride, pad, act=True):
@@ -194,7 +203,156 @@ def fused_stem_main(out_path, B, steps, dt, n_ped, K, reps):
     print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "fused_over_parent", "torch_stem_share_of_parent_network")}))
 
 
+def _stem_output(ev, n_item):
+    """The fused first layer's output [n_item * N, C, Hp, Wp] for ``n_item`` pedestrians of the evaluator's start state."""
+    st = ev.mmp_stem
+    C, (Hp, Wp) = int(st.weight.shape[0]), nm._capi.mmp_stem_shape(ev.mmp_Hm, ev.mmp_Wm)
+    out = torch.empty(n_item * ev.N, C, Hp, Wp, dtype=torch.float32, device=ev.dev)
+    a = nm._capi.NmpcMmpStemArgs().set_transform(ev.mmp_tf, ev.mmp_rescale, MMP_SIGMA)
+    a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = ev.B, ev.H, n_item, ev.N, ev.mmp_Hm, ev.mmp_Wm
+    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
+    a.hist, a.hcount, a.ref_image, a.out = hist.data_ptr(), hcount.data_ptr(), ev.mmp_ref.data_ptr(), out.data_ptr()
+    a.C, a.slope, a.weight, a.bn_scale, a.bn_shift = C, st.slope, st.weight.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr()
+    ev.h.mmp_stem(ev.dt, a)
+    torch.cuda.synchronize()
+    return out
+
+
+def _timed(call, reps, warm=2):
+    ms = []
+    for i in range(warm + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        y = call()
+        e1.record()
+        torch.cuda.synchronize()
+        del y
+        if i >= warm:
+            ms.append(e0.elapsed_time(e1))
+    return {"ms_median": float(np.median(ms)), "ms_min": float(min(ms))}
+
+
+def torch_layer1_alone(ev, layer1, n_item, reps=5):
+    """ms of torch's own layer1 (three blocks, eager) on the stem output of ``n_item`` pedestrians: one chunk of the parent path."""
+    x = _stem_output(ev, n_item)
+    with torch.no_grad():
+        t = _timed(lambda: layer1(x), reps)
+    return dict(items=n_item, samples=n_item * ev.N, **t)
+
+
+def block_kernel_rate(ev, n_item, reps=10):
+    """The three nmpc_mmp_block_f32 launches alone on the stem output of ``n_item`` pedestrians: ms each and together, useful fma
+    per second (9 Cin 16 + 9 16 16 (+ Cin 16) per pixel) and bytes per second (x read once, out written once)."""
+    x = _stem_output(ev, n_item)
+    rows, (_, Hp, Wp) = x.shape[0], ev.mmp_row
+    bufs = torch.empty(2, rows, 16, Hp, Wp, dtype=torch.float32, device=ev.dev)
+    args, src = [], x
+    for i, b in enumerate(ev.mmp_blocks):
+        a = nm._capi.NmpcMmpBlockArgs()
+        a.M, a.Cin, a.H, a.W = rows, int(b.w1.shape[1]), Hp, Wp
+        for name in ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd"):
+            setattr(a, name, None if getattr(b, name) is None else getattr(b, name).data_ptr())
+        a.slope_mid, a.slope_out, a.x, a.out = b.slope_mid, b.slope_out, src.data_ptr(), bufs[i % 2].data_ptr()
+        src = bufs[i % 2]
+        args.append(a)
+    rec = {"items": n_item, "rows": rows, "blocks": []}
+    fma_all = bytes_all = 0
+    for a in args:
+        fma = rows * Hp * Wp * 16 * (9 * a.Cin + 9 * 16 + (a.Cin if a.wd else 0))
+        nbytes = rows * Hp * Wp * 4 * (a.Cin + 16)
+        t = _timed(lambda: ev.h.mmp_block(a), reps, warm=3)
+        rec["blocks"].append(dict(Cin=a.Cin, projection=bool(a.wd), fma=fma, bytes=nbytes, TFMAps_median=fma / t["ms_median"] * 1e-9,
+                                  share_of_fp32_peak=fma / t["ms_median"] * 1e-9 / PEAK_TFMAS, GBps_median=nbytes / t["ms_median"] * 1e-6,
+                                  share_of_copy_rate=nbytes / t["ms_median"] * 1e-9 / COPY_TBS, **t))
+        fma_all, bytes_all = fma_all + fma, bytes_all + nbytes
+    t = _timed(lambda: [ev.h.mmp_block(a) for a in args], reps, warm=3)
+    rec.update(fma=fma_all, bytes=bytes_all, TFMAps_median=fma_all / t["ms_median"] * 1e-9, share_of_fp32_peak=fma_all / t["ms_median"] * 1e-9 / PEAK_TFMAS,
+               GBps_median=bytes_all / t["ms_median"] * 1e-6, share_of_copy_rate=bytes_all / t["ms_median"] * 1e-9 / COPY_TBS, **t)
+    return rec
+
+
+def fused_layer1_main(out_path, B, steps, dt, n_ped, K, reps):
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import fold_block, fold_stem
+    z = np.load(os.path.join(ROOT, "tests", "golden", "snap_map.npz"))
+    Hm, Wm = (int(v) for v in z["shape"])
+    occupied = np.unpackbits(z["occupied_bits"])[:Hm * Wm].reshape(Hm, Wm).astype(bool)
+    ref = np.where(occupied, 0.0, 255.0).astype(np.float32)
+    tf = WorldTransform(scale=0.1, offsetx_after=-15.0, offsety_after=-15.0, y_reverse=True, y_max_before=float(Hm))
+    sc = nm.scenarios.make_reference_scenarios(B, n_ped=n_ped)
+    sc.pop("scenario_index")
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    # the split, by hand: net[0], net[1] = the first layer; net[2 .. 4] = layer1 (Block: a, b, skip, act); the rest is the trunk
+    spec = fold_stem(net[0][0], net[0][1], net[0][2], net[1])
+    blocks = tuple(fold_block(SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)) for b in list(net)[2:5])
+    layer1, trunk1, trunk2 = torch.nn.Sequential(*list(net)[2:5]), torch.nn.Sequential(*list(net)[2:]), torch.nn.Sequential(*list(net)[5:])
+    paths = {"parent": dict(network=lambda x: trunk1(x) + 150.0, mmp_stem=spec),
+             "fused": dict(network=lambda x: trunk2(x) + 150.0, mmp_stem=spec, mmp_blocks=blocks)}
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage: the parent path (fused first layer + "
+                   "whole trunk in torch) and the fused first layer + fused layer1 + trunk from layer2 on, alternated in one process; random "
+                   "network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS, "fp32_peak_TFMAps": PEAK_TFMAS}, "chunk_pedestrians": {}, "runs": {"parent": [], "fused": []}}
+    for path in paths:                                      # warm-up: code objects, library algorithm choice, allocator
+        ev = evaluator(path)
+        rec["chunk_pedestrians"][path] = ev.mmp_chunk
+        try:
+            if path == "fused":
+                rec["block_kernels"] = block_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped))
+            else:
+                rec["torch_layer1_alone"] = torch_layer1_alone(ev, layer1, min(ev.mmp_chunk, B * n_ped))
+            ev.run(max_steps=1)
+        finally:
+            ev.close()
+        print(json.dumps({k: rec[k] for k in ("block_kernels", "torch_layer1_alone") if k in rec}), flush=True)
+        with open(out_path, "w") as f:
+            json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = {"parent": ("input", "network"), "fused": ("input", "layer1", "network")}
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names[p]},
+                                              behind_input=med(p, lambda s, p=p: sum(s[k] for k in names[p][1:])),
+                                              stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    m = rec["median_per_lock_step_ms"]
+    rec["fused_layer1_over_parent"] = m["fused"]["stage"] / m["parent"]["stage"]
+    # torch's layer1 alone on one chunk, scaled to the pedestrians of a lock-step: its share of the parent's network time; and
+    # the three block launches alone, scaled alike
+    tl, bk = rec["torch_layer1_alone"], rec["block_kernels"]
+    rec["torch_layer1_per_lock_step_ms"] = tl["ms_median"] * (B * n_ped / tl["items"])
+    rec["torch_layer1_share_of_parent_network"] = rec["torch_layer1_per_lock_step_ms"] / m["parent"]["network"]
+    rec["block_kernels_per_lock_step_ms"] = bk["ms_median"] * (B * n_ped / bk["items"])
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "fused_layer1_over_parent", "torch_layer1_per_lock_step_ms",
+                                          "torch_layer1_share_of_parent_network", "block_kernels_per_lock_step_ms")}))
+
+
 def main():
+    if "--fused-layer1" in sys.argv:
+        i = sys.argv.index("--fused-layer1")
+        reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
+        argv = sys.argv[1:i]
+        B, steps, dt, n_ped, K = (argv[1:] + ["256", "3", "f32", "4", "20"][len(argv) - 1:])[:5]
+        return fused_layer1_main(argv[0], int(B), int(steps), dt, int(n_ped), int(K), reps)
     if "--fused-stem" in sys.argv:
         i = sys.argv.index("--fused-stem")
         reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
