@@ -114,6 +114,15 @@ class NmpcDwaArgs(C.Structure):
         return self
 
 
+def set_world_transform(args, transform, rescale: float = 1.0):
+    """The constants of a :class:`.snap.WorldTransform` and ``rescale`` into ``args`` (any struct with these field names), returned."""
+    args.x_reverse, args.y_reverse = int(bool(transform.x_reverse)), int(bool(transform.y_reverse))
+    args.scale, args.offset_x, args.offset_y = float(transform.scale), float(transform.offsetx_after), float(transform.offsety_after)
+    args.x_max, args.y_max = float(transform.x_max_before), float(transform.y_max_before)
+    args.rescale = float(rescale)
+    return args
+
+
 class NmpcSnapArgs(C.Structure):
     """Mirror of ``struct nmpc_snap_args`` (device pointers)."""
     _fields_ = ([(n, C.c_int32) for n in ("n_ped", "n_hyp", "x_reverse", "y_reverse")] +
@@ -130,10 +139,7 @@ class NmpcMmpArgs(C.Structure):
 
     def set_transform(self, transform, rescale: float = 1.0, sigma: float = 20.0):
         """The constants of a :class:`.snap.WorldTransform` (applied backwards: world -> map pixels), ``rescale``, ``sigma``."""
-        self.x_reverse, self.y_reverse = int(bool(transform.x_reverse)), int(bool(transform.y_reverse))
-        self.scale, self.offset_x, self.offset_y = float(transform.scale), float(transform.offsetx_after), float(transform.offsety_after)
-        self.x_max, self.y_max = float(transform.x_max_before), float(transform.y_max_before)
-        self.rescale, self.sigma = float(rescale), float(sigma)
+        set_world_transform(self, transform, rescale).sigma = float(sigma)
         return self
 
 
@@ -469,12 +475,8 @@ class Handle:
             raise ValueError(f"raw must be [B, {self.cfg.N_hor}, {int(n_ped) * int(n_hyp)}, 2], got {tuple(raw.shape)}")
         if tuple(out.shape) != tuple(raw.shape):
             raise ValueError(f"out {tuple(out.shape)} and raw {tuple(raw.shape)} differ in shape")
-        a = NmpcSnapArgs()
+        a = set_world_transform(NmpcSnapArgs(), transform, rescale)
         a.n_ped, a.n_hyp = int(n_ped), int(n_hyp)
-        a.x_reverse, a.y_reverse = int(bool(transform.x_reverse)), int(bool(transform.y_reverse))
-        a.rescale, a.scale = float(rescale), float(transform.scale)
-        a.offset_x, a.offset_y = float(transform.offsetx_after), float(transform.offsety_after)
-        a.x_max, a.y_max = float(transform.x_max_before), float(transform.y_max_before)
         p = _Arg.ptr
         a.n_snapped, a.n_outside = p(n_snapped), p(n_outside)
         fn = getattr(self._lib, "nmpc_snap_hypotheses_" + _suffix(dtype))

@@ -1478,6 +1478,35 @@ int kf_predict(nmpc_handle_s* h, const nmpc_kf_args* g)
     return 0;
 }
 
+// What nmpc_mmp_input and nmpc_mmp_stem share (their args and params structs agree in these names): the refusals both open
+// with, under the name fn, and the item list, history and plane constants -- both kernels must compute the same planes.
+template <typename Args>
+int mmp_check(const char* fn, const Args* g)
+{
+    if (g->B < 1 || g->H < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: B = %d, H = %d", fn, g->B, g->H);
+    if (g->n_item < 0 || g->n_item > (long long)g->B * g->H)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: n_item = %d outside 0 .. B * H = %lld", fn, g->n_item, (long long)g->B * g->H);
+    if (g->n_off < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: n_off = %d < 1", fn, g->n_off);
+    if (g->Hm < 1 || g->Wm < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: map %d x %d", fn, g->Hm, g->Wm);
+    if (!(g->sigma > 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: sigma = %g", fn, g->sigma);
+    if (!(g->scale != 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: scale = %g", fn, g->scale);
+    return 0;
+}
+
+template <typename Params, typename Args>
+void mmp_fill(Params& p, const Args* g)
+{
+    p.n_item = g->n_item, p.n_off = g->n_off, p.Hm = g->Hm, p.Wm = g->Wm;
+    p.xr = g->x_reverse != 0, p.yr = g->y_reverse != 0;
+    p.n_ped = (long long)g->B * g->H;
+    p.items = reinterpret_cast<const long long*>(g->items);
+    p.hist = g->hist, p.hcount = reinterpret_cast<const long long*>(g->hcount);
+    p.scale = g->scale, p.offx = g->offset_x, p.offy = g->offset_y, p.xmax = g->x_max, p.ymax = g->y_max, p.rescale = g->rescale;
+    p.s2 = g->sigma * g->sigma;
+    p.k = 1.0 / (2.0 * 3.141592653589793 * g->sigma * g->sigma); // numpy's order: ((2 pi) sigma_x) sigma_y
+    p.ref = g->ref_image;
+}
+
 template <typename T, int V>
 void launch_mmp(nmpc_handle_s* h, nmpc::MmpParams& p, long long groups)
 {
@@ -1489,13 +1518,7 @@ template <typename T>
 int mmp_input(nmpc_handle_s* h, const nmpc_mmp_args* g)
 {
     if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
-    if (g->B < 1 || g->H < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: B = %d, H = %d", g->B, g->H);
-    if (g->n_item < 0 || g->n_item > (long long)g->B * g->H)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: n_item = %d outside 0 .. B * H = %lld", g->n_item, (long long)g->B * g->H);
-    if (g->n_off < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: n_off = %d < 1", g->n_off);
-    if (g->Hm < 1 || g->Wm < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: map %d x %d", g->Hm, g->Wm);
-    if (!(g->sigma > 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: sigma = %g", g->sigma);
-    if (!(g->scale != 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: scale = %g", g->scale);
+    if (const int rc = mmp_check("nmpc_mmp_input", g)) return rc;
     if (!g->hist || !g->hcount || !g->ref_image || !g->out) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: a required array is NULL");
     if (g->n_item == 0) return 0;
     const long long HW = (long long)g->Hm * g->Wm;
@@ -1511,15 +1534,8 @@ int mmp_input(nmpc_handle_s* h, const nmpc_mmp_args* g)
         return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_input: every array must be a device pointer");
     nmpc::MmpParams p;
     std::memset(&p, 0, sizeof p);
-    p.n_item = g->n_item, p.n_off = g->n_off, p.H = g->H, p.Hm = g->Hm, p.Wm = g->Wm;
-    p.xr = g->x_reverse != 0, p.yr = g->y_reverse != 0;
-    p.n_ped = (long long)g->B * g->H;
-    p.items = reinterpret_cast<const long long*>(g->items);
-    p.hist = g->hist, p.hcount = reinterpret_cast<const long long*>(g->hcount);
-    p.scale = g->scale, p.offx = g->offset_x, p.offy = g->offset_y, p.xmax = g->x_max, p.ymax = g->y_max, p.rescale = g->rescale;
-    p.s2 = g->sigma * g->sigma;
-    p.k = 1.0 / (2.0 * 3.141592653589793 * g->sigma * g->sigma); // numpy's order: ((2 pi) sigma_x) sigma_y
-    p.ref = g->ref_image, p.out = g->out;
+    mmp_fill(p, g);
+    p.H = g->H, p.out = g->out;
     if (V == 4)
         launch_mmp<T, 4>(h, p, HW);
     else if (V == 2)
@@ -1534,13 +1550,7 @@ template <typename T>
 int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g)
 {
     if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
-    if (g->B < 1 || g->H < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: B = %d, H = %d", g->B, g->H);
-    if (g->n_item < 0 || g->n_item > (long long)g->B * g->H)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: n_item = %d outside 0 .. B * H = %lld", g->n_item, (long long)g->B * g->H);
-    if (g->n_off < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: n_off = %d < 1", g->n_off);
-    if (g->Hm < 1 || g->Wm < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: map %d x %d", g->Hm, g->Wm);
-    if (!(g->sigma > 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: sigma = %g", g->sigma);
-    if (!(g->scale != 0.0)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: scale = %g", g->scale);
+    if (const int rc = mmp_check("nmpc_mmp_stem", g)) return rc;
     if (g->C < nmpc::kStemCG || g->C % nmpc::kStemCG) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: C = %d is no positive multiple of 8", g->C);
     if (!std::isfinite(g->slope)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: slope = %g", (double)g->slope);
     if (!g->hist || !g->hcount || !g->ref_image || !g->weight || !g->bn_scale || !g->bn_shift || !g->out)
@@ -1558,16 +1568,9 @@ int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g)
     // (a host pointer here would fault inside the kernel: samples of the argument block are looked up)
     if (h->ptr_mode != NMPC_PTR_DEVICE && (!is_device_ptr(g->hist) || !is_device_ptr(g->ref_image) || !is_device_ptr(g->weight) || !is_device_ptr(g->out)))
         return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: every array must be a device pointer");
-    p.n_item = g->n_item, p.n_off = g->n_off, p.Hm = g->Hm, p.Wm = g->Wm, p.C = g->C;
-    p.xr = g->x_reverse != 0, p.yr = g->y_reverse != 0;
-    p.mono = g->slope >= 0.0f;
-    p.n_ped = (long long)g->B * g->H;
-    p.items = reinterpret_cast<const long long*>(g->items);
-    p.hist = g->hist, p.hcount = reinterpret_cast<const long long*>(g->hcount);
-    p.scale = g->scale, p.offx = g->offset_x, p.offy = g->offset_y, p.xmax = g->x_max, p.ymax = g->y_max, p.rescale = g->rescale;
-    p.s2 = g->sigma * g->sigma;
-    p.k = 1.0 / (2.0 * 3.141592653589793 * g->sigma * g->sigma); // as in mmp_input: the planes must be the same floats
-    p.ref = g->ref_image, p.weight = g->weight, p.bn_scale = g->bn_scale, p.bn_shift = g->bn_shift, p.slope = g->slope, p.out = g->out;
+    mmp_fill(p, g);
+    p.C = g->C, p.mono = g->slope >= 0.0f;
+    p.weight = g->weight, p.bn_scale = g->bn_scale, p.bn_shift = g->bn_shift, p.slope = g->slope, p.out = g->out;
     hipLaunchKernelGGL(nmpc::mmp_stem_kernel<T>, dim3((unsigned)groups), dim3(nmpc::kStemThreads), 0, h->stream, p);
     HIP_TRY(hipGetLastError());
     return 0;

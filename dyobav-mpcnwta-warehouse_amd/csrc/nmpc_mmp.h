@@ -70,6 +70,22 @@ __device__ __forceinline__ double mmp_nearest(double c, int n)
     return !(r > 0.0) ? 0.0 : r > (double)(n - 1) ? (double)(n - 1) : r; // (a NaN centre: pixel 0, the values are NaN anyway)
 }
 
+// distinct entries of a history that has seen cnt positions: channels n - 1 .. 4 all show the newest one
+__device__ __forceinline__ int mmp_distinct(long long cnt) { return cnt < 1 ? 1 : cnt > 5 ? 5 : (int)cnt; }
+
+// The centre of history entry e in network pixels, for both kernels (their planes must be the same floats): ct2real backwards,
+// the reversals, * rescale. The constants come as values: a reference to or a copy of the kernel's params struct keeps its
+// private copy alive past the pass that marks the argument loads (hipcc, gfx950: all marks lost, mmp_stem_kernel + 6 instructions).
+template <typename T>
+__device__ __forceinline__ void mmp_centre(const T* hist, int e, double offx, double offy, double scale, int xr, double xmax, int yr, double ymax,
+                                           double rescale, double& cx, double& cy)
+{
+    cx = ((double)hist[2 * e] - offx) / scale, cy = ((double)hist[2 * e + 1] - offy) / scale;
+    if (xr) cx = xmax - cx;
+    if (yr) cy = ymax - cy;
+    cx *= rescale, cy *= rescale;
+}
+
 template <typename T, int V>
 __global__ __launch_bounds__(kMmpThreads) void mmp_input_kernel(MmpParams p)
 {
@@ -80,8 +96,7 @@ __global__ __launch_bounds__(kMmpThreads) void mmp_input_kernel(MmpParams p)
     if (item >= p.n_item || pix0 >= HW) return; // (HW % V == 0: a vector never straddles the end of a plane)
     const long long ped = p.items ? p.items[item] : item;
     if (ped < 0 || ped >= p.n_ped) return; // (a device-side item list is not validated by the host: stay inside the arrays)
-    long long cnt = p.hcount[ped];
-    const int n = cnt < 1 ? 1 : cnt > 5 ? 5 : (int)cnt; // distinct entries: channels n - 1 .. 4 all show the newest one
+    const int n = mmp_distinct(p.hcount[ped]);
     const T* hist = static_cast<const T*>(p.hist) + ped * 10;
 
     float val[6][V]; // (every index below is a compile-time constant after unrolling: registers)
@@ -92,11 +107,8 @@ __global__ __launch_bounds__(kMmpThreads) void mmp_input_kernel(MmpParams p)
             for (int v = 0; v < V; ++v) val[c][v] = val[c > 0 ? c - 1 : 0][v];
             continue;
         }
-        const int e = 5 - n + c;
-        double cx = ((double)hist[2 * e] - p.offx) / p.scale, cy = ((double)hist[2 * e + 1] - p.offy) / p.scale;
-        if (p.xr) cx = p.xmax - cx;
-        if (p.yr) cy = p.ymax - cy;
-        cx *= p.rescale, cy *= p.rescale;
+        double cx, cy;
+        mmp_centre(hist, 5 - n + c, p.offx, p.offy, p.scale, p.xr, p.xmax, p.yr, p.ymax, p.rescale, cx, cy);
         const double zmax = mmp_gauss(mmp_nearest(cx, p.Wm), mmp_nearest(cy, p.Hm), cx, cy, p.s2, p.k);
 #pragma unroll
         for (int v = 0; v < V; ++v) {

@@ -15,8 +15,8 @@
 // slope >= 0 leaky is non-decreasing, so max(leaky(z_i)) == leaky(max(z_i)) bit for bit and leaky is applied once per
 // pooled output (MmpStemParams::mono, workgroup-uniform); a negative slope takes the element-wise form.
 //
-// The six planes are the float values nmpc_mmp_input_* writes: mmp_gauss / mmp_nearest and the centre arithmetic of
-// nmpc_mmp.h in float64, rounded once to float, per pixel (no separable shortcut). fp32 accumulation in a fixed order (per
+// The six planes are the float values nmpc_mmp_input_* writes: mmp_gauss / mmp_nearest / mmp_centre of nmpc_mmp.h, the same
+// functions, in float64, rounded once to float, per pixel (no separable shortcut). fp32 accumulation in a fixed order (per
 // output: input channel, then ky, then kx, one fma chain per output channel), so an item's bits depend on its own hist /
 // hcount rows, the map and the weights only: not on the item list, the chunk, n_off or the alignment of out.
 //
@@ -103,15 +103,11 @@ __global__ __launch_bounds__(kStemThreads) void mmp_stem_kernel(MmpStemParams p)
     const int oy0 = 2 * py0 - 1, ox0 = 2 * px0 - 1; // conv grid
     const int iy0 = 2 * oy0 - 3, ix0 = 2 * ox0 - 3; // map
 
-    const long long cnt = p.hcount[ped];
-    const int n = cnt < 1 ? 1 : cnt > 5 ? 5 : (int)cnt; // distinct entries: channels n - 1 .. 4 all show the newest one
+    const int n = mmp_distinct(p.hcount[ped]);
     if (tid < 5) {
         const T* hist = static_cast<const T*>(p.hist) + ped * 10;
-        const int e = 5 - n + (tid < n - 1 ? tid : n - 1);
-        double cx = ((double)hist[2 * e] - p.offx) / p.scale, cy = ((double)hist[2 * e + 1] - p.offy) / p.scale;
-        if (p.xr) cx = p.xmax - cx;
-        if (p.yr) cy = p.ymax - cy;
-        cx *= p.rescale, cy *= p.rescale;
+        double cx, cy;
+        mmp_centre(hist, 5 - n + (tid < n - 1 ? tid : n - 1), p.offx, p.offy, p.scale, p.xr, p.xmax, p.yr, p.ymax, p.rescale, cx, cy);
         cen[tid][0] = cx, cen[tid][1] = cy;
         cen[tid][2] = mmp_gauss(mmp_nearest(cx, p.Wm), mmp_nearest(cy, p.Hm), cx, cy, p.s2, p.k);
     }

@@ -28,7 +28,9 @@ scenarios still running:
 1. ``nmpc_loop_pre_*`` (``csrc/nmpc_step.h``): constant-velocity obstacle rows, reference windows, speed reference;
 2. predictor stage, with ``predictor="kfmp"`` only: ``nmpc_kf_predict_*`` (``csrc/nmpc_kf.h``) overwrites the obstacle rows
    (fused path only -- its independent check is tests/kf_reference.py);
-   with ``predictor="mmp"``: ``_mmp_predict`` = ``nmpc_mmp_input_*`` (``csrc/nmpc_mmp.h``) -> the caller's network ->
+   with ``predictor="mmp"``: ``_mmp_predict`` = the device front end (``mmp_front.MmpFrontEnd.run``: ``nmpc_mmp_input_*``,
+   ``csrc/nmpc_mmp.h``, or with ``mmp_stem`` the fused first layer ``nmpc_mmp_stem_*``, then with ``mmp_blocks`` the fused blocks
+   of layer1, ``nmpc_mmp_block_f32``; its structs, weights and buffers are stated there, once) -> the caller's network ->
    ``nmpc_snap_hypotheses_*`` -> ``nmpc_hypotheses_to_ellipses_*`` (row f2), whose ``Ndynobs`` rows per scenario replace
    ``loop_pre``'s as the input of f1 (``MainBase.run_wta_prediction``, main_base.py:175-208, ``MmpInterface``,
    interfaces/mmp_interface.py:20-70; its independent check is tests/mmp_reference.py);
@@ -51,6 +53,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _capi
+from .mmp_front import MmpFrontEnd
 from .trajectory_tracker import TrajectoryTracker
 
 HUMAN_SIZE = 0.2   # main_base.py:75, main_pre.py:18
@@ -174,16 +177,9 @@ class BatchEvaluator:
             raise ValueError("tracker = 'mpc' needs a predictor (cvmp, kfmp or mmp)")
         if predictor not in ("cvmp", "kfmp") and not (tracker == "dwa" and predictor is None) and not (tracker == "mpc" and predictor == "mmp"):
             raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; mmp with tracker = 'mpc'; None with tracker = 'dwa')")
-        if mmp_stem is not None:
-            if predictor != "mmp":
-                raise ValueError("mmp_stem needs predictor = 'mmp'")
-            from .mmp_stem import check_spec
-            mmp_stem = check_spec(mmp_stem)
-        if mmp_blocks is not None:
-            if mmp_stem is None:
-                raise ValueError("mmp_blocks needs mmp_stem (the blocks run on the fused first layer's output)")
-            from .mmp_stem import check_blocks
-            mmp_blocks = check_blocks(mmp_stem, mmp_blocks)
+        if mmp_stem is not None and predictor != "mmp":
+            raise ValueError("mmp_stem needs predictor = 'mmp'")
+        mmp_stem, mmp_blocks = MmpFrontEnd.check_specs(mmp_stem, mmp_blocks, prefix="mmp_")
         if predictor == "mmp":
             if self.n_hyp != 1 or not fused:
                 raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
@@ -344,9 +340,9 @@ class BatchEvaluator:
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
 
     def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem, blocks=None):
-        """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the shape of
-        one row of the network's input -- the stack's [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind
-        fused blocks [16, Hp, Wp] -- and the chunk."""
+        """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the device front
+        end (``mmp_front``: its kernels, weights and buffers) and from it the shape of one row of the network's input -- the stack's
+        [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind fused blocks [16, Hp, Wp] -- and the chunk."""
         img = np.ascontiguousarray(ref_image, dtype=np.float32)
         if img.ndim != 2:
             raise ValueError(f"ref_image must be [Hm, Wm], got {img.shape}")
@@ -357,20 +353,10 @@ class BatchEvaluator:
         self.mmp_ref = self.torch.as_tensor(img, device=self.dev)
         # mmp_interface.py:60 snaps on 255 - ref_image; its grey levels decide the edges (Handle.set_map)
         self.h.set_map(255.0 - img.astype(np.float64))
-        self.mmp_stem, self.mmp_row = None, (7, self.mmp_Hm, self.mmp_Wm)
-        if stem is not None:
-            self.mmp_stem = stem._replace(weight=self.torch.as_tensor(stem.weight, device=self.dev), scale=self.torch.as_tensor(stem.scale, device=self.dev),
-                                          shift=self.torch.as_tensor(stem.shift, device=self.dev))
-            self.mmp_row = (int(stem.weight.shape[0]),) + _capi.mmp_stem_shape(self.mmp_Hm, self.mmp_Wm)
-        self.mmp_fill_row, self.mmp_blocks = self.mmp_row, None    # a row of what nmpc_mmp_input_* / nmpc_mmp_stem_* write
-        per_ped = self.N * int(np.prod(self.mmp_row)) * 4
-        if blocks is not None:
-            dev = lambda v: None if v is None else self.torch.as_tensor(v, device=self.dev)
-            self.mmp_blocks = tuple(b._replace(**{n: dev(getattr(b, n)) for n in ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")}) for b in blocks)
-            C, Hp, Wp = self.mmp_row
-            self.mmp_row = (16, Hp, Wp)
-            per_ped = self.N * (C + 32) * Hp * Wp * 4           # the stem's output and the two buffers the blocks alternate between
-        self.mmp_chunk = int(mmp_chunk) if mmp_chunk is not None else max(1, MMP_INPUT_BYTES // per_ped)
+        fe = self.mmp_front = MmpFrontEnd(self.h, self.dt, self.dev, self.mmp_Hm, self.mmp_Wm, self.N, transform, self.mmp_rescale, MMP_SIGMA,
+                                          self.mmp_ref, stem, blocks)
+        self.mmp_row, self.mmp_stem, self.mmp_blocks = fe.row, fe.stem, fe.blocks      # (the specs with their arrays on the device)
+        self.mmp_chunk = int(mmp_chunk) if mmp_chunk is not None else max(1, MMP_INPUT_BYTES // fe.bytes_per_item)
 
     def _init_dwa(self, robot_paths):
         """The node paths the deviation term measures against, padded with their last node; no solver state."""
@@ -569,26 +555,11 @@ class BatchEvaluator:
         return kf
 
     def _mmp_args(self, r, max_steps):
-        """``NmpcMmpArgs`` (``NmpcMmpStemArgs`` with a fused first layer) of a run and the stage's buffers: the network's input tensor of one chunk, the hypotheses (pedestrian
-        major as the network returns them, then per scenario as snap and f2 take them), f2's obstacle rows -- which f1 reads
-        instead of ``loop_pre``'s -- and the per-step counts."""
+        """The stage's buffers of a run: the hypotheses (pedestrian major as the network returns them, then per scenario as snap
+        and f2 take them), f2's obstacle rows -- which f1 reads instead of ``loop_pre``'s -- and the per-step counts. Returns the
+        front end with its own buffers (the network's input tensor of one chunk) in place."""
         torch, B, N, H, K, z = self.torch, self.B, self.N, self.H, self.mmp_hyp, self._full
-        chunk = min(self.mmp_chunk, B * H)
-        r.mmp_in = torch.empty(chunk, N, *self.mmp_fill_row, dtype=torch.float32, device=self.dev)
-        r.mmp_net_in, r.mmp_block_args = r.mmp_in, ()
-        if self.mmp_blocks is not None:
-            r.mmp_pp = torch.empty(2, chunk, N, *self.mmp_row, dtype=torch.float32, device=self.dev)
-            args, src = [], r.mmp_in
-            for i, b in enumerate(self.mmp_blocks):
-                a = _capi.NmpcMmpBlockArgs()
-                a.Cin, a.H, a.W = int(b.w1.shape[1]), self.mmp_row[1], self.mmp_row[2]
-                for name in ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd"):
-                    setattr(a, name, None if getattr(b, name) is None else getattr(b, name).data_ptr())
-                a.slope_mid, a.slope_out = b.slope_mid, b.slope_out
-                a.x, a.out = src.data_ptr(), r.mmp_pp[i % 2].data_ptr()
-                src = r.mmp_pp[i % 2]
-                args.append(a)
-            r.mmp_net_in, r.mmp_block_args = src, tuple(args)
+        self.mmp_front.allocate(min(self.mmp_chunk, B * H))
         r.mmp_raw_p, r.mmp_hyp = z(B * H, N, K, 2), z(B, N, H * K, 2)
         r.mmp_dyn = z(B, self.cfg.Ndynobs, N + 1, 6)
         r.mmp_n_obs, r.mmp_n_out = z(B, dtype=torch.int32, fill=0), z(B, dtype=torch.int32, fill=0)
@@ -597,20 +568,13 @@ class BatchEvaluator:
         r.mmp_all = torch.arange(B * H, dtype=torch.long, device=self.dev)
         r.mmp_events = []
         r.dyn_in = r.mmp_dyn
-        st = self.mmp_stem
-        m = (_capi.NmpcMmpArgs() if st is None else _capi.NmpcMmpStemArgs()).set_transform(self.mmp_tf, self.mmp_rescale, MMP_SIGMA)
-        if st is not None:
-            m.C, m.slope = self.mmp_fill_row[0], st.slope
-            m.weight, m.bn_scale, m.bn_shift = st.weight.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr()
-        r.mmp_fill = self.h.mmp_input if st is None else self.h.mmp_stem     # what writes the network's input
-        m.B, m.H, m.n_off, m.Hm, m.Wm = B, H, N, self.mmp_Hm, self.mmp_Wm
-        m.hist, m.hcount, m.ref_image, m.out = self.hist.data_ptr(), self.hcount.data_ptr(), self.mmp_ref.data_ptr(), r.mmp_in.data_ptr()
-        return m
+        return self.mmp_front
 
-    def _mmp_predict(self, r, m, kt, idx, nA):
+    def _mmp_predict(self, r, fe, kt, idx, nA):
         """The multi-hypothesis predictor for the ``nA`` running scenarios (``idx``, None = all), MainBase.run_wta_prediction
-        (main_base.py:175-208): per chunk of pedestrians input stack (or the fused first layer's output, then the fused blocks of layer1) -> network; then, per scenario with its pedestrians'
-        segments concatenated in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]``."""
+        (main_base.py:175-208): per chunk of pedestrians the device front end (``MmpFrontEnd.run``: input stack, or the fused first
+        layer's output, then the fused blocks of layer1) -> network; then, per scenario with its pedestrians' segments concatenated
+        in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]``."""
         torch, N, H, K = self.torch, self.N, self.H, self.mmp_hyp
 
         def part(name, call):
@@ -622,21 +586,13 @@ class BatchEvaluator:
             e1.record()
             r.mmp_events.append((kt, name, e0, e1))
             return out
-
-        def layer1(rows):
-            for a in r.mmp_block_args:
-                a.M = rows
-                self.h.mmp_block(a)
         items = r.mmp_all if idx is None else (idx[:, None] * H + r.mmp_all[None, :H]).reshape(-1).contiguous()
         n_ped = nA * H
         for c0 in range(0, n_ped, self.mmp_chunk):
             n = min(self.mmp_chunk, n_ped - c0)
-            m.n_item, m.items = n, items[c0:].data_ptr()
-            part("input", lambda: r.mmp_fill(self.dt, m))
-            if r.mmp_block_args:
-                part("layer1", lambda: layer1(n * N))
+            x = fe.run(self.hist.data_ptr(), self.hcount.data_ptr(), self.B, H, items[c0:].data_ptr(), n, part)
             with torch.no_grad():
-                out = part("network", lambda: self.network(r.mmp_net_in[:n].view(n * N, *self.mmp_row)))
+                out = part("network", lambda: self.network(x))
             if out.numel() != n * N * K * 2:
                 raise ValueError(f"the network returned {tuple(out.shape)} for {n * N} inputs; expected {K} hypotheses (x, y) each")
             r.mmp_raw_p[c0:c0 + n] = out.reshape(n, N, K, 2)

@@ -1,0 +1,112 @@
+"""``MmpFrontEnd``: what runs on the device in front of the caller's network in the multi-hypothesis predictor (``mmp``) stage,
+stated once for ``evaluate.BatchEvaluator``, ``mmp_interface.MmpInterface`` and ``tools/mmp_evaluate_profile.py``: the *fill* --
+the input stack ``[7, Hm, Wm]`` per pedestrian and time offset (``nmpc_mmp_input_*``, csrc/nmpc_mmp.h) or, with ``stem``, the
+network's first layer fused with it, ``[C, Hp, Wp]`` (``nmpc_mmp_stem_*``, csrc/nmpc_mmp_stem.h) -- then, with ``blocks``, the
+residual blocks of ``layer1``, one launch each between two 16-channel buffers (``nmpc_mmp_block_f32``, csrc/nmpc_mmp_block.h).
+The object owns the folded weights on the device, the argument structs and the buffers they point to; the structs of these
+kernels are built nowhere else in the package."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _capi
+from .mmp_stem import BLOCK_CHANNELS, check_blocks, check_spec
+
+_BLOCK_ARRAYS = ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
+
+
+class MmpFrontEnd:
+    def __init__(self, handle: _capi.Handle, dtype, device, Hm: int, Wm: int, n_off: int, transform, rescale: float, sigma: float,
+                 ref_image, stem=None, blocks=None):
+        """``dtype``: the element type of ``hist``; ``ref_image``: the float32 label image ``[Hm, Wm]`` on ``device``; ``transform``: the
+        :class:`.snap.WorldTransform` between map pixels and the world of ``hist``; ``stem`` / ``blocks``: :class:`.mmp_stem.StemSpec` /
+        ``BlockSpec`` s. ``fill_row``: a row of what the fill writes; ``row``: a row of what the network sees; ``bytes_per_item``: the
+        buffers one pedestrian takes -- with blocks the stem's output and the two buffers the blocks alternate between."""
+        import torch
+        stem, blocks = self.check_specs(stem, blocks)
+        self.h, self.dt, self.dev, self.n_off = handle, np.dtype(dtype), device, int(n_off)
+        dev = lambda v: None if v is None else torch.as_tensor(v, device=device)
+        self.stem = None if stem is None else stem._replace(weight=dev(stem.weight), scale=dev(stem.scale), shift=dev(stem.shift))
+        self.blocks = None if blocks is None else tuple(b._replace(**{n: dev(getattr(b, n)) for n in _BLOCK_ARRAYS}) for b in blocks)
+        self.ref = ref_image
+        if stem is None:
+            self.fill_row = (7, int(Hm), int(Wm))
+            a, self._fill = _capi.NmpcMmpArgs(), handle.mmp_input
+        else:
+            self.fill_row = (int(stem.weight.shape[0]),) + _capi.mmp_stem_shape(Hm, Wm)
+            a, self._fill = _capi.NmpcMmpStemArgs(), handle.mmp_stem
+            a.C, a.slope = self.fill_row[0], stem.slope
+            a.weight, a.bn_scale, a.bn_shift = self.stem.weight.data_ptr(), self.stem.scale.data_ptr(), self.stem.shift.data_ptr()
+        a.set_transform(transform, rescale, sigma)
+        a.n_off, a.Hm, a.Wm, a.ref_image = self.n_off, int(Hm), int(Wm), ref_image.data_ptr()
+        self.row, self.bytes_per_item = self.fill_row, self.n_off * int(np.prod(self.fill_row)) * 4
+        if blocks is not None:
+            C, Hp, Wp = self.fill_row
+            self.row, self.bytes_per_item = (BLOCK_CHANNELS, Hp, Wp), self.n_off * (C + 2 * BLOCK_CHANNELS) * Hp * Wp * 4
+        self._fill_args, self._block_args, self.chunk = a, (), 0
+
+    @staticmethod
+    def check_specs(stem, blocks, prefix: str = ""):
+        """``(stem, blocks)`` checked, either may be ``None``; ``prefix``: what the caller's argument names carry in front."""
+        if stem is not None:
+            stem = check_spec(stem)
+        if blocks is not None:
+            if stem is None:
+                raise ValueError(f"{prefix}blocks needs {prefix}stem (the blocks run on the fused first layer's output)")
+            blocks = check_blocks(stem, blocks)
+        return stem, blocks
+
+    def allocate(self, chunk: int):
+        """The buffers for up to ``chunk`` pedestrians per ``run``, and the kernels' structs wired to them (kept while they suffice)."""
+        import torch
+        if chunk <= self.chunk:
+            return
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.dev)
+        self._fill_buf = self._out = new(chunk, self.n_off, *self.fill_row)
+        self._fill_args.out = self._fill_buf.data_ptr()
+        args = []
+        if self.blocks is not None:
+            self._pp = new(2, chunk, self.n_off, *self.row)
+            for i, b in enumerate(self.blocks):
+                a = _capi.NmpcMmpBlockArgs()
+                a.Cin, a.H, a.W = int(b.w1.shape[1]), self.row[1], self.row[2]
+                for name in _BLOCK_ARRAYS:
+                    setattr(a, name, None if getattr(b, name) is None else getattr(b, name).data_ptr())
+                a.slope_mid, a.slope_out = b.slope_mid, b.slope_out
+                a.x, a.out = self._out.data_ptr(), self._pp[i % 2].data_ptr()
+                self._out = self._pp[i % 2]
+                args.append(a)
+        self._block_args, self.chunk = tuple(args), chunk
+
+    def fill(self, hist: int, hcount: int, B: int, H: int, items, n: int):
+        """The fill alone for ``n`` pedestrians: ``hist`` ``[B, H, 5, 2]`` / ``hcount`` ``[B, H]`` device pointers, ``items`` a device
+        pointer to their int64 indices or ``None`` = 0 .. n - 1. Returns its output ``[n * n_off, *fill_row]``."""
+        if not 0 <= n <= self.chunk:
+            raise ValueError(f"{n} items; allocate() was called for {self.chunk}")
+        a = self._fill_args
+        a.B, a.H, a.n_item, a.hist, a.hcount, a.items = B, H, n, hist, hcount, items
+        self._fill(self.dt, a)
+        return self._fill_buf.view(-1, *self.fill_row)[:n * self.n_off]
+
+    def run_block(self, i: int, rows: int):
+        """Block ``i`` alone on the first ``rows`` rows of its input buffer (what ``fill`` or block ``i - 1`` left there)."""
+        if not 0 <= rows <= self.chunk * self.n_off:
+            raise ValueError(f"{rows} rows; allocate() was called for {self.chunk * self.n_off}")
+        self._block_args[i].M = rows
+        self.h.mmp_block(self._block_args[i])
+
+    def run_blocks(self, rows: int):
+        """All blocks, one after the other, on the first ``rows`` rows of the fill's output. Returns the last one's ``[rows, *row]``."""
+        for i in range(len(self._block_args)):
+            self.run_block(i, rows)
+        return self._out.view(-1, *self.row)[:rows]
+
+    def run(self, hist: int, hcount: int, B: int, H: int, items, n: int, part=None):
+        """One chunk: fill, then the blocks on its ``n * n_off`` rows (arguments as in ``fill``). ``part(name, call)``, if given,
+        makes the launches in place of a plain ``call()`` and returns its result: ``"input"``, then with blocks ``"layer1"``.
+        Returns the view ``[n * n_off, *row]`` the network is to be called on; the next ``run`` overwrites it."""
+        part = part or (lambda name, call: call())
+        x = part("input", lambda: self.fill(hist, hcount, B, H, items, n))
+        if self._block_args:
+            x = part("layer1", lambda: self.run_blocks(n * self.n_off))
+        return x

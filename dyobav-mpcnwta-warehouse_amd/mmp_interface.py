@@ -11,7 +11,9 @@ What the reference does on the host around the network runs on the device: the i
 the copy per time offset) through ``nmpc_mmp_input_f64`` with one item (with ``stem=``, a :class:`.mmp_stem.StemSpec`, the
 stack and the network's first layer in one kernel, ``nmpc_mmp_stem_f64``, and ``network`` = the trunk; with ``blocks=`` as well, the
 first residual stage behind it, one ``nmpc_mmp_block_f32`` per block), ``get_closest_edge_point(...) / rescale`` through
-``nmpc_snap_hypotheses_f64`` with the identity transform. There is no host implementation of either in this package.
+``nmpc_snap_hypotheses_f64`` with the identity transform. There is no host implementation of either in this package. The kernels
+in front of the network are driven through :class:`.mmp_front.MmpFrontEnd`, the same object the evaluator uses, with
+``B = H = 1``, one item and float64 positions.
 
 For whole batches of scenarios use ``evaluate.BatchEvaluator(predictor="mmp")``, which keeps the pedestrians' histories on
 the device and goes on to the obstacle rows; this class uploads its arguments at every call.
@@ -23,6 +25,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from . import _capi
+from .mmp_front import MmpFrontEnd
 from .snap import WorldTransform
 
 SIGMA = 20.0        # pre_load.py:128
@@ -39,18 +42,10 @@ class MmpInterface:
             raise TypeError(f"network must be a callable, got {type(network)}")
         self._prt_name = "MMPInterface"
         self.network = network
-        self.stem, self._stem_dev = None, None
-        if stem is not None:
-            from .mmp_stem import check_spec
-            self.stem = check_spec(stem)
-        self.blocks, self._blocks_dev = None, None
-        if blocks is not None:
-            if self.stem is None:
-                raise ValueError("blocks needs stem (the blocks run on the fused first layer's output)")
-            from .mmp_stem import check_blocks
-            self.blocks = check_blocks(self.stem, blocks)
+        self.stem, self.blocks = MmpFrontEnd.check_specs(stem, blocks)
         self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)
         self._map_of = {}         # pred_offset -> the ref_image its map was set from
+        self._fronts = {}         # (pred_offset, Hm, Wm, rescale) -> device front end: the weights are uploaded once, the buffers reused
 
     def _handle(self, pred_offset: int, ref_image, img: np.ndarray) -> _capi.Handle:
         h = self._handles.get(pred_offset)
@@ -90,34 +85,15 @@ class MmpInterface:
         hist[OBSV_LEN - len(last):] = last
         d_hist = torch.from_numpy(hist.reshape(1, 1, OBSV_LEN, 2)).cuda()
         d_count = torch.full((1, 1), traj.shape[0], dtype=torch.long, device="cuda")
-        d_ref = torch.from_numpy(img).cuda()
         ident = WorldTransform()
-        if self.stem is None:
-            stack = torch.empty(N, 7, Hm, Wm, dtype=torch.float32, device="cuda")
-            a, fill = _capi.NmpcMmpArgs().set_transform(ident, rescale, SIGMA), h.mmp_input
-        else:
-            if self._stem_dev is None:
-                self._stem_dev = tuple(torch.from_numpy(v).cuda() for v in self.stem[:3])
-            w, sc, sh = self._stem_dev
-            stack = torch.empty(N, w.shape[0], *_capi.mmp_stem_shape(Hm, Wm), dtype=torch.float32, device="cuda")
-            a, fill = _capi.NmpcMmpStemArgs().set_transform(ident, rescale, SIGMA), h.mmp_stem
-            a.C, a.slope, a.weight, a.bn_scale, a.bn_shift = w.shape[0], self.stem.slope, w.data_ptr(), sc.data_ptr(), sh.data_ptr()
-        a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = 1, 1, 1, N, Hm, Wm
-        a.hist, a.hcount, a.ref_image, a.out = d_hist.data_ptr(), d_count.data_ptr(), d_ref.data_ptr(), stack.data_ptr()
-        fill(np.float64, a)
-        if self.blocks is not None:
-            if self._blocks_dev is None:
-                self._blocks_dev = [{n: torch.from_numpy(getattr(b, n)).cuda() for n in ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
-                                     if getattr(b, n) is not None} for b in self.blocks]
-            for b, dev in zip(self.blocks, self._blocks_dev):
-                out = torch.empty(N, 16, *stack.shape[2:], dtype=torch.float32, device="cuda")
-                g = _capi.NmpcMmpBlockArgs()
-                g.M, g.Cin, g.H, g.W = N, int(b.w1.shape[1]), int(stack.shape[2]), int(stack.shape[3])
-                for name, t in dev.items():
-                    setattr(g, name, t.data_ptr())
-                g.slope_mid, g.slope_out, g.x, g.out = b.slope_mid, b.slope_out, stack.data_ptr(), out.data_ptr()
-                h.mmp_block(g)
-                stack = out
+        key = (N, Hm, Wm, float(rescale))
+        if key not in self._fronts:
+            d_ref = torch.empty(Hm, Wm, dtype=torch.float32, device=d_hist.device)
+            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, self.stem, self.blocks)
+            self._fronts[key].allocate(1)
+        fe = self._fronts[key]
+        fe.ref.copy_(torch.from_numpy(img))
+        stack = fe.run(d_hist.data_ptr(), d_count.data_ptr(), 1, 1, None, 1)
         with torch.no_grad():
             outs = [self.network(stack[i:i + bs]) for i in range(0, N, bs)]
         raw = torch.cat([o.reshape(o.shape[0], -1, 2) for o in outs], dim=0).to(torch.float64)
@@ -131,4 +107,4 @@ class MmpInterface:
     def close(self):
         for h in self._handles.values():
             h.close()
-        self._handles, self._map_of = {}, {}
+        self._handles, self._map_of, self._fronts = {}, {}, {}

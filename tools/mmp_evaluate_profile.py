@@ -37,7 +37,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 
 import dyobav_mpcnwta_warehouse_amd as nm  # noqa: E402
-from dyobav_mpcnwta_warehouse_amd.evaluate import MMP_SIGMA, BatchEvaluator  # noqa: E402
+from dyobav_mpcnwta_warehouse_amd.evaluate import BatchEvaluator  # noqa: E402
 from dyobav_mpcnwta_warehouse_amd.snap import WorldTransform  # noqa: E402
 
 COPY_TBS, F1_TBS = 6.29, 5.6
@@ -72,76 +72,8 @@ def make_network(K, fc_input=3200):
     return torch.nn.Sequential(*layers)
 
 
-def input_kernel_rate(ev, n_item, reps=20):
-    """ms and GB/s of nmpc_mmp_input_* alone on ``n_item`` pedestrians of the evaluator's start state."""
-    out = torch.empty(n_item, ev.N, 7, ev.mmp_Hm, ev.mmp_Wm, dtype=torch.float32, device=ev.dev)
-    a = nm._capi.NmpcMmpArgs().set_transform(ev.mmp_tf, ev.mmp_rescale, MMP_SIGMA)
-    a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = ev.B, ev.H, n_item, ev.N, ev.mmp_Hm, ev.mmp_Wm
-    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
-    a.hist, a.hcount, a.ref_image, a.out = hist.data_ptr(), hcount.data_ptr(), ev.mmp_ref.data_ptr(), out.data_ptr()
-    ms = []
-    for i in range(5 + reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ev.h.mmp_input(ev.dt, a)
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= 5:
-            ms.append(e0.elapsed_time(e1))
-    nbytes = out.numel() * 4
-    med = float(np.median(ms))
-    return {"items": n_item, "bytes_written": nbytes, "ms_median": med, "ms_min": float(min(ms)), "write_GBps_median": nbytes / med * 1e-6,
-            "write_GBps_best": nbytes / min(ms) * 1e-6, "share_of_copy_rate": nbytes / med * 1e-9 / COPY_TBS, "share_of_f1_rate": nbytes / med * 1e-9 / F1_TBS}
-
-
-def stem_kernel_rate(ev, n_item, reps=20):
-    """ms and GB/s stored of nmpc_mmp_stem_* alone on ``n_item`` pedestrians of the evaluator's start state."""
-    st = ev.mmp_stem
-    out = torch.empty(n_item, ev.N, *ev.mmp_row, dtype=torch.float32, device=ev.dev)
-    a = nm._capi.NmpcMmpStemArgs().set_transform(ev.mmp_tf, ev.mmp_rescale, MMP_SIGMA)
-    a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = ev.B, ev.H, n_item, ev.N, ev.mmp_Hm, ev.mmp_Wm
-    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
-    a.hist, a.hcount, a.ref_image, a.out = hist.data_ptr(), hcount.data_ptr(), ev.mmp_ref.data_ptr(), out.data_ptr()
-    a.C, a.slope, a.weight, a.bn_scale, a.bn_shift = ev.mmp_row[0], st.slope, st.weight.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr()
-    ms = []
-    for i in range(5 + reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ev.h.mmp_stem(ev.dt, a)
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= 5:
-            ms.append(e0.elapsed_time(e1))
-    nbytes, med = out.numel() * 4, float(np.median(ms))
-    fma = n_item * ev.mmp_row[0] * ((ev.mmp_Hm - 1) // 2 + 1) * ((ev.mmp_Wm - 1) // 2 + 1) * 343        # base and E, once per pedestrian
-    return {"items": n_item, "bytes_stored": nbytes, "ms_median": med, "ms_min": float(min(ms)), "store_GBps_median": nbytes / med * 1e-6,
-            "share_of_copy_rate": nbytes / med * 1e-9 / COPY_TBS, "conv_fma": fma, "conv_TFMAps_median": fma / med * 1e-9}
-
-
-def torch_stem_alone(ev, stem_modules, n_item, reps=5):
-    """ms of torch's own first layer (the four modules, eager) on the input stack of ``n_item`` pedestrians: one chunk of the parent path."""
-    x = torch.empty(n_item * ev.N, 7, ev.mmp_Hm, ev.mmp_Wm, dtype=torch.float32, device=ev.dev)
-    a = nm._capi.NmpcMmpArgs().set_transform(ev.mmp_tf, ev.mmp_rescale, MMP_SIGMA)
-    a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = ev.B, ev.H, n_item, ev.N, ev.mmp_Hm, ev.mmp_Wm
-    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
-    a.hist, a.hcount, a.ref_image, a.out = hist.data_ptr(), hcount.data_ptr(), ev.mmp_ref.data_ptr(), x.data_ptr()
-    ev.h.mmp_input(ev.dt, a)
-    ms = []
-    with torch.no_grad():
-        for i in range(2 + reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            y = stem_modules(x)
-            e1.record()
-            torch.cuda.synchronize()
-            del y
-            if i >= 2:
-                ms.append(e0.elapsed_time(e1))
-    return {"items": n_item, "samples": n_item * ev.N, "ms_median": float(np.median(ms)), "ms_min": float(min(ms))}
-
-
-def fused_stem_main(out_path, B, steps, dt, n_ped, K, reps):
-    from dyobav_mpcnwta_warehouse_amd.mmp_stem import fold_stem
+def _world(B, n_ped):
+    """The warehouse label image with its size and transform, and the reference scenarios: (Hm, Wm, ref, tf, sc)."""
     z = np.load(os.path.join(ROOT, "tests", "golden", "snap_map.npz"))
     Hm, Wm = (int(v) for v in z["shape"])
     occupied = np.unpackbits(z["occupied_bits"])[:Hm * Wm].reshape(Hm, Wm).astype(bool)
@@ -149,6 +81,61 @@ def fused_stem_main(out_path, B, steps, dt, n_ped, K, reps):
     tf = WorldTransform(scale=0.1, offsetx_after=-15.0, offsety_after=-15.0, y_reverse=True, y_max_before=float(Hm))
     sc = nm.scenarios.make_reference_scenarios(B, n_ped=n_ped)
     sc.pop("scenario_index")
+    return Hm, Wm, ref, tf, sc
+
+
+def _timed(call, reps, warm=2):
+    ms = []
+    for i in range(warm + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        y = call()
+        e1.record()
+        torch.cuda.synchronize()
+        del y
+        if i >= warm:
+            ms.append(e0.elapsed_time(e1))
+    return {"ms_median": float(np.median(ms)), "ms_min": float(min(ms))}
+
+
+def _fill(ev, n_item):
+    """A call that launches the fill kernel of the evaluator's front end alone (nmpc_mmp_input_* or nmpc_mmp_stem_*) on the first
+    ``n_item`` pedestrians of its start state and returns the kernel's output [n_item * N, *fill_row]."""
+    fe = ev.mmp_front
+    fe.allocate(n_item)
+    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
+    return lambda: fe.fill(hist.data_ptr(), hcount.data_ptr(), ev.B, ev.H, None, n_item)
+
+
+def input_kernel_rate(ev, n_item, reps=20):
+    """ms and GB/s of nmpc_mmp_input_* alone on ``n_item`` pedestrians of the evaluator's start state."""
+    t = _timed(_fill(ev, n_item), reps, warm=5)
+    nbytes, med = n_item * ev.N * int(np.prod(ev.mmp_front.fill_row)) * 4, t["ms_median"]
+    return {"items": n_item, "bytes_written": nbytes, **t, "write_GBps_median": nbytes / med * 1e-6,
+            "write_GBps_best": nbytes / t["ms_min"] * 1e-6, "share_of_copy_rate": nbytes / med * 1e-9 / COPY_TBS, "share_of_f1_rate": nbytes / med * 1e-9 / F1_TBS}
+
+
+def stem_kernel_rate(ev, n_item, reps=20):
+    """ms and GB/s stored of nmpc_mmp_stem_* alone on ``n_item`` pedestrians of the evaluator's start state."""
+    t = _timed(_fill(ev, n_item), reps, warm=5)
+    C = ev.mmp_front.fill_row[0]
+    nbytes, med = n_item * ev.N * int(np.prod(ev.mmp_front.fill_row)) * 4, t["ms_median"]
+    fma = n_item * C * ((ev.mmp_Hm - 1) // 2 + 1) * ((ev.mmp_Wm - 1) // 2 + 1) * 343        # base and E, once per pedestrian
+    return {"items": n_item, "bytes_stored": nbytes, **t, "store_GBps_median": nbytes / med * 1e-6,
+            "share_of_copy_rate": nbytes / med * 1e-9 / COPY_TBS, "conv_fma": fma, "conv_TFMAps_median": fma / med * 1e-9}
+
+
+def torch_stem_alone(ev, stem_modules, n_item, reps=5):
+    """ms of torch's own first layer (the four modules, eager) on the input stack of ``n_item`` pedestrians: one chunk of the parent path."""
+    x = _fill(ev, n_item)()
+    with torch.no_grad():
+        t = _timed(lambda: stem_modules(x), reps)
+    return dict(items=n_item, samples=n_item * ev.N, **t)
+
+
+def fused_stem_main(out_path, B, steps, dt, n_ped, K, reps):
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import fold_stem
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
     torch.manual_seed(0)
     net = make_network(K).cuda().eval()
     # the split, by hand: net[0] = Sequential(Conv2d, BatchNorm2d, LeakyReLU), net[1] = MaxPool2d, the rest is the trunk
@@ -203,38 +190,9 @@ def fused_stem_main(out_path, B, steps, dt, n_ped, K, reps):
     print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "fused_over_parent", "torch_stem_share_of_parent_network")}))
 
 
-def _stem_output(ev, n_item):
-    """The fused first layer's output [n_item * N, C, Hp, Wp] for ``n_item`` pedestrians of the evaluator's start state."""
-    st = ev.mmp_stem
-    C, (Hp, Wp) = int(st.weight.shape[0]), nm._capi.mmp_stem_shape(ev.mmp_Hm, ev.mmp_Wm)
-    out = torch.empty(n_item * ev.N, C, Hp, Wp, dtype=torch.float32, device=ev.dev)
-    a = nm._capi.NmpcMmpStemArgs().set_transform(ev.mmp_tf, ev.mmp_rescale, MMP_SIGMA)
-    a.B, a.H, a.n_item, a.n_off, a.Hm, a.Wm = ev.B, ev.H, n_item, ev.N, ev.mmp_Hm, ev.mmp_Wm
-    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
-    a.hist, a.hcount, a.ref_image, a.out = hist.data_ptr(), hcount.data_ptr(), ev.mmp_ref.data_ptr(), out.data_ptr()
-    a.C, a.slope, a.weight, a.bn_scale, a.bn_shift = C, st.slope, st.weight.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr()
-    ev.h.mmp_stem(ev.dt, a)
-    torch.cuda.synchronize()
-    return out
-
-
-def _timed(call, reps, warm=2):
-    ms = []
-    for i in range(warm + reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        y = call()
-        e1.record()
-        torch.cuda.synchronize()
-        del y
-        if i >= warm:
-            ms.append(e0.elapsed_time(e1))
-    return {"ms_median": float(np.median(ms)), "ms_min": float(min(ms))}
-
-
 def torch_layer1_alone(ev, layer1, n_item, reps=5):
     """ms of torch's own layer1 (three blocks, eager) on the stem output of ``n_item`` pedestrians: one chunk of the parent path."""
-    x = _stem_output(ev, n_item)
+    x = _fill(ev, n_item)()
     with torch.no_grad():
         t = _timed(lambda: layer1(x), reps)
     return dict(items=n_item, samples=n_item * ev.N, **t)
@@ -243,29 +201,20 @@ def torch_layer1_alone(ev, layer1, n_item, reps=5):
 def block_kernel_rate(ev, n_item, reps=10):
     """The three nmpc_mmp_block_f32 launches alone on the stem output of ``n_item`` pedestrians: ms each and together, useful fma
     per second (9 Cin 16 + 9 16 16 (+ Cin 16) per pixel) and bytes per second (x read once, out written once)."""
-    x = _stem_output(ev, n_item)
-    rows, (_, Hp, Wp) = x.shape[0], ev.mmp_row
-    bufs = torch.empty(2, rows, 16, Hp, Wp, dtype=torch.float32, device=ev.dev)
-    args, src = [], x
-    for i, b in enumerate(ev.mmp_blocks):
-        a = nm._capi.NmpcMmpBlockArgs()
-        a.M, a.Cin, a.H, a.W = rows, int(b.w1.shape[1]), Hp, Wp
-        for name in ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd"):
-            setattr(a, name, None if getattr(b, name) is None else getattr(b, name).data_ptr())
-        a.slope_mid, a.slope_out, a.x, a.out = b.slope_mid, b.slope_out, src.data_ptr(), bufs[i % 2].data_ptr()
-        src = bufs[i % 2]
-        args.append(a)
+    fe = ev.mmp_front
+    rows, (_, Hp, Wp) = _fill(ev, n_item)().shape[0], fe.row
     rec = {"items": n_item, "rows": rows, "blocks": []}
     fma_all = bytes_all = 0
-    for a in args:
-        fma = rows * Hp * Wp * 16 * (9 * a.Cin + 9 * 16 + (a.Cin if a.wd else 0))
-        nbytes = rows * Hp * Wp * 4 * (a.Cin + 16)
-        t = _timed(lambda: ev.h.mmp_block(a), reps, warm=3)
-        rec["blocks"].append(dict(Cin=a.Cin, projection=bool(a.wd), fma=fma, bytes=nbytes, TFMAps_median=fma / t["ms_median"] * 1e-9,
+    for i, b in enumerate(fe.blocks):
+        Cin, proj = int(b.w1.shape[1]), b.wd is not None
+        fma = rows * Hp * Wp * 16 * (9 * Cin + 9 * 16 + (Cin if proj else 0))
+        nbytes = rows * Hp * Wp * 4 * (Cin + 16)
+        t = _timed(lambda: fe.run_block(i, rows), reps, warm=3)
+        rec["blocks"].append(dict(Cin=Cin, projection=proj, fma=fma, bytes=nbytes, TFMAps_median=fma / t["ms_median"] * 1e-9,
                                   share_of_fp32_peak=fma / t["ms_median"] * 1e-9 / PEAK_TFMAS, GBps_median=nbytes / t["ms_median"] * 1e-6,
                                   share_of_copy_rate=nbytes / t["ms_median"] * 1e-9 / COPY_TBS, **t))
         fma_all, bytes_all = fma_all + fma, bytes_all + nbytes
-    t = _timed(lambda: [ev.h.mmp_block(a) for a in args], reps, warm=3)
+    t = _timed(lambda: fe.run_blocks(rows), reps, warm=3)
     rec.update(fma=fma_all, bytes=bytes_all, TFMAps_median=fma_all / t["ms_median"] * 1e-9, share_of_fp32_peak=fma_all / t["ms_median"] * 1e-9 / PEAK_TFMAS,
                GBps_median=bytes_all / t["ms_median"] * 1e-6, share_of_copy_rate=bytes_all / t["ms_median"] * 1e-9 / COPY_TBS, **t)
     return rec
@@ -275,13 +224,7 @@ def fused_layer1_main(out_path, B, steps, dt, n_ped, K, reps):
     from types import SimpleNamespace
 
     from dyobav_mpcnwta_warehouse_amd.mmp_stem import fold_block, fold_stem
-    z = np.load(os.path.join(ROOT, "tests", "golden", "snap_map.npz"))
-    Hm, Wm = (int(v) for v in z["shape"])
-    occupied = np.unpackbits(z["occupied_bits"])[:Hm * Wm].reshape(Hm, Wm).astype(bool)
-    ref = np.where(occupied, 0.0, 255.0).astype(np.float32)
-    tf = WorldTransform(scale=0.1, offsetx_after=-15.0, offsety_after=-15.0, y_reverse=True, y_max_before=float(Hm))
-    sc = nm.scenarios.make_reference_scenarios(B, n_ped=n_ped)
-    sc.pop("scenario_index")
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
     torch.manual_seed(0)
     net = make_network(K).cuda().eval()
     # the split, by hand: net[0], net[1] = the first layer; net[2 .. 4] = layer1 (Block: a, b, skip, act); the rest is the trunk
@@ -347,28 +290,17 @@ def fused_layer1_main(out_path, B, steps, dt, n_ped, K, reps):
 
 
 def main():
-    if "--fused-layer1" in sys.argv:
-        i = sys.argv.index("--fused-layer1")
-        reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
-        argv = sys.argv[1:i]
-        B, steps, dt, n_ped, K = (argv[1:] + ["256", "3", "f32", "4", "20"][len(argv) - 1:])[:5]
-        return fused_layer1_main(argv[0], int(B), int(steps), dt, int(n_ped), int(K), reps)
-    if "--fused-stem" in sys.argv:
-        i = sys.argv.index("--fused-stem")
-        reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
-        argv = sys.argv[1:i]
-        B, steps, dt, n_ped, K = (argv[1:] + ["256", "3", "f32", "4", "20"][len(argv) - 1:])[:5]
-        return fused_stem_main(argv[0], int(B), int(steps), dt, int(n_ped), int(K), reps)
+    for flag, run in (("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+        if flag in sys.argv:
+            i = sys.argv.index(flag)
+            reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
+            argv = sys.argv[1:i]
+            B, steps, dt, n_ped, K = (argv[1:] + ["256", "3", "f32", "4", "20"][len(argv) - 1:])[:5]
+            return run(argv[0], int(B), int(steps), dt, int(n_ped), int(K), reps)
     out_path = sys.argv[1]
     B, steps, dt, n_ped, K = (sys.argv[2:] + ["256", "3", "f32", "4", "20"][len(sys.argv) - 2:])[:5]
     B, steps, n_ped, K = int(B), int(steps), int(n_ped), int(K)
-    z = np.load(os.path.join(ROOT, "tests", "golden", "snap_map.npz"))
-    Hm, Wm = (int(v) for v in z["shape"])
-    occupied = np.unpackbits(z["occupied_bits"])[:Hm * Wm].reshape(Hm, Wm).astype(bool)
-    ref = np.where(occupied, 0.0, 255.0).astype(np.float32)
-    tf = WorldTransform(scale=0.1, offsetx_after=-15.0, offsety_after=-15.0, y_reverse=True, y_max_before=float(Hm))
-    sc = nm.scenarios.make_reference_scenarios(B, n_ped=n_ped)
-    sc.pop("scenario_index")
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
     torch.manual_seed(0)
     net = make_network(K).cuda().eval()
     ev = BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp",
