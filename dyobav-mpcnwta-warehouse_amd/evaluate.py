@@ -30,7 +30,7 @@ scenarios still running:
    (fused path only -- its independent check is tests/kf_reference.py);
    with ``predictor="mmp"``: ``_mmp_predict`` = the device front end (``mmp_front.MmpFrontEnd.run``: ``nmpc_mmp_input_*``,
    ``csrc/nmpc_mmp.h``, or with ``mmp_stem`` the fused first layer ``nmpc_mmp_stem_*``, then with ``mmp_blocks`` the fused blocks
-   of layer1, ``nmpc_mmp_block_f32``; its structs, weights and buffers are stated there, once) -> the caller's network ->
+   of layer1, ``nmpc_mmp_block_f32``, then with ``mmp_blocks2`` those of layer2, ``nmpc_mmp_block2_f32``; its structs, weights and buffers are stated there, once) -> the caller's network ->
    ``nmpc_snap_hypotheses_*`` -> ``nmpc_hypotheses_to_ellipses_*`` (row f2), whose ``Ndynobs`` rows per scenario replace
    ``loop_pre``'s as the input of f1 (``MainBase.run_wta_prediction``, main_base.py:175-208, ``MmpInterface``,
    interfaces/mmp_interface.py:20-70; its independent check is tests/mmp_reference.py);
@@ -127,7 +127,7 @@ class BatchEvaluator:
                  compact: Optional[bool] = None, fused: bool = True, n_hyp: int = 1, hyp_fan: float = 0.15,
                  hyp_radius_growth: float = 0.05, predictor: Optional[str] = "cvmp", kf_Q=None, kf_R=None, kf_P0=None,
                  tracker: str = "mpc", dwa_config=None, network=None, mmp_hyp: int = 20, mmp_chunk: Optional[int] = None,
-                 ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None, mmp_blocks=None):
+                 ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None, mmp_blocks=None, mmp_blocks2=None):
         """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
@@ -161,6 +161,13 @@ class BatchEvaluator:
         both buffers at or below 1 GiB (22 pedestrians for the warehouse map at N_hor = 20 and C = 64). Measured on an MI355X at
         B = 256, 4 pedestrians, K = 20 (``profiles/mmp_layer1_evaluate.json``): the stage takes 524 ms per
         lock-step against 685 ms with ``mmp_stem`` alone; the three block launches 88 ms where torch's own layer1 took 232.
+        ``mmp_blocks2`` (needs ``mmp_blocks``): the :class:`.mmp_stem.Block2Spec` s of the second residual stage
+        (``mmp_stem.split_network_layer2``: four for the reference's ``resnet34.layer2``, the first 16 -> 32 at stride 2), one fused
+        kernel per block (``nmpc_mmp_block2_f32``, csrc/nmpc_mmp_block2.h) between two 32-channel buffers that lie inside the stem's
+        output where they fit (the chunk stays at 22 pedestrians); ``network`` is then the trunk from ``layer3`` on, called on
+        ``[M, 32, H2, W2]`` (37 x 42 for the warehouse map). Measured in the same setting (``profiles/mmp_layer2_evaluate.json``,
+        DESIGN.md section 7): the stage takes 467 ms per lock-step against 521 ms without; the four launches 72 ms where torch's own
+        layer2 took 129.
 
         ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the
@@ -179,7 +186,7 @@ class BatchEvaluator:
             raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; mmp with tracker = 'mpc'; None with tracker = 'dwa')")
         if mmp_stem is not None and predictor != "mmp":
             raise ValueError("mmp_stem needs predictor = 'mmp'")
-        mmp_stem, mmp_blocks = MmpFrontEnd.check_specs(mmp_stem, mmp_blocks, prefix="mmp_")
+        mmp_stem, mmp_blocks, mmp_blocks2 = MmpFrontEnd.check_specs(mmp_stem, mmp_blocks, prefix="mmp_", blocks2=mmp_blocks2)
         if predictor == "mmp":
             if self.n_hyp != 1 or not fused:
                 raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
@@ -204,7 +211,7 @@ class BatchEvaluator:
         self.kf_Q, self.kf_R, self.kf_P0 = eye(kf_Q, 4), eye(kf_R, 2), eye(kf_P0, 4)
         # time_predictor / time_tracker: HIP events around every nmpc_kf_predict / nmpc_dwa_step call; run() leaves the
         # times (ms) in predictor_ms / tracker_ms
-        # (predictor "mmp": time_predictor_parts adds events around its four parts -- five with mmp_blocks: "layer1" --;
+        # (predictor "mmp": time_predictor_parts adds events around its four parts -- five with mmp_blocks: "layer1", six with mmp_blocks2: "layer2" --;
         # predictor_part_ms: name -> ms per step)
         self.time_predictor, self.time_tracker, self.time_predictor_parts = False, False, False
         self.predictor_ms, self.tracker_ms, self.predictor_part_ms = [], [], {}
@@ -278,7 +285,7 @@ class BatchEvaluator:
         else:
             self._init_dwa(robot_paths)
         if predictor == "mmp":
-            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_stem, mmp_blocks)
+            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_stem, mmp_blocks, mmp_blocks2)
 
     def _tensor(self, x):
         return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
@@ -339,10 +346,10 @@ class BatchEvaluator:
         self._info, self._evals = self._full(B, 8), self._full(B)
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
 
-    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem, blocks=None):
+    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem, blocks=None, blocks2=None):
         """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the device front
         end (``mmp_front``: its kernels, weights and buffers) and from it the shape of one row of the network's input -- the stack's
-        [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind fused blocks [16, Hp, Wp] -- and the chunk."""
+        [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind fused blocks [16, Hp, Wp], or behind those of layer2 [32, H2, W2] -- and the chunk."""
         img = np.ascontiguousarray(ref_image, dtype=np.float32)
         if img.ndim != 2:
             raise ValueError(f"ref_image must be [Hm, Wm], got {img.shape}")
@@ -354,8 +361,8 @@ class BatchEvaluator:
         # mmp_interface.py:60 snaps on 255 - ref_image; its grey levels decide the edges (Handle.set_map)
         self.h.set_map(255.0 - img.astype(np.float64))
         fe = self.mmp_front = MmpFrontEnd(self.h, self.dt, self.dev, self.mmp_Hm, self.mmp_Wm, self.N, transform, self.mmp_rescale, MMP_SIGMA,
-                                          self.mmp_ref, stem, blocks)
-        self.mmp_row, self.mmp_stem, self.mmp_blocks = fe.row, fe.stem, fe.blocks      # (the specs with their arrays on the device)
+                                          self.mmp_ref, stem, blocks, blocks2)
+        self.mmp_row, self.mmp_stem, self.mmp_blocks, self.mmp_blocks2 = fe.row, fe.stem, fe.blocks, fe.blocks2  # (the specs with their arrays on the device)
         self.mmp_chunk = int(mmp_chunk) if mmp_chunk is not None else max(1, MMP_INPUT_BYTES // fe.bytes_per_item)
 
     def _init_dwa(self, robot_paths):
@@ -573,7 +580,7 @@ class BatchEvaluator:
     def _mmp_predict(self, r, fe, kt, idx, nA):
         """The multi-hypothesis predictor for the ``nA`` running scenarios (``idx``, None = all), MainBase.run_wta_prediction
         (main_base.py:175-208): per chunk of pedestrians the device front end (``MmpFrontEnd.run``: input stack, or the fused first
-        layer's output, then the fused blocks of layer1) -> network; then, per scenario with its pedestrians' segments concatenated
+        layer's output, then the fused blocks of layer1 and of layer2) -> network; then, per scenario with its pedestrians' segments concatenated
         in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]``."""
         torch, N, H, K = self.torch, self.N, self.H, self.mmp_hyp
 

@@ -17,7 +17,14 @@ resolution (net_module/net.py:45-61), can go the same way (``nmpc_mmp_block_f32`
 slopes -- 0.1 inside the block (``compact_conv_layer``), 0.01 behind the addition (a default ``nn.LeakyReLU``).
 ``fold_block`` folds one block, ``split_network_layer1(net)`` returns the stem, the three blocks and the trunk from
 ``layer2`` on, for ``BatchEvaluator(..., mmp_stem=spec, mmp_blocks=blocks, network=trunk)`` and
-``MmpInterface(trunk, stem=spec, blocks=blocks)``."""
+``MmpInterface(trunk, stem=spec, blocks=blocks)``.
+
+The second residual stage, ``resnet34.layer2`` = four ``BasicBlock`` s at 32 channels, the first ``16 -> 32`` at stride 2 with a
+1 x 1, stride-2 projection (37 x 42 from 74 x 83 on the warehouse map), goes the same way through a second kernel family
+(``nmpc_mmp_block2_f32``, csrc/nmpc_mmp_block2.h): ``Block2Spec`` = ``BlockSpec`` 's fields plus ``stride`` (1 or 2, of the first
+convolution and the projection), ``fold_block2`` folds one block, ``split_network_layer2(net)`` returns the stem, the three blocks
+of layer1, the four of layer2 and the trunk from ``layer3`` on, for ``BatchEvaluator(..., mmp_stem=spec, mmp_blocks=blocks,
+mmp_blocks2=blocks2, network=trunk)`` and ``MmpInterface(trunk, stem=spec, blocks=blocks, blocks2=blocks2)``."""
 from __future__ import annotations
 
 from typing import Callable, NamedTuple, Optional, Tuple
@@ -47,6 +54,24 @@ class BlockSpec(NamedTuple):
 
 
 BLOCK_CHANNELS = 16                 # output channels of the fused block (csrc/nmpc_mmp_block.h)
+
+
+class Block2Spec(NamedTuple):
+    w1: np.ndarray                  # [32, Cin, 3, 3] float32
+    s1: np.ndarray                  # [32] float32
+    b1: np.ndarray                  # [32] float32
+    slope_mid: float
+    w2: np.ndarray                  # [32, 32, 3, 3] float32
+    s2: np.ndarray                  # [32]
+    b2: np.ndarray                  # [32]
+    wd: Optional[np.ndarray]        # [32, Cin] float32, or None: the identity (Cin == 32 and stride == 1)
+    sd: Optional[np.ndarray]        # [32] or None
+    bd: Optional[np.ndarray]        # [32] or None
+    slope_out: float
+    stride: int                     # 1 or 2: of the first convolution and of the projection
+
+
+BLOCK2_CHANNELS = 32                # output channels of the fused strided block (csrc/nmpc_mmp_block2.h)
 
 
 def _pair(v):
@@ -263,3 +288,131 @@ def split_network_layer1(net) -> Tuple[StemSpec, Tuple[BlockSpec, BlockSpec, Blo
             x = layer(x)
         return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
     return spec, blocks, trunk
+
+
+def block2_plane(H: int, W: int, stride: int) -> Tuple[int, int]:
+    """The output plane of a block of stride ``stride`` on an ``H x W`` input plane (3 x 3, padding 1 / 1 x 1, padding 0)."""
+    return (int(H) - 1) // int(stride) + 1, (int(W) - 1) // int(stride) + 1
+
+
+def _conv2_is(name, conv, kernel, padding, stride):
+    if (_pair(conv.kernel_size) != (kernel, kernel) or _pair(conv.padding) != (padding, padding) or conv.groups != 1
+            or _pair(conv.dilation) != (1, 1) or conv.padding_mode != "zeros"):
+        raise ValueError(f"fold_block2: '{name}' must have kernel {kernel}, padding {padding}, groups 1, dilation 1 and zero padding; got {conv}")
+    if _pair(conv.stride) != (stride, stride):
+        raise ValueError(f"fold_block2: '{name}' must have stride {stride}, got stride {_pair(conv.stride)}")
+
+
+def fold_block2(block) -> Block2Spec:
+    """A module shaped like the reference's ``BasicBlock`` -- ``conv1 = Sequential(Conv2d 3 x 3 at stride 1 or 2, BatchNorm2d,
+    LeakyReLU)``, ``conv2 = Sequential(Conv2d 3 x 3, BatchNorm2d)``, ``downsample = None | Sequential(Conv2d 1 x 1 at conv1's stride,
+    BatchNorm2d)``, ``leaky = LeakyReLU`` -- with 32 output channels -> :class:`Block2Spec`, folded in float64 (``fold_doubles``) and
+    rounded once; ``ValueError`` for anything the kernel does not compute."""
+    for name in ("conv1", "conv2", "downsample", "leaky"):
+        if not hasattr(block, name):
+            raise ValueError(f"fold_block2: the module has no {name!r}")
+    try:
+        c1, n1, act = _conv_norm("conv1", block.conv1, 3)
+        c2, n2 = _conv_norm("conv2", block.conv2, 2)
+        parts_d = None if block.downsample is None else _conv_norm("downsample", block.downsample, 2)
+    except ValueError as e:
+        raise ValueError(str(e).replace("fold_block:", "fold_block2:")) from None
+    stride = _pair(c1.stride)[0]
+    if _pair(c1.stride) not in ((1, 1), (2, 2)):
+        raise ValueError(f"fold_block2: 'conv1' must have stride 1 or 2, got stride {_pair(c1.stride)}")
+    _conv2_is("conv1", c1, 3, 1, stride)
+    _conv2_is("conv2", c2, 3, 1, 1)
+    C, Cin = BLOCK2_CHANNELS, int(c1.in_channels)
+    if c1.out_channels != C or c2.in_channels != C or c2.out_channels != C:
+        raise ValueError(f"fold_block2: the block must have {C} output channels, got {c1.out_channels} and {c2.in_channels} -> {c2.out_channels}")
+    if Cin < 8 or Cin > 256 or Cin % 8:
+        raise ValueError(f"fold_block2: the block must have a multiple of 8 input channels from 8 to 256, got {Cin}")
+    try:
+        slope_mid, slope_out = _slope("conv1[2]", act), _slope("leaky", block.leaky)
+    except ValueError as e:
+        raise ValueError(str(e).replace("fold_block:", "fold_block2:")) from None
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    wd = sd = bd = None
+    if parts_d is not None:
+        cd, nd = parts_d
+        if _pair(cd.stride) != _pair(c1.stride):
+            raise ValueError(f"fold_block2: mismatched strides: 'conv1' has stride {_pair(c1.stride)}, 'downsample' {_pair(cd.stride)}")
+        _conv2_is("downsample", cd, 1, 0, stride)
+        if cd.in_channels != Cin or cd.out_channels != C:
+            raise ValueError(f"fold_block2: 'downsample' must be {Cin} -> {C}, got {cd.in_channels} -> {cd.out_channels}")
+        wd, sd, bd = fold_doubles(cd, nd)
+        wd, sd, bd = f32(wd.reshape(C, Cin)), f32(sd), f32(bd)
+    elif stride != 1:
+        raise ValueError("fold_block2: a block at stride 2 without 'downsample' has no identity of the output's shape to add")
+    elif Cin != C:
+        raise ValueError(f"fold_block2: a block {Cin} -> {C} without 'downsample' has no identity to add")
+    w1, s1, b1 = fold_doubles(c1, n1)
+    w2, s2, b2 = fold_doubles(c2, n2)
+    return Block2Spec(f32(w1), f32(s1), f32(b1), slope_mid, f32(w2), f32(s2), f32(b2), wd, sd, bd, slope_out, int(stride))
+
+
+def check_block2(spec) -> Block2Spec:
+    """``spec`` with contiguous float32 arrays of consistent shapes and a stride of 1 or 2 (``ValueError`` otherwise)."""
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    C = BLOCK2_CHANNELS
+    w1, s1, b1, w2, s2, b2 = (f32(v) for v in (spec.w1, spec.s1, spec.b1, spec.w2, spec.s2, spec.b2))
+    Cin = w1.shape[1] if w1.ndim == 4 else -1
+    stride = spec.stride
+    ok = (w1.ndim == 4 and w1.shape == (C, Cin, 3, 3) and 8 <= Cin <= 256 and Cin % 8 == 0 and w2.shape == (C, C, 3, 3)
+          and all(v.shape == (C,) for v in (s1, b1, s2, b2)) and isinstance(stride, (int, np.integer)) and int(stride) in (1, 2))
+    proj = [v is not None for v in (spec.wd, spec.sd, spec.bd)]
+    wd = sd = bd = None
+    if ok and all(proj):
+        wd, sd, bd = f32(spec.wd), f32(spec.sd), f32(spec.bd)
+        ok = wd.shape == (C, Cin) and sd.shape == (C,) and bd.shape == (C,)
+    elif ok:
+        ok = not any(proj) and Cin == C and int(stride) == 1
+    if not ok:
+        shp = lambda v: None if v is None else np.shape(v)
+        raise ValueError(f"Block2Spec: w1 {w1.shape}, s1 {s1.shape}, b1 {b1.shape}, w2 {w2.shape}, s2 {s2.shape}, b2 {b2.shape}, wd {shp(spec.wd)}, "
+                         f"sd {shp(spec.sd)}, bd {shp(spec.bd)}, stride {stride!r}; expected [32, Cin, 3, 3], [32], [32], [32, 32, 3, 3], [32], [32] "
+                         "with Cin a multiple of 8 from 8 to 256, stride 1 or 2, and [32, Cin], [32], [32] or three None (Cin = 32, stride 1)")
+    for name in ("slope_mid", "slope_out"):
+        if not np.isfinite(float(getattr(spec, name))) or abs(float(getattr(spec, name))) > 1.0:
+            raise ValueError(f"Block2Spec: {name} = {getattr(spec, name)}")
+    return Block2Spec(w1, s1, b1, float(spec.slope_mid), w2, s2, b2, wd, sd, bd, float(spec.slope_out), int(stride))
+
+
+def check_blocks2(blocks, blocks2) -> Tuple[Block2Spec, ...]:
+    """The layer-2 blocks behind the (checked) layer-1 ``blocks`` as a tuple of checked specs: the first takes the 16 channels layer1
+    gives, each later one is 32 -> 32."""
+    if not blocks:
+        raise ValueError("mmp_blocks2: the blocks of layer1 are needed in front")
+    blocks2 = tuple(check_block2(b) for b in blocks2)
+    if not blocks2:
+        raise ValueError("mmp_blocks2: at least one Block2Spec is needed")
+    cin = BLOCK_CHANNELS
+    for i, b in enumerate(blocks2):
+        if b.w1.shape[1] != cin:
+            raise ValueError(f"mmp_blocks2: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive "
+                             f"({'layer1 gives 16' if i == 0 else 'every block of layer2 gives 32'})")
+        cin = BLOCK2_CHANNELS
+    return blocks2
+
+
+def split_network_layer2(net) -> Tuple[StemSpec, Tuple[BlockSpec, ...], Tuple[Block2Spec, ...], Callable]:
+    """As ``split_network_layer1``, with ``resnet34.layer2`` (four blocks, ``fold_block2``) taken off the trunk as well:
+    ``(StemSpec, blocks, blocks2, trunk)``; the trunk, a callable on ``[M, 32, H2, W2]``, is ``layer3``, ``layer4``, ``apool``,
+    flatten, ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
+    spec, blocks, _ = split_network_layer1(net)
+    body = net.resnet34
+    try:
+        l2 = list(body.layer2)
+    except TypeError:
+        l2 = []
+    if len(l2) != 4:
+        raise ValueError("split_network_layer2: 'resnet34.layer2' is not a Sequential of four blocks")
+    blocks2 = check_blocks2(blocks, [fold_block2(b) for b in l2])
+    layers = [getattr(body, n) for n in ("layer3", "layer4", "apool")]
+    fc1, leaky, swarm = net.fc1, net.leaky, net.swarm
+
+    def trunk(x):
+        for layer in layers:
+            x = layer(x)
+        return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
+    return spec, blocks, blocks2, trunk

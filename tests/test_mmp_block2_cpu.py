@@ -1,0 +1,337 @@
+"""CPU tests of the fused strided residual block's host side: ``mmp_stem.fold_block2`` / ``split_network_layer2`` against
+block-shaped torch modules run in float64 (written anew here, and the reference's own ``BasicBlock`` / ``make_layer(..., stride=2)``
+where its tree is present), every refusal, the layout of the argument struct against the C compiler, the resources of the shipped
+kernels, and the controls of the float64 restatement's bound (tests/mmp_block2_reference.py) before any device run."""
+import ctypes
+import importlib
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+import dyobav_mpcnwta_warehouse_amd as nm
+import mmp_block2_reference as b2
+import mmp_block_reference as br
+import mmp_stem_reference as sr
+from dyobav_mpcnwta_warehouse_amd import _capi
+from dyobav_mpcnwta_warehouse_amd.mmp_front import MmpFrontEnd
+from dyobav_mpcnwta_warehouse_amd.mmp_stem import (BLOCK2_CHANNELS, Block2Spec, check_block2, check_blocks, check_blocks2, fold_block2,
+                                                   fold_doubles, split_network_layer2)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the reference's ``src`` directory: NMPC_REFERENCE_SRC, or a checkout named ``reference`` next to this repository
+REFERENCE_SRC = os.environ.get("NMPC_REFERENCE_SRC") or os.path.join(os.path.dirname(ROOT), "reference", "src")
+
+
+def _randomise(module, seed):
+    """Non-trivial weights, affine parameters of both signs and running statistics for every norm of ``module``."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for m in module.modules():
+            if isinstance(m, torch.nn.Conv2d):
+                m.weight.copy_(torch.randn(m.weight.shape, generator=g) / (m.weight[0].numel() ** 0.5))
+                if m.bias is not None:
+                    m.bias.copy_(torch.randn(m.bias.shape, generator=g))
+            elif isinstance(m, torch.nn.BatchNorm2d):
+                C = m.num_features
+                m.weight.copy_(torch.randn(C, generator=g))
+                m.bias.copy_(torch.randn(C, generator=g))
+                m.running_mean.copy_(torch.randn(C, generator=g) * 3)
+                m.running_var.copy_(torch.rand(C, generator=g) * 4 + 0.25)
+    return module
+
+
+class _Block(torch.nn.Module):
+    """A module with the attribute names of the reference's BasicBlock, written anew; ``Cout`` = 16 gives a block of layer1."""
+    def __init__(self, Cin, stride, projection, slope_mid=0.1, slope_out=0.01, bias=False, Cout=32):
+        super().__init__()
+        nn = torch.nn
+        self.conv1 = nn.Sequential(nn.Conv2d(Cin, Cout, 3, stride, 1, bias=bias), nn.BatchNorm2d(Cout), nn.LeakyReLU(slope_mid))
+        self.conv2 = nn.Sequential(nn.Conv2d(Cout, Cout, 3, 1, 1, bias=bias), nn.BatchNorm2d(Cout))
+        self.downsample = nn.Sequential(nn.Conv2d(Cin, Cout, 1, stride, bias=bias), nn.BatchNorm2d(Cout)) if projection else None
+        self.leaky = nn.LeakyReLU(slope_out)
+
+    def forward(self, x):
+        out = self.conv2(self.conv1(x))
+        return self.leaky(out + (x if self.downsample is None else self.downsample(x)))
+
+
+def _module_in_double(module, x):
+    module.double()
+    try:
+        with torch.no_grad():
+            return module(torch.from_numpy(x).double()).numpy()
+    finally:
+        module.float()
+
+
+def _exact_spec(blk):
+    """The fold in doubles, before the one rounding to float."""
+    d1, d2 = fold_doubles(blk.conv1[0], blk.conv1[1]), fold_doubles(blk.conv2[0], blk.conv2[1])
+    dd = fold_doubles(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else (None, None, None)
+    return Block2Spec(*d1, 0.1, *d2, None if dd[0] is None else dd[0].reshape(32, -1), dd[1], dd[2], 0.01, int(blk.conv1[0].stride[0]))
+
+
+# ---- 1. the fold: the restatement on the folded block equals the module in float64 ---------------------------------------------------
+@pytest.mark.parametrize("Cin,stride,projection,bias", [(32, 1, False, False), (16, 2, True, False), (64, 1, True, False), (8, 2, True, True),
+                                                        (32, 2, True, False)], ids=["identity", "strided", "projection", "strided-bias", "strided-32"])
+def test_fold_equals_the_module_in_float64(Cin, stride, projection, bias):
+    blk = _randomise(_Block(Cin, stride, projection, bias=bias), seed=Cin + stride).eval()
+    spec = fold_block2(blk)
+    assert (spec.wd is not None) == projection and spec.slope_mid == pytest.approx(0.1) and spec.slope_out == pytest.approx(0.01)
+    assert spec.stride == stride and type(spec.stride) is int
+    assert (spec.s1 < 0).any() and (spec.s1 > 0).any() and np.abs(spec.b1).min() > 0
+    assert all(v.dtype == np.float32 and v.flags.c_contiguous for v in spec if isinstance(v, np.ndarray))
+    assert spec.w1.shape == (32, Cin, 3, 3) and spec.w2.shape == (32, 32, 3, 3) and (not projection or spec.wd.shape == (32, Cin))
+    for H, W in ((9, 11), (10, 12)):                        # both parities
+        x = br.random_x(2, Cin, H, W, seed=3)
+        want = _module_in_double(blk, x)
+        exact = _exact_spec(blk)
+        got, bound = b2.block(x, exact)
+        print(f"Cin = {Cin}, stride {stride}, {H} x {W}: largest |restatement - module| = {np.abs(got - want).max():.2e}")
+        assert got.shape == want.shape == (2, 32) + b2.out_plane(H, W, stride) and np.abs(got - want).max() <= 1e-12
+    # and fold_block2 is the same numbers, rounded once
+    for a, b in zip(spec, exact):
+        if isinstance(a, np.ndarray):
+            assert np.array_equal(a, np.asarray(b).astype(np.float32))
+    assert check_block2(spec).w1.flags.c_contiguous and check_block2(spec).stride == stride
+
+
+# ---- 2. the reference's own layer2, where its tree is present ---------------------------------------------------------------------------
+def test_fold_equals_the_reference_layer2():
+    if not os.path.isdir(os.path.join(REFERENCE_SRC, "pkg_motion_prediction", "net_module")):
+        pytest.skip("the reference tree is not present")
+    sys.path.insert(0, REFERENCE_SRC)
+    try:
+        net = importlib.import_module("pkg_motion_prediction.net_module.net")
+    except ImportError as e:                                # (a dependency of the reference that is not installed)
+        pytest.skip(f"the reference's net module does not import: {e}")
+    finally:
+        sys.path.remove(REFERENCE_SRC)
+    layer2 = _randomise(net.make_layer(net.BasicBlock, 16, 32, 4, stride=2), seed=7).eval()
+    x = br.random_x(2, 16, 10, 13, seed=4)
+    want = _module_in_double(layer2, x)
+    y = x.astype(np.float64)
+    specs = [fold_block2(blk) for blk in layer2]
+    for blk, spec in zip(layer2, specs):
+        assert spec.slope_mid == pytest.approx(0.1) and spec.slope_out == pytest.approx(0.01)
+        y, _ = b2.block(y, _exact_spec(blk))
+    assert [s.stride for s in specs] == [2, 1, 1, 1] and specs[0].wd is not None and all(s.wd is None for s in specs[1:])
+    assert len(check_blocks2((br.doubling_block(),), specs)) == 4
+    print(f"largest |four folded blocks - the reference's layer2| = {np.abs(y - want).max():.2e}")
+    assert y.shape == want.shape == (2, 32, 5, 7) and np.abs(y - want).max() <= 1e-12
+
+
+# ---- 3. what fold_block2, check_block2 and check_blocks2 refuse -----------------------------------------------------------------------------
+def test_fold_refuses_what_the_kernel_does_not_compute():
+    nn = torch.nn
+    good = lambda **kw: _Block(kw.pop("Cin", 32), kw.pop("stride", 1), kw.pop("projection", False), **kw).eval()
+    fold_block2(good())
+    fold_block2(good(Cin=16, stride=2, projection=True))
+
+    def with_(attr, value, **kw):
+        b = good(**kw)
+        setattr(b, attr, value)
+        return b
+    bn = lambda: nn.BatchNorm2d(32).eval()
+    strided = dict(Cin=16, stride=2, projection=True)
+    cases = [
+        ("mismatched strides", with_("downsample", nn.Sequential(nn.Conv2d(16, 32, 1, 1), bn()), **strided)),
+        ("mismatched strides", with_("downsample", nn.Sequential(nn.Conv2d(64, 32, 1, 2), bn()), Cin=64, projection=True)),
+        ("stride 2 without 'downsample'", with_("downsample", None, Cin=32, stride=2, projection=True)),
+        ("'conv2' must have stride 1", with_("conv2", nn.Sequential(nn.Conv2d(32, 32, 3, 2, 1), bn()))),
+        ("stride 1 or 2", with_("conv1", nn.Sequential(nn.Conv2d(32, 32, 3, 3, 1), bn(), nn.LeakyReLU(0.1)))),
+        ("stride 1 or 2", with_("conv1", nn.Sequential(nn.Conv2d(32, 32, 3, (1, 2), 1), bn(), nn.LeakyReLU(0.1)))),
+        ("padding 1", with_("conv1", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 0), bn(), nn.LeakyReLU(0.1)))),
+        ("padding 0", with_("downsample", nn.Sequential(nn.Conv2d(16, 32, 1, 2, 1), bn()), **strided)),
+        ("dilation 1", with_("conv2", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 1, dilation=2), bn()))),
+        ("groups 1", with_("conv2", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 1, groups=2), bn()))),
+        ("zero padding", with_("conv1", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 1, padding_mode="reflect"), bn(), nn.LeakyReLU(0.1)))),
+        ("kernel 3", with_("conv2", nn.Sequential(nn.Conv2d(32, 32, 5, 1, 2), bn()))),
+        ("kernel 1", with_("downsample", nn.Sequential(nn.Conv2d(16, 32, 3, 2, 1), bn()), **strided)),
+        ("eval", with_("conv2", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 1), nn.BatchNorm2d(32).train()))),
+        ("running statistics", with_("conv1", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 1), nn.BatchNorm2d(32, track_running_stats=False).eval(), nn.LeakyReLU(0.1)))),
+        ("32 output channels", with_("conv1", nn.Sequential(nn.Conv2d(32, 16, 3, 1, 1), nn.BatchNorm2d(16).eval(), nn.LeakyReLU(0.1)))),
+        ("32 output channels", _Block(16, 1, False, Cout=16).eval()),                                                  # a block of layer1
+        ("multiple of 8", with_("conv1", nn.Sequential(nn.Conv2d(12, 32, 3, 1, 1), bn(), nn.LeakyReLU(0.1)))),
+        ("no identity", with_("downsample", None, Cin=64, projection=True)),
+        ("LeakyReLU", with_("leaky", nn.ReLU())),
+        ("LeakyReLU", with_("conv1", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 1), bn(), nn.ReLU()))),
+        ("slope", with_("leaky", nn.LeakyReLU(float("nan")))),
+        ("slope", with_("leaky", nn.LeakyReLU(float("inf")))),
+        ("slope", with_("leaky", nn.LeakyReLU(1.5))),
+        ("slope", with_("conv1", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 1), bn(), nn.LeakyReLU(-2.0)))),
+        ("Sequential", with_("conv2", nn.Sequential(nn.Conv2d(32, 32, 3, 1, 1), bn(), nn.LeakyReLU(0.1)))),          # an activation where none is computed
+        ("Sequential", with_("conv1", nn.Conv2d(32, 32, 3, 1, 1))),
+    ]
+    for match, blk in cases:
+        with pytest.raises(ValueError, match="fold_block2: .*" + match):
+            fold_block2(blk.eval() if match != "eval" else blk)
+    with pytest.raises(ValueError, match="has no 'conv1'"):
+        fold_block2(nn.Linear(3, 3))
+    ok, strd = b2.random_block2(32, 1, 1, False), b2.random_block2(16, 1, 2, True)
+    assert check_block2(strd).stride == 2
+    for bad in (ok._replace(s1=np.zeros(4)), ok._replace(w1=np.zeros((32, 12, 3, 3))), ok._replace(w2=np.zeros((32, 8, 3, 3))),
+                ok._replace(wd=np.zeros((32, 32))), ok._replace(w1=np.zeros((32, 64, 3, 3))), ok._replace(slope_mid=float("nan")),
+                ok._replace(slope_out=2.0), b2.random_block2(64, 1, 1, True)._replace(sd=None), ok._replace(stride=2), ok._replace(stride=0),
+                strd._replace(stride=3), strd._replace(stride=1.5), ok._replace(w1=np.zeros((16, 32, 3, 3)))):
+        with pytest.raises(ValueError, match="Block2Spec"):
+            check_block2(bad)
+    blocks = check_blocks(sr.delta_spec(16), [br.doubling_block()])
+    assert len(check_blocks2(blocks, [strd, ok, ok, ok])) == 4 and BLOCK2_CHANNELS == 32
+    with pytest.raises(ValueError, match="block 0 takes 32 channels, but 16 arrive"):
+        check_blocks2(blocks, [ok])
+    with pytest.raises(ValueError, match="block 1 takes 16 channels, but 32 arrive"):
+        check_blocks2(blocks, [strd, strd])
+    with pytest.raises(ValueError, match="at least one"):
+        check_blocks2(blocks, [])
+    # the front end's one place for these refusals, with its old two-value form intact
+    stem = sr.delta_spec(16)
+    assert len(MmpFrontEnd.check_specs(stem, blocks)) == 2 and MmpFrontEnd.check_specs(None, None) == (None, None)
+    assert MmpFrontEnd.check_specs(stem, blocks, blocks2=None)[2] is None and len(MmpFrontEnd.check_specs(stem, blocks, blocks2=[strd, ok])[2]) == 2
+    with pytest.raises(ValueError, match="mmp_blocks2 needs mmp_blocks "):
+        MmpFrontEnd.check_specs(stem, None, prefix="mmp_", blocks2=[strd])
+    with pytest.raises(ValueError, match="blocks needs stem"):
+        MmpFrontEnd.check_specs(None, blocks, blocks2=[strd])
+
+
+# ---- 4. the split ---------------------------------------------------------------------------------------------------------------------------
+class _Net(torch.nn.Module):
+    """A module with the attribute names of the reference's ConvMultiHypoNet(lite=True), written anew and much smaller."""
+    def __init__(self, C=8, K=3, n_blocks2=4):
+        super().__init__()
+        nn = torch.nn
+        body = nn.Module()
+        body.stem = nn.Module()
+        body.stem.conv1 = nn.Sequential(nn.Conv2d(7, C, 7, 2, 3, bias=False), nn.BatchNorm2d(C), nn.LeakyReLU(0.1))
+        body.stem.pooling = nn.MaxPool2d(3, 2, 1)
+        body.layer1 = nn.Sequential(*[_Block(C if i == 0 else 16, 1, i == 0, Cout=16) for i in range(3)])
+        body.layer2 = nn.Sequential(*[_Block(16 if i == 0 else 32, 2 if i == 0 else 1, i == 0) for i in range(n_blocks2)])
+        body.layer3, body.layer4, body.apool = nn.Conv2d(32, 4, 3, 2, 1), nn.ReLU(), nn.AdaptiveAvgPool2d(2)
+        self.resnet34 = body
+        self.fc1, self.leaky, self.swarm = nn.Linear(16, 8), nn.LeakyReLU(), nn.Linear(8, 2 * K)
+        _randomise(self, seed=11)
+
+    def forward(self, x):
+        b = self.resnet34
+        x = b.layer2(b.layer1(b.stem.pooling(b.stem.conv1(x))))
+        x = b.apool(b.layer4(b.layer3(x)))
+        return self.swarm(self.leaky(self.fc1(x.view(x.size(0), -1))))
+
+
+def test_split_network_layer2_gives_stem_blocks_and_a_trunk_that_completes_them():
+    import mmp_reference as mr
+    net = _Net().eval()
+    spec, blocks, blocks2, trunk = split_network_layer2(net)
+    assert len(blocks) == 3 and blocks[0].wd is not None and blocks[0].w1.shape[1] == 8 and all(b.wd is None for b in blocks[1:])
+    assert len(blocks2) == 4 and [b.stride for b in blocks2] == [2, 1, 1, 1] and blocks2[0].wd.shape == (32, 16) and all(b.wd is None for b in blocks2[1:])
+    rng = np.random.default_rng(0)
+    ref = np.where(rng.random((24, 31)) < 0.3, 0.0, 255.0).astype(np.float32)
+    stack = mr.input_stack(mr.input_planes(np.array([[3.25, 4.5], [5.0, 6.75], [7.5, 8.0]]), ref), 2)
+    with torch.no_grad():
+        want = net(torch.from_numpy(stack))
+        y, _ = sr.stem(stack, spec.weight, spec.scale, spec.shift, spec.slope)
+        for b in blocks:
+            y, _ = br.block(y, b)
+        for b in blocks2:
+            y, _ = b2.block(y, b)
+        assert y.shape == (2, 32, 3, 4)                     # 24 x 31 -> 12 x 16 -> 6 x 8 -> 3 x 4
+        got = trunk(torch.from_numpy(y.astype(np.float32)))
+    assert got.shape == want.shape == (2, 6) and torch.allclose(got, want, rtol=1e-4, atol=1e-4)
+    with pytest.raises(ValueError, match="four blocks"):
+        split_network_layer2(_Net(n_blocks2=3).eval())
+    with pytest.raises(ValueError, match="eval"):
+        split_network_layer2(_Net().train())
+    with pytest.raises(ValueError, match="resnet34"):
+        split_network_layer2(torch.nn.Linear(3, 3))
+
+
+# ---- 5. the struct and the symbol: no device needed -------------------------------------------------------------------------------------------
+def test_block2_entry_point_refuses_null_arguments():
+    lib = nm.load_library()
+    assert "nmpc_mmp_block2_f32" in nm.EXPORTED_SYMBOLS and hasattr(lib, "nmpc_mmp_block2_f32")
+    a = _capi.NmpcMmpBlock2Args()
+    assert lib.nmpc_mmp_block2_f32(None, ctypes.byref(a)) == -1 and lib.nmpc_mmp_block2_f32(None, None) == -1
+
+
+def test_block2_args_layout_matches_the_c_compiler():
+    fields = [f[0] for f in _capi.NmpcMmpBlock2Args._fields_]
+    assert fields == ["M", "Cin", "H", "W", "x", "w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd", "slope_mid", "slope_out", "out", "stride"]
+    assert [f[0] for f in _capi.NmpcMmpBlockArgs._fields_] == fields[:-1]
+    with tempfile.TemporaryDirectory() as td:
+        src = os.path.join(td, "sz.c")
+        body = "".join(f'printf(" %zu", offsetof(nmpc_mmp_block2_args, {f}));' for f in fields)
+        body += "".join(f'printf(" %zu", offsetof(nmpc_mmp_block_args, {f}));' for f in fields[:-1])
+        open(src, "w").write('#include <stdio.h>\n#include <stddef.h>\n#include "nmpc_hip.h"\nint main(void){printf("%zu", sizeof(nmpc_mmp_block2_args));'
+                             + body + 'printf(" %zu %d", sizeof(nmpc_mmp_block_args), NMPC_ABI_VERSION);return 0;}\n')
+        exe = os.path.join(td, "sz")
+        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
+        out = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    n = len(fields)
+    assert ctypes.sizeof(_capi.NmpcMmpBlock2Args) == out[0]
+    assert [getattr(_capi.NmpcMmpBlock2Args, f).offset for f in fields] == out[1:1 + n]
+    assert [getattr(_capi.NmpcMmpBlockArgs, f).offset for f in fields[:-1]] == out[1 + n:2 * n]      # nothing that existed changed
+    assert out[-2] == ctypes.sizeof(_capi.NmpcMmpBlockArgs) == 112 and out[-1] == 5
+
+
+def test_block2_kernels_use_no_scratch_and_fit_two_workgroups_per_cu():
+    """Read from the shipped code object: the three kernels (stride 2; stride 1 with and without the projection) without VGPR
+    spills or scratch, within the 256 registers of two wavefronts per SIMD, and under 80 KB of LDS (two workgroups in a CU's
+    160 KB): the occupancy csrc/nmpc_mmp_block2.h states in its __launch_bounds__."""
+    import re
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import kernel_resources
+    finally:
+        sys.path.remove(os.path.join(ROOT, "tools"))
+    nm.build_library()
+    res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
+    mine = {k: v for k, v in res.items() if re.search(r"mmp_blk2_kernel", k)}
+    assert len(mine) == 3, sorted(mine)
+    assert not any("mmp_block_kernel" in k for k in mine)
+    for name, r in mine.items():
+        print(name, r)
+        assert r["vgpr_spill"] == 0 and r["scratch"] == 0, (name, r)      # (SGPRs parked in VGPR lanes touch no memory)
+        assert r["vgpr"] + max(r["agpr"], 0) <= 256 and r["lds_static"] <= 80 * 1024, (name, r)
+
+
+# ---- 6. the controls of the bound, before any device run ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", b2.CASES + b2.REAL, ids=b2.case_id)
+def test_the_bound_admits_float32_and_refuses_the_wrong_variants(c):
+    """On every case of the GPU tests: torch's own float32 block meets the bound, each wrong variant misses it ("phase" and
+    "idphase" exist at stride 2 only; no plane had to be excluded). Recorded here: torch's float32 at most 0.0041 of the bound;
+    the smallest factor by which a wrong variant misses it -- "slope" 146 (8 x 44, Cin 64), "halo" 521 (11 x 50, Cin 64), "phase"
+    3 580 (16 x 88, Cin 16), "idphase" 11 200 (74 x 83, Cin 16)."""
+    H, W, Cin, stride, projection = c
+    x, spec, want, bound = b2.case("random", *c, 2 if c in b2.REAL else b2.M_MAX)
+    assert want.shape == (x.shape[0], 32) + b2.out_plane(H, W, stride) and (bound > 0).all()
+    r32 = (np.abs(b2.torch_float32(x, spec) - want) / bound).max()
+    line = f"{b2.case_id(c)}: torch float32 {r32:.4f}"
+    assert r32 <= 1.0, "the bound refuses torch's own float32 block"
+    for wrong in ("slope", "halo") + (("phase", "idphase") if stride == 2 else ()):
+        bad, _ = b2.block(x, spec, wrong=wrong)
+        factor = (np.abs(bad - want) / bound).max()
+        line += f", {wrong} x {factor:.0f}"
+        assert bad.shape == want.shape and factor > 1.0, f"the bound admits the wrong variant {wrong!r}"
+    print(line)
+    if stride == 1:
+        with pytest.raises(ValueError, match="stride 2 only"):
+            b2.block(x[:1], spec, wrong="phase")
+    # the integer block of the exact GPU test: nothing can round, and torch's float32 is exact on it as well
+    xi, si, wi, _ = b2.case("integer", *c, 2 if c in b2.REAL else b2.M_MAX)
+    assert b2.integer_units(xi, si) < 2.0 ** 24
+    assert np.array_equal(wi.astype(np.float32).astype(np.float64), wi) and np.array_equal(b2.torch_float32(xi, si), wi.astype(np.float32))
+
+
+def test_the_exact_blocks_of_the_loop_test():
+    x = np.abs(br.random_x(2, 16, 7, 10, seed=5))
+    half = x[:, :, ::2, ::2]
+    got, _ = b2.block(x, b2.duplicate_and_double_block2(16))
+    assert np.array_equal(got, np.concatenate([half + half, half + half], axis=1))
+    got2, _ = b2.block(got, b2.doubling_block2())
+    assert np.array_equal(got2, got + got)
+    check_blocks2((br.doubling_block(),), (b2.duplicate_and_double_block2(16),) + (b2.doubling_block2(),) * 3)

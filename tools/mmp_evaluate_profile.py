@@ -23,8 +23,15 @@ one chunk of the parent path -- the share of the network's time that the first l
 events around ``input``, ``layer1``, ``network`` and the whole stage. Beside them: torch's own layer1, eager, alone on one chunk
 of the parent path's stem output (the time the three block launches have to beat, and its share of the parent's network time),
 and the block kernels alone on one chunk as fma per second against the fp32 peak and bytes per second against the copy rate.
-   usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp] [--fused-stem [REPS] | --fused-layer1 [REPS]]
-          (defaults 256 3 f32 4 20; 3)"""
+
+``--fused-layer2``: one step further again. The parent path is the new path of ``--fused-layer1`` (fused first layer and layer1,
+trunk from layer2 on in torch); the new path hands the second residual stage (four blocks at 32 channels, the first at stride 2,
+``mmp_stem.fold_block2`` -> ``nmpc_mmp_block2_f32``) to the device stage as well and keeps the trunk from layer3 on. Alternated as
+above, with HIP events around ``input``, ``layer1``, ``layer2``, ``network`` and the whole stage. Beside them: torch's own layer2,
+eager, alone on one chunk of the parent path's layer1 output, and the four launches alone on one chunk as fma per second against
+the fp32 peak and bytes per second against the copy rate, next to the model of csrc/nmpc_mmp_block2.h.
+   usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]
+          [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS]]      (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
 import sys
@@ -289,8 +296,121 @@ def fused_layer1_main(out_path, B, steps, dt, n_ped, K, reps):
                                           "torch_layer1_share_of_parent_network", "block_kernels_per_lock_step_ms")}))
 
 
+def torch_layer2_alone(ev, layer2, n_item, reps=5):
+    """ms of torch's own layer2 (four blocks, eager) on the layer1 output of ``n_item`` pedestrians: one chunk of the parent path."""
+    fe = ev.mmp_front
+    rows = _fill(ev, n_item)().shape[0]
+    x = fe.run_blocks(rows)
+    with torch.no_grad():
+        t = _timed(lambda: layer2(x), reps)
+    return dict(items=n_item, samples=rows, **t)
+
+
+def block2_kernel_rate(ev, n_item, reps=10):
+    """The four nmpc_mmp_block2_f32 launches alone on the layer1 output of ``n_item`` pedestrians: ms each and together, useful fma
+    per second (32 (9 Cin + 9 32 (+ Cin)) per output pixel) and bytes per second (x read once, out written once)."""
+    fe = ev.mmp_front
+    rows = _fill(ev, n_item)().shape[0]
+    fe.run_blocks(rows)
+    n1, (H, W) = len(fe.blocks), fe.fill_row[1:]
+    rec = {"items": n_item, "rows": rows, "blocks": []}
+    fma_all = bytes_all = 0
+    for i, b in enumerate(fe.blocks2):
+        Cin, proj, s = int(b.w1.shape[1]), b.wd is not None, int(b.stride)
+        H2, W2 = (H - 1) // s + 1, (W - 1) // s + 1
+        fma = rows * H2 * W2 * 32 * (9 * Cin + 9 * 32 + (Cin if proj else 0))
+        nbytes = rows * 4 * (Cin * H * W + 32 * H2 * W2)
+        t = _timed(lambda: fe.run_block(n1 + i, rows), reps, warm=3)
+        rec["blocks"].append(dict(Cin=Cin, stride=s, projection=proj, plane_in=[H, W], plane_out=[H2, W2], fma=fma, bytes=nbytes,
+                                  TFMAps_median=fma / t["ms_median"] * 1e-9, share_of_fp32_peak=fma / t["ms_median"] * 1e-9 / PEAK_TFMAS,
+                                  GBps_median=nbytes / t["ms_median"] * 1e-6, share_of_copy_rate=nbytes / t["ms_median"] * 1e-9 / COPY_TBS, **t))
+        fma_all, bytes_all, H, W = fma_all + fma, bytes_all + nbytes, H2, W2
+    t = _timed(lambda: fe.run_blocks2(rows), reps, warm=3)
+    rec.update(fma=fma_all, bytes=bytes_all, TFMAps_median=fma_all / t["ms_median"] * 1e-9, share_of_fp32_peak=fma_all / t["ms_median"] * 1e-9 / PEAK_TFMAS,
+               GBps_median=bytes_all / t["ms_median"] * 1e-6, share_of_copy_rate=bytes_all / t["ms_median"] * 1e-9 / COPY_TBS, **t)
+    return rec
+
+
+def fused_layer2_main(out_path, B, steps, dt, n_ped, K, reps):
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import fold_block, fold_block2, fold_stem
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    # the split, by hand (the module here is a plain Sequential, not of the shape split_network_layer2 takes): net[0], net[1] = the
+    # first layer; net[2 .. 4] = layer1, net[5 .. 8] = layer2 (Block: a, b, skip, act); the rest is the trunk
+    spec = fold_stem(net[0][0], net[0][1], net[0][2], net[1])
+    as_block = lambda b: SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)
+    blocks = tuple(fold_block(as_block(b)) for b in list(net)[2:5])
+    blocks2 = tuple(fold_block2(as_block(b)) for b in list(net)[5:9])
+    layer2, trunk2, trunk3 = torch.nn.Sequential(*list(net)[5:9]), torch.nn.Sequential(*list(net)[5:]), torch.nn.Sequential(*list(net)[9:])
+    paths = {"parent": dict(network=lambda x: trunk2(x) + 150.0, mmp_stem=spec, mmp_blocks=blocks),
+             "fused": dict(network=lambda x: trunk3(x) + 150.0, mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2)}
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rows_step = B * n_ped * nm.default_config_struct().N_hor
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage: the parent path (fused first layer + "
+                   "fused layer1 + trunk from layer2 on in torch) and the same with layer2 fused as well + trunk from layer3 on, alternated in "
+                   "one process; random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS, "fp32_peak_TFMAps": PEAK_TFMAS},
+           "model_of_the_header_per_lock_step_ms": {"rows": 20480, "mfma_pipe_never_waits": 40.2, "useful_fma_at_fp32_peak": 28.2, "bytes_at_copy_rate": 5.8},
+           "chunk_pedestrians": {}, "runs": {"parent": [], "fused": []}}
+    for path in paths:                                      # warm-up: code objects, library algorithm choice, allocator
+        ev = evaluator(path)
+        rec["chunk_pedestrians"][path] = ev.mmp_chunk
+        try:
+            if path == "fused":
+                rec["block2_kernels"] = block2_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped))
+            else:
+                rec["torch_layer2_alone"] = torch_layer2_alone(ev, layer2, min(ev.mmp_chunk, B * n_ped))
+            ev.run(max_steps=1)
+        finally:
+            ev.close()
+        print(json.dumps({k: rec[k] for k in ("block2_kernels", "torch_layer2_alone") if k in rec}), flush=True)
+        with open(out_path, "w") as f:
+            json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = {"parent": ("input", "layer1", "network"), "fused": ("input", "layer1", "layer2", "network")}
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names[p]},
+                                              behind_layer1=med(p, lambda s, p=p: sum(s[k] for k in names[p][2:])),
+                                              stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    m = rec["median_per_lock_step_ms"]
+    rec["fused_layer2_over_parent"] = m["fused"]["stage"] / m["parent"]["stage"]
+    # torch's layer2 alone on one chunk, scaled to the rows of a lock-step: its share of the parent's network time; and the four
+    # block launches alone, scaled alike, against the header's model
+    tl, bk = rec["torch_layer2_alone"], rec["block2_kernels"]
+    rec["torch_layer2_per_lock_step_ms"] = tl["ms_median"] * (rows_step / tl["samples"])
+    rec["torch_layer2_share_of_parent_network"] = rec["torch_layer2_per_lock_step_ms"] / m["parent"]["network"]
+    rec["block2_kernels_per_lock_step_ms"] = bk["ms_median"] * (rows_step / bk["rows"])
+    rec["block2_kernels_over_torch_layer2"] = rec["block2_kernels_per_lock_step_ms"] / rec["torch_layer2_per_lock_step_ms"]
+    rec["block2_kernels_over_model"] = rec["block2_kernels_per_lock_step_ms"] * (20480 / rows_step) / 40.2
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "fused_layer2_over_parent", "torch_layer2_per_lock_step_ms",
+                                          "torch_layer2_share_of_parent_network", "block2_kernels_per_lock_step_ms",
+                                          "block2_kernels_over_torch_layer2", "block2_kernels_over_model")}))
+
+
 def main():
-    for flag, run in (("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+    for flag, run in (("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
         if flag in sys.argv:
             i = sys.argv.index(flag)
             reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
