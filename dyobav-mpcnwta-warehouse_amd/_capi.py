@@ -177,8 +177,42 @@ EXPORTED_SYMBOLS = (
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
     "nmpc_mmp_block2_f32",
-    "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_last_error",
+    "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
+    "nmpc_last_error",
 )
+
+# nmpc_probe_*: op name -> (number = ``nmpc_probe_op`` of include/nmpc_hip.h, the functions of csrc/wave_ops.h /
+# csrc/nmpc_device.h the op runs, operands read from ``in``, rows of ``out`` it produces, float only). The CPU suite checks
+# that every ``__device__`` function of wave_ops.h (but dpp_mov and the ref_* loops) is run by some op.
+PROBE_OPS = {
+    "wave_sum": (0, ("wave_sum", "read_lane"), 1, 1, False),
+    "wave_sum2": (1, ("wave_sum2",), 2, 2, False),
+    "wave_sum3": (2, ("wave_sum3",), 3, 3, False),
+    "wave_scan_incl": (3, ("wave_scan_incl",), 1, 1, False),
+    "wave_scan_incl2": (4, ("wave_scan_incl2",), 2, 2, False),
+    "wave_scan_suffix_incl": (5, ("wave_scan_suffix_incl", "wave_suffix_fix_rows"), 1, 1, False),
+    "wave_scan_suffix_incl2": (6, ("wave_scan_suffix_incl2", "wave_suffix_fix_rows"), 2, 2, False),
+    "wave_suffix_fix_rows": (7, ("wave_suffix_fix_rows",), 1, 1, False),
+    "class3_sum2": (8, ("class3_sum2", "class3_addresses", "bperm"), 2, 2, False),
+    "class3_sum1": (9, ("class3_sum1", "class3_addresses", "bperm"), 1, 1, False),
+    "class3_issue1_finish1": (10, ("class3_issue1", "class3_finish1", "class3_addresses", "bperm"), 1, 1, False),
+    "class3_addresses": (11, ("class3_addresses",), 0, 4, False),
+    "wave_reverse": (12, ("wave_reverse",), 1, 1, False),
+    "read_lane": (13, ("read_lane",), 1, 6, False),
+    "bperm": (14, ("bperm",), 2, 1, False),
+    "wave_shift_up_1": (15, ("wave_shift_up",), 1, 1, False),
+    "wave_shift_up_3": (16, ("wave_shift_up",), 1, 1, False),
+    "wave_shift_down_1": (17, ("wave_shift_down",), 1, 1, False),
+    "wave_shift_down_2": (18, ("wave_shift_down",), 1, 1, False),
+    "wave_shift_down_3": (19, ("wave_shift_down",), 1, 1, False),
+    "rollout_prefix": (20, ("wave_scan_incl", "wave_shift_up"), 1, 2, False),
+    "adjoint_suffix": (21, ("wave_shift_up", "wave_scan_suffix_incl2", "wave_scan_suffix_incl", "wave_shift_down"), 2, 4, False),
+    "class_sums_by_wave_sum3": (22, ("wave_sum3",), 1, 3, False),
+    "sincos_medium": (23, ("sincos_medium",), 1, 4, True),
+    "sincos_small": (24, ("sincos_small",), 1, 4, True),
+    "fast_rcp": (25, ("fast_rcp",), 1, 2, False),
+    "ls_point": (26, ("ls_point",), 4, 1, False),
+}
 
 _lib: Optional[C.CDLL] = None
 
@@ -239,6 +273,7 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     lib.nmpc_kernel_info.argtypes = [vp] + [C.POINTER(i32)] * 5
     lib.nmpc_last_launch_info.argtypes = [vp, C.POINTER(i32 * 8)]
     lib.nmpc_selftest.argtypes = [vp]
+    lib.nmpc_probe_f32.argtypes = lib.nmpc_probe_f64.argtypes = [vp, i32, i32, i32, vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name != "nmpc_last_error":
             getattr(lib, name).restype = C.c_int
@@ -358,6 +393,29 @@ class Handle:
 
     def selftest(self) -> int:
         return _check(self._lib.nmpc_selftest(self._h))
+
+    def probe_raw(self, dtype, op: int, block_threads: int, n_waves: int, x, out):
+        """Thin call of ``nmpc_probe_*``: ``x`` [n_waves, 4, 64] and ``out`` [n_waves, 6, 64] may be numpy, torch or raw pointers."""
+        fn = getattr(self._lib, "nmpc_probe_" + _suffix(dtype))
+        _check(fn(self._h, int(op), int(block_threads), int(n_waves), _Arg.ptr(x), _Arg.ptr(out)))
+
+    def probe(self, op: str, x, dtype, block_threads: int = 64):
+        """``nmpc_probe_*``: one wavefront primitive or scalar function of the product headers (``PROBE_OPS``) run by itself.
+        ``x``: one array [n_waves, 64] per operand of the op (a single array for a one-operand op). Returns the op's output
+        rows as numpy arrays [n_waves, 64] (a single array if it has one)."""
+        num, _, n_in, n_out, _ = PROBE_OPS[op]
+        dtype = np.dtype(dtype)
+        xs = [x] if isinstance(x, np.ndarray) else list(x)
+        assert len(xs) == n_in or (n_in == 0 and len(xs) == 1), (op, len(xs))
+        n_waves = xs[0].shape[0]
+        buf = np.zeros((n_waves, 4, 64), dtype)
+        for i, a in enumerate(xs[:n_in]):
+            assert a.shape == (n_waves, 64), a.shape
+            buf[:, i, :] = a
+        out = np.full((n_waves, 6, 64), np.nan, dtype)
+        self.probe_raw(dtype, num, block_threads, n_waves, buf, out)
+        rows = [np.ascontiguousarray(out[:, i, :]) for i in range(n_out)]
+        return rows[0] if n_out == 1 else rows
 
     def last_kernel_ms(self) -> float:
         ms = C.c_float()

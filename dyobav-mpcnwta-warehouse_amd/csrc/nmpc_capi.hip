@@ -13,6 +13,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/nmpc_hip.h"
@@ -489,6 +490,126 @@ __global__ __launch_bounds__(64) void selftest_kernel(int* fails)
         }
     }
     if (bad) atomicOr(fails, bad);
+}
+
+// nmpc_probe_*: ONE product function per kernel, every lane's result stored (include/nmpc_hip.h, nmpc_probe_op). One kernel
+// per (op, T), so that no primitive's schedule depends on another's; the wave-uniform guard on the wave index is the only
+// control flow. Wave w reads in[w][4][64] and writes out[w][6][64] (rows an op does not produce: 0).
+constexpr int kProbeLps = 3; // lanes per horizon step of the shipped configurations: the shift counts and classes of the compositions
+template <int OP, typename T>
+__global__ __launch_bounds__(256) void probe_kernel(const T* __restrict__ in, T* __restrict__ out, int n_waves)
+{
+    const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); // (<= n_waves + 3: no overflow)
+    if (wave >= n_waves) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const T* src = in + (size_t)wave * (4 * 64) + lane;
+    const T x0 = src[0], x1 = src[64], x2 = src[128], x3 = src[192];
+    T o0 = 0, o1 = 0, o2 = 0, o3 = 0, o4 = 0, o5 = 0;
+    if constexpr (OP == NMPC_PROBE_WAVE_SUM) {
+        o0 = nmpc::wave_sum(x0);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SUM2) {
+        nmpc::wave_sum2(x0, x1, o0, o1);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SUM3) {
+        nmpc::wave_sum3(x0, x1, x2, o0, o1, o2);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SCAN_INCL) {
+        o0 = nmpc::wave_scan_incl(x0);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SCAN_INCL2) {
+        o0 = x0, o1 = x1;
+        nmpc::wave_scan_incl2(o0, o1);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SCAN_SUFFIX_INCL) {
+        o0 = nmpc::wave_scan_suffix_incl(x0);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SCAN_SUFFIX_INCL2) {
+        o0 = x0, o1 = x1;
+        nmpc::wave_scan_suffix_incl2(o0, o1);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SUFFIX_FIX_ROWS) {
+        o0 = nmpc::wave_suffix_fix_rows(x0);
+    } else if constexpr (OP == NMPC_PROBE_CLASS3_SUM2) {
+        int a[4];
+        nmpc::class3_addresses(lane % 3, a);
+        o0 = x0, o1 = x1;
+        nmpc::class3_sum2(o0, o1, a);
+    } else if constexpr (OP == NMPC_PROBE_CLASS3_SUM1) {
+        int a[4];
+        nmpc::class3_addresses(lane % 3, a);
+        o0 = x0;
+        nmpc::class3_sum1(o0, a);
+    } else if constexpr (OP == NMPC_PROBE_CLASS3_ISSUE1_FINISH1) {
+        int a[4];
+        nmpc::class3_addresses(lane % 3, a);
+        nmpc::Class3Pending1<T> pend;
+        nmpc::class3_issue1(x0, a, pend);
+        o0 = nmpc::class3_finish1(pend);
+    } else if constexpr (OP == NMPC_PROBE_CLASS3_ADDRESSES) {
+        int a[4];
+        nmpc::class3_addresses(lane % 3, a);
+        o0 = T(a[0]), o1 = T(a[1]), o2 = T(a[2]), o3 = T(a[3]);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_REVERSE) {
+        o0 = nmpc::wave_reverse(x0);
+    } else if constexpr (OP == NMPC_PROBE_READ_LANE) { // (the lanes the kernels read: the row starts of the suffix scan, the last tail lane, 63)
+        o0 = nmpc::read_lane(x0, 0), o1 = nmpc::read_lane(x0, 16), o2 = nmpc::read_lane(x0, 32);
+        o3 = nmpc::read_lane(x0, 48), o4 = nmpc::read_lane(x0, 57), o5 = nmpc::read_lane(x0, 63);
+    } else if constexpr (OP == NMPC_PROBE_BPERM) {
+        o0 = nmpc::bperm(x0, (int)x1);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SHIFT_UP_1) {
+        o0 = nmpc::wave_shift_up<1>(x0);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SHIFT_UP_3) {
+        o0 = nmpc::wave_shift_up<3>(x0);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SHIFT_DOWN_1) {
+        o0 = nmpc::wave_shift_down<1>(x0);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SHIFT_DOWN_2) {
+        o0 = nmpc::wave_shift_down<2>(x0);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SHIFT_DOWN_3) {
+        o0 = nmpc::wave_shift_down<3>(x0);
+    } else if constexpr (OP == NMPC_PROBE_ROLLOUT_PREFIX) { // nmpc_device.h, rollout: the heading prefix and its shift by one step
+        o1 = nmpc::wave_scan_incl(x0);
+        o0 = nmpc::wave_shift_up<kProbeLps>(o1);
+    } else if constexpr (OP == NMPC_PROBE_ADJOINT_SUFFIX) { // nmpc_device.h, adjoint: step totals at the tail lane, two suffix sums, the shift back
+        const bool tail = lane % kProbeLps == kProbeLps - 1;
+        T Gx = x0, Gy = x1;
+        T a = x0, b = x1;
+#pragma unroll
+        for (int i = 1; i < kProbeLps; ++i) {
+            a = nmpc::wave_shift_up<1>(a);
+            b = nmpc::wave_shift_up<1>(b);
+            Gx += a;
+            Gy += b;
+        }
+        T Lx = tail ? Gx : T(0), Ly = tail ? Gy : T(0);
+        nmpc::wave_scan_suffix_incl2(Lx, Ly);
+        const T Mx = nmpc::wave_scan_suffix_incl(tail ? Lx : T(0));
+        o2 = nmpc::wave_shift_down<kProbeLps>(Mx);
+        const T My = nmpc::wave_scan_suffix_incl(tail ? Ly : T(0));
+        o3 = nmpc::wave_shift_down<kProbeLps>(My);
+        o0 = Lx, o1 = Ly;
+    } else if constexpr (OP == NMPC_PROBE_CLASS_SUMS_BY_WAVE_SUM3) { // nmpc_device.h, obstacle passes on the LDS / global table
+        const int r = lane % 3;
+        nmpc::wave_sum3(r == 0 ? x0 : T(0), r == 1 ? x0 : T(0), r == 2 ? x0 : T(0), o0, o1, o2);
+    } else if constexpr (OP == NMPC_PROBE_SINCOS_MEDIUM) {
+        if constexpr (sizeof(T) == 4) {
+            nmpc::sincos_medium(x0, o0, o1);
+            sincosf(x0, &o2, &o3);
+        }
+    } else if constexpr (OP == NMPC_PROBE_SINCOS_SMALL) {
+        if constexpr (sizeof(T) == 4) {
+            nmpc::sincos_small(x0, o0, o1);
+            sincosf(x0, &o2, &o3);
+        }
+    } else if constexpr (OP == NMPC_PROBE_FAST_RCP) {
+        o0 = nmpc::fast_rcp(x0);
+        o1 = T(1) / x0;
+    } else if constexpr (OP == NMPC_PROBE_LS_POINT) {
+        o0 = nmpc::ls_point(x0, x1, x2, x3);
+    }
+    T* dst = out + (size_t)wave * (6 * 64) + lane;
+    dst[0] = o0, dst[64] = o1, dst[128] = o2, dst[192] = o3, dst[256] = o4, dst[320] = o5;
+}
+template <typename T>
+using ProbeFn = void (*)(const T*, T*, int);
+template <typename T, int... OP>
+ProbeFn<T> probe_kernel_of(int op, std::integer_sequence<int, OP...>)
+{
+    static constexpr ProbeFn<T> table[] = {probe_kernel<OP, T>...};
+    return table[op];
 }
 
 // The layout-dependent fields only (parameter offsets, LDS map): what a kernel choice that brings its own layout re-fills,
@@ -1778,6 +1899,39 @@ int set_lds_limit(nmpc_handle_s* h)
 
 } // namespace
 
+// nmpc_probe_*: see include/nmpc_hip.h
+template <typename T>
+int probe(nmpc_handle_s* h, int op, int block_threads, int n_waves, const T* in, T* out)
+{
+    // (the arguments before the handle: every refusal below needs no device)
+    if (op < 0 || op >= NMPC_PROBE_N_OPS) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: unknown op %d (0 .. %d)", op, NMPC_PROBE_N_OPS - 1);
+    if (sizeof(T) == 8 && (op == NMPC_PROBE_SINCOS_MEDIUM || op == NMPC_PROBE_SINCOS_SMALL))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: unknown op %d for f64 (sincos_medium / sincos_small are float only)", op);
+    if (block_threads != 64 && block_threads != 128 && block_threads != 256)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: block_threads %d is not 64, 128 or 256", block_threads);
+    if (n_waves < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: negative n_waves %d", n_waves);
+    if (!in || !out) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: NULL in / out");
+    if (!h) return fail(NMPC_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_waves == 0) return 0;
+    const size_t waves_per_block = (size_t)block_threads / 64, blocks = ((size_t)n_waves + waves_per_block - 1) / waves_per_block;
+    if (blocks > 0x7fffffffull) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_probe: %d waves need more than 2^31 - 1 workgroups", n_waves);
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    DevBuf bin, bout; // freed on every path below
+    const T* din = nullptr;
+    T* dout = nullptr;
+    bool out_host = false;
+    const size_t n_in = (size_t)n_waves * 4 * 64, n_out = (size_t)n_waves * 6 * 64;
+    if (int rc = stage_in(h, bin, in, n_in, &din)) return rc;
+    if (int rc = stage_out(h, bout, out, n_out, &dout, &out_host)) return rc;
+    hipLaunchKernelGGL(probe_kernel_of<T>(op, std::make_integer_sequence<int, NMPC_PROBE_N_OPS>{}), dim3((unsigned)blocks), dim3(block_threads),
+                       0, h->stream, din, dout, n_waves);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && out_host) e = hipMemcpyAsync(out, dout, n_out * sizeof(T), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // (synchronous: the staging buffers go out of scope)
+    if (e != hipSuccess) return fail(NMPC_ERR_HIP, "nmpc_probe: %s", hipGetErrorString(e));
+    return 0;
+}
+
 extern "C" {
 
 const char* nmpc_last_error(void) { return g_err.c_str(); }
@@ -2162,6 +2316,15 @@ int nmpc_kernel_info(nmpc_handle h, int32_t* lds_bytes_f32, int32_t* lds_bytes_f
         *waves_per_cu_f64 = nb;
     }
     return 0;
+}
+
+int nmpc_probe_f32(nmpc_handle h, int32_t op, int32_t block_threads, int32_t n_waves, const float* in, float* out)
+{
+    return probe<float>(h, op, block_threads, n_waves, in, out);
+}
+int nmpc_probe_f64(nmpc_handle h, int32_t op, int32_t block_threads, int32_t n_waves, const double* in, double* out)
+{
+    return probe<double>(h, op, block_threads, n_waves, in, out);
 }
 
 int nmpc_selftest(nmpc_handle h)

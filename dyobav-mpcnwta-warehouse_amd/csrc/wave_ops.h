@@ -73,6 +73,11 @@ __device__ __forceinline__ double read_lane(double x, int lane)
 //      (row_bcast) would come out as v_mov (old) + v_mov_dpp + v_add: those are asm blocks with their own s_nop.
 
 // Sum over the 64 lanes; the result is wave-uniform (read back from lane 63 into scalar registers).
+// Association (every wave_sum / wave_sum2 / wave_sum3, float and double): in each 16-lane row a butterfly -- every lane
+// adds its quad neighbour (lane ^ 1), then the other pair of its quad (lane ^ 2), then the mirrored lane of its half row
+// (lane ^ 7), then the mirrored lane of its row (lane ^ 15) -- which leaves the row sum r0..r3 in every lane of the row;
+// then r1 += r0 and r3 += r2 (row_bcast:15 into rows 1, 3), then rows 2 and 3 += (r0 + r1) (row_bcast:31), and lane 63
+// holds (r3 + r2) + (r0 + r1).
 __device__ __forceinline__ float wave_sum(float x)
 {
     // The four in-row steps (full row / bank masks) through builtins: the compiler folds each into one v_add_f32_dpp and
@@ -131,27 +136,6 @@ __device__ __forceinline__ void wave_sum3(float x, float y, float z, float& sx, 
     sy = read_lane(y, 63);
     sz = read_lane(z, 63);
 }
-// six independent sums: with six chains in flight no DPP wait state is left to pad
-#define NMPC_P6(ctrl)                                                                                         \
-    "v_add_f32_dpp %0, %0, %0 " ctrl "\n\tv_add_f32_dpp %1, %1, %1 " ctrl "\n\tv_add_f32_dpp %2, %2, %2 " ctrl \
-    "\n\tv_add_f32_dpp %3, %3, %3 " ctrl "\n\tv_add_f32_dpp %4, %4, %4 " ctrl "\n\tv_add_f32_dpp %5, %5, %5 " ctrl "\n\t"
-__device__ __forceinline__ void wave_sum6(float (&x)[6])
-{
-    asm("s_nop 1\n\t" NMPC_P6("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-            NMPC_P6("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                NMPC_P6("row_half_mirror row_mask:0xf bank_mask:0xf") NMPC_P6("row_mirror row_mask:0xf bank_mask:0xf")
-                    NMPC_P6("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                        NMPC_P6("row_bcast:31 row_mask:0xc bank_mask:0xf")
-        : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]));
-#pragma unroll
-    for (int i = 0; i < 6; ++i) x[i] = read_lane(x[i], 63);
-}
-#undef NMPC_P6
-__device__ __forceinline__ void wave_sum6(double (&x)[6])
-{
-#pragma unroll
-    for (int i = 0; i < 6; ++i) x[i] = wave_sum(x[i]);
-}
 __device__ __forceinline__ void wave_sum2(double x, double y, double& sx, double& sy)
 {
     sx = wave_sum(x);
@@ -165,6 +149,9 @@ __device__ __forceinline__ void wave_sum3(double x, double y, double z, double& 
 }
 
 // Inclusive prefix sum over lanes 0..63 (lane i gets x_0 + ... + x_i).
+// Association (float and double, one value or two): in each 16-lane row Hillis-Steele, x_i += x_{i-s} for s = 1, 2, 4, 8
+// (a lane with fewer than s lanes below it in its row adds 0.0); then rows 1 and 3 += lane 15 / lane 47 (the totals of
+// rows 0 and 2), then rows 2 and 3 += lane 31 (by then r0 + r1): a lane of row 3 ends up as (p + r2) + (r0 + r1).
 __device__ __forceinline__ float wave_scan_incl(float x)
 {
     x += dpp_mov<DPP_ROW_SHR0 + 1, 0xf, 0xf, true>(0.0f, x);
@@ -208,6 +195,9 @@ __device__ __forceinline__ void wave_scan_incl2(double& x, double& y)
 
 // Inclusive suffix sum (lane i gets x_i + ... + x_63): in-row suffix with row_shl, then the totals of the rows
 // above (they sit in the first lane of each row) are added from scalar registers. No LDS crossbar involved.
+// Association: in each row x_i += x_{i+s} for s = 1, 2, 4, 8 (0.0 past the end of the row); with t1, t2, t3 the totals of
+// rows 1..3 (lanes 16, 32, 48) wave_suffix_fix_rows returns x + (t1 + (t2 + t3)) in row 0, x + (t2 + t3) in row 1,
+// x + t3 in row 2 and x + 0.0 in row 3.
 template <typename T>
 __device__ __forceinline__ T wave_suffix_fix_rows(T x)
 {
@@ -266,6 +256,8 @@ __device__ __forceinline__ void wave_scan_suffix_incl2(double& x, double& y)
 // partials of its class through the LDS crossbar (ds_bpermute, no memory touched) -- 10 instructions per value for all
 // three classes, against three masked full-wave reductions. `a[q]` = 4 * (last lane of this lane's class in row q),
 // see class3_addresses().
+// Association (class3_sum2, class3_sum1, class3_issue1 + class3_finish1, float and double): in each row x_i += x_{i-s} for
+// s = 3, 6, 12 (0.0 below the start of the row), then (x0 + x1) + (x2 + x3) of the four row partials, row 0 first.
 __device__ __forceinline__ void class3_sum2(float& x, float& y, const int (&a)[4])
 {
     asm("s_nop 0\n\t" NMPC_P2("row_shr:3 row_mask:0xf bank_mask:0xf bound_ctrl:0")
@@ -288,6 +280,8 @@ __device__ __forceinline__ void class3_sum1(T& x, const int (&a)[4])
     const T x0 = bperm(x, a[0]), x1 = bperm(x, a[1]), x2 = bperm(x, a[2]), x3 = bperm(x, a[3]);
     x = (x0 + x1) + (x2 + x3);
 }
+// The same in two halves, so that independent work can sit between the crossbar requests and their results:
+// class3_issue1() leaves the four row partials in flight, class3_finish1() adds them up.
 template <typename T>
 struct Class3Pending1 {
     T x[4];
@@ -305,51 +299,6 @@ template <typename T>
 __device__ __forceinline__ T class3_finish1(const Class3Pending1<T>& p)
 {
     return (p.x[0] + p.x[1]) + (p.x[2] + p.x[3]);
-}
-// The same in two halves, so that independent work can sit between the crossbar requests and their results (the
-// round trip is ~130 cycles; a wavefront that waits for it does not issue, and with two wavefronts per SIMD nobody else
-// takes its slots): class3_issue() leaves the eight row partials in flight, class3_finish() adds them up.
-template <typename T>
-struct Class3Pending {
-    T x[4], y[4];
-};
-__device__ __forceinline__ void class3_issue(float x, float y, const int (&a)[4], Class3Pending<float>& p)
-{
-    // (builtins here, not an asm block: with full row / bank masks the compiler folds each step into one v_add_f32_dpp
-    //  and fills the DPP wait states with the caller's independent instructions instead of s_nop)
-    auto rows = [](float v) {
-        v += dpp_mov<DPP_ROW_SHR0 + 3, 0xf, 0xf, true>(0.0f, v);
-        v += dpp_mov<DPP_ROW_SHR0 + 6, 0xf, 0xf, true>(0.0f, v);
-        v += dpp_mov<DPP_ROW_SHR0 + 12, 0xf, 0xf, true>(0.0f, v);
-        return v;
-    };
-    x = rows(x);
-    y = rows(y);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) p.x[q] = bperm(x, a[q]);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) p.y[q] = bperm(y, a[q]);
-}
-__device__ __forceinline__ void class3_issue(double x, double y, const int (&a)[4], Class3Pending<double>& p)
-{
-    auto rows = [](double v) {
-        v += dpp_mov<DPP_ROW_SHR0 + 3, 0xf, 0xf, true>(0.0, v);
-        v += dpp_mov<DPP_ROW_SHR0 + 6, 0xf, 0xf, true>(0.0, v);
-        v += dpp_mov<DPP_ROW_SHR0 + 12, 0xf, 0xf, true>(0.0, v);
-        return v;
-    };
-    x = rows(x);
-    y = rows(y);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) p.x[q] = bperm(x, a[q]);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) p.y[q] = bperm(y, a[q]);
-}
-template <typename T>
-__device__ __forceinline__ void class3_finish(const Class3Pending<T>& p, T& x, T& y)
-{
-    x = (p.x[0] + p.x[1]) + (p.x[2] + p.x[3]);
-    y = (p.y[0] + p.y[1]) + (p.y[2] + p.y[3]);
 }
 __device__ __forceinline__ void class3_sum2(double& x, double& y, const int (&a)[4])
 {
