@@ -165,6 +165,13 @@ class NmpcMmpBlock2Args(C.Structure):
     the first convolution and the projection); ``wd = None`` for the block without a projection (``Cin == 32``, stride 1)."""
     _fields_ = NmpcMmpBlockArgs._fields_ + [("stride", C.c_int32)]
 
+
+class NmpcMmpBlock3Args(C.Structure):
+    """Mirror of ``struct nmpc_mmp_block3_args`` (device pointers): one residual block of the network's layer3, ``x`` [M, Cin, H, W]
+    -> ``out`` [M, 64, H2, W2]; the fields of ``NmpcMmpBlock2Args``; ``wd = None`` for the block without a projection (``Cin == 64``,
+    stride 1)."""
+    _fields_ = NmpcMmpBlock2Args._fields_
+
 # every symbol include/nmpc_hip.h declares (checked by the CPU test-suite against the built library)
 EXPORTED_SYMBOLS = (
     "nmpc_default_config", "nmpc_layout", "nmpc_create", "nmpc_destroy", "nmpc_param_len", "nmpc_set_stream", "nmpc_use_own_stream", "nmpc_set_pointer_mode",
@@ -176,7 +183,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
-    "nmpc_mmp_block2_f32",
+    "nmpc_mmp_block2_f32", "nmpc_mmp_block3_f32",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
     "nmpc_last_error",
 )
@@ -268,6 +275,7 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     lib.nmpc_mmp_stem_shape.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.nmpc_mmp_block_f32.argtypes = [vp, C.POINTER(NmpcMmpBlockArgs)]
     lib.nmpc_mmp_block2_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock2Args)]
+    lib.nmpc_mmp_block3_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock3Args)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     lib.nmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.nmpc_kernel_info.argtypes = [vp] + [C.POINTER(i32)] * 5
@@ -506,6 +514,11 @@ class Handle:
         with ``args.stride`` = 1 or 2 on the first convolution and the projection), ``out[M, 32, H2, W2]`` from ``x[M, Cin, H, W]``,
         float32 under both dtypes, one launch enqueued on the handle's stream."""
         _check(self._lib.nmpc_mmp_block2_f32(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_block3(self, args: "NmpcMmpBlock3Args"):
+        """``nmpc_mmp_block3_f32``: one fused residual block of the network's layer3 (as ``mmp_block2``, at 64 output channels),
+        ``out[M, 64, H2, W2]`` from ``x[M, Cin, H, W]``, float32 under both dtypes, one launch enqueued on the handle's stream."""
+        _check(self._lib.nmpc_mmp_block3_f32(self._h, C.byref(args) if args is not None else None))
 
     def hypotheses_to_ellipses(self, dtype, hypos, cur, dyn_out, n_obs_out=None, human_size=0.2, eps=1.0, enlarge=2.0,
                                extra_margin=0.0):

@@ -4,14 +4,15 @@ the input stack ``[7, Hm, Wm]`` per pedestrian and time offset (``nmpc_mmp_input
 network's first layer fused with it, ``[C, Hp, Wp]`` (``nmpc_mmp_stem_*``, csrc/nmpc_mmp_stem.h) -- then, with ``blocks``, the
 residual blocks of ``layer1``, one launch each between two 16-channel buffers (``nmpc_mmp_block_f32``, csrc/nmpc_mmp_block.h),
 then, with ``blocks2``, those of ``layer2``, one launch each between two 32-channel buffers on the strided plane
-(``nmpc_mmp_block2_f32``, csrc/nmpc_mmp_block2.h). The object owns the folded weights on the device, the argument structs and
+(``nmpc_mmp_block2_f32``, csrc/nmpc_mmp_block2.h), then, with ``blocks3``, those of ``layer3``, one launch each between two
+64-channel buffers on the plane strided once more (``nmpc_mmp_block3_f32``, csrc/nmpc_mmp_block3.h). The object owns the folded weights on the device, the argument structs and
 the buffers they point to; the structs of these kernels are built nowhere else in the package."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _capi
-from .mmp_stem import BLOCK2_CHANNELS, BLOCK_CHANNELS, block2_plane, check_blocks, check_blocks2, check_spec
+from .mmp_stem import BLOCK2_CHANNELS, BLOCK3_CHANNELS, BLOCK_CHANNELS, block2_plane, check_blocks, check_blocks2, check_blocks3, check_spec
 
 _BLOCK_ARRAYS = ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
 _ABSENT = object()
@@ -19,21 +20,24 @@ _ABSENT = object()
 
 class MmpFrontEnd:
     def __init__(self, handle: _capi.Handle, dtype, device, Hm: int, Wm: int, n_off: int, transform, rescale: float, sigma: float,
-                 ref_image, stem=None, blocks=None, blocks2=None):
+                 ref_image, stem=None, blocks=None, blocks2=None, blocks3=None):
         """``dtype``: the element type of ``hist``; ``ref_image``: the float32 label image ``[Hm, Wm]`` on ``device``; ``transform``: the
         :class:`.snap.WorldTransform` between map pixels and the world of ``hist``; ``stem`` / ``blocks``: :class:`.mmp_stem.StemSpec` /
-        ``BlockSpec`` s; ``blocks2`` (needs ``blocks``): the ``Block2Spec`` s of layer2. ``fill_row``: a row of what the fill writes;
+        ``BlockSpec`` s; ``blocks2`` (needs ``blocks``): the ``Block2Spec`` s of layer2; ``blocks3`` (needs ``blocks2``): the ``Block3Spec`` s of layer3. ``fill_row``: a row of what the fill writes;
         ``row``: a row of what the network sees; ``bytes_per_item``: the buffers one pedestrian takes -- with blocks the stem's
         output and the two buffers the blocks alternate between. The two
         32-channel buffers of layer2 lie INSIDE the stem's output, which is idle once layer1's first block has read it, where they fit
-        (``2 * 32 * H2 * W2 <= C * Hp * Wp``: the 64-channel stem) and are allocated and counted otherwise."""
+        (``2 * 32 * H2 * W2 <= C * Hp * Wp``: the 64-channel stem) and are allocated and counted otherwise. The two 64-channel buffers of
+        layer3 lie behind them in the same place where everything fits (``2 * 32 * H2 * W2 + 2 * 64 * H3 * W3 <= C * Hp * Wp``) and are
+        allocated and counted otherwise."""
         import torch
-        stem, blocks, blocks2 = self.check_specs(stem, blocks, blocks2=blocks2)
+        stem, blocks, blocks2, blocks3 = self.check_specs(stem, blocks, blocks2=blocks2, blocks3=blocks3)
         self.h, self.dt, self.dev, self.n_off = handle, np.dtype(dtype), device, int(n_off)
         dev = lambda v: None if v is None else torch.as_tensor(v, device=device)
         self.stem = None if stem is None else stem._replace(weight=dev(stem.weight), scale=dev(stem.scale), shift=dev(stem.shift))
         self.blocks = None if blocks is None else tuple(b._replace(**{n: dev(getattr(b, n)) for n in _BLOCK_ARRAYS}) for b in blocks)
         self.blocks2 = None if blocks2 is None else tuple(b._replace(**{n: dev(getattr(b, n)) for n in _BLOCK_ARRAYS}) for b in blocks2)
+        self.blocks3 = None if blocks3 is None else tuple(b._replace(**{n: dev(getattr(b, n)) for n in _BLOCK_ARRAYS}) for b in blocks3)
         self.ref = ref_image
         if stem is None:
             self.fill_row = (7, int(Hm), int(Wm))
@@ -62,12 +66,32 @@ class MmpFrontEnd:
             self.row = (BLOCK2_CHANNELS,) + plane
             if not self._pp2_in_fill:
                 self.bytes_per_item += self.n_off * 2 * int(np.prod(self._pp2_row)) * 4
-        self._fill_args, self._block_args, self._block2_args, self.chunk = a, (), (), 0
+        self._pp3_in_fill = False
+        if blocks3 is not None:
+            self._planes3 = []                                   # the input plane of every layer-3 block, then the last one's output
+            for b in blocks3:
+                self._planes3.append(plane)
+                plane = block2_plane(*plane, b.stride)
+            self._planes3.append(plane)
+            self._pp3_row = (BLOCK3_CHANNELS,) + self._planes3[1]
+            self._pp3_in_fill = self._pp2_in_fill and 2 * int(np.prod(self._pp2_row)) + 2 * int(np.prod(self._pp3_row)) <= int(np.prod(self.fill_row))
+            self.row = (BLOCK3_CHANNELS,) + plane
+            if not self._pp3_in_fill:
+                self.bytes_per_item += self.n_off * 2 * int(np.prod(self._pp3_row)) * 4
+        self._fill_args, self._block_args, self._block2_args, self._block3_args, self.chunk = a, (), (), (), 0
 
     @staticmethod
-    def check_specs(stem, blocks, prefix: str = "", blocks2=_ABSENT):
+    def check_specs(stem, blocks, prefix: str = "", blocks2=_ABSENT, blocks3=_ABSENT):
         """``(stem, blocks)`` checked, either may be ``None``; ``prefix``: what the caller's argument names carry in front. With
-        ``blocks2=`` given (``None`` included): ``(stem, blocks, blocks2)``."""
+        ``blocks2=`` given (``None`` included): ``(stem, blocks, blocks2)``; with ``blocks3=`` given as well: ``(stem, blocks, blocks2,
+        blocks3)``."""
+        if blocks3 is not _ABSENT:
+            stem, blocks, blocks2 = MmpFrontEnd.check_specs(stem, blocks, prefix, blocks2=None if blocks2 is _ABSENT else blocks2)
+            if blocks3 is not None:
+                if blocks2 is None:
+                    raise ValueError(f"{prefix}blocks3 needs {prefix}blocks2 (the blocks of layer3 run on the fused layer2's output)")
+                blocks3 = check_blocks3(blocks2, blocks3)
+            return stem, blocks, blocks2, blocks3
         if blocks2 is not _ABSENT:
             stem, blocks = MmpFrontEnd.check_specs(stem, blocks, prefix)
             if blocks2 is not None:
@@ -91,7 +115,7 @@ class MmpFrontEnd:
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.dev)
         self._fill_buf = self._out = new(chunk, self.n_off, *self.fill_row)
         self._fill_args.out = self._fill_buf.data_ptr()
-        args, args2 = [], []
+        args, args2, args3 = [], [], []
         if self.blocks is not None:
             self._pp = new(2, chunk, self.n_off, BLOCK_CHANNELS, *self.fill_row[1:])
             for i, b in enumerate(self.blocks):
@@ -116,7 +140,21 @@ class MmpFrontEnd:
                 a.x, a.out = self._out.data_ptr(), self._pp2[i % 2].data_ptr()
                 self._out = self._pp2[i % 2]
                 args2.append(a)
-        self._block_args, self._block2_args, self.chunk = tuple(args), tuple(args2), chunk
+        if self.blocks3 is not None:
+            rows, n3 = chunk * self.n_off, int(np.prod(self._pp3_row))
+            # (inside the stem's output, behind layer2's two buffers)
+            behind = 2 * rows * int(np.prod(self._pp2_row))
+            self._pp3 = self._fill_buf.view(-1)[behind:behind + 2 * rows * n3].view(2, rows * n3) if self._pp3_in_fill else new(2, rows * n3)
+            for i, b in enumerate(self.blocks3):
+                a = _capi.NmpcMmpBlock3Args()
+                a.Cin, (a.H, a.W), a.stride = int(b.w1.shape[1]), self._planes3[i], b.stride
+                for name in _BLOCK_ARRAYS:
+                    setattr(a, name, None if getattr(b, name) is None else getattr(b, name).data_ptr())
+                a.slope_mid, a.slope_out = b.slope_mid, b.slope_out
+                a.x, a.out = self._out.data_ptr(), self._pp3[i % 2].data_ptr()
+                self._out = self._pp3[i % 2]
+                args3.append(a)
+        self._block_args, self._block2_args, self._block3_args, self.chunk = tuple(args), tuple(args2), tuple(args3), chunk
 
     def fill(self, hist: int, hcount: int, B: int, H: int, items, n: int):
         """The fill alone for ``n`` pedestrians: ``hist`` ``[B, H, 5, 2]`` / ``hcount`` ``[B, H]`` device pointers, ``items`` a device
@@ -130,18 +168,22 @@ class MmpFrontEnd:
 
     def run_block(self, i: int, rows: int):
         """Block ``i`` alone on the first ``rows`` rows of its input buffer (what ``fill`` or block ``i - 1`` left there). ONE index
-        space covers both stages: ``0 .. len(blocks) - 1`` are the blocks of layer1, ``len(blocks) ..`` those of layer2."""
+        space covers all stages: ``0 .. len(blocks) - 1`` are the blocks of layer1, ``len(blocks) ..`` those of layer2, then those of
+        layer3."""
         if not 0 <= rows <= self.chunk * self.n_off:
             raise ValueError(f"{rows} rows; allocate() was called for {self.chunk * self.n_off}")
-        n1 = len(self._block_args)
-        if not 0 <= i < n1 + len(self._block2_args):
-            raise IndexError(f"block {i} of {n1} + {len(self._block2_args)}")
+        n1, n2, n3 = len(self._block_args), len(self._block2_args), len(self._block3_args)
+        if not 0 <= i < n1 + n2 + n3:
+            raise IndexError(f"block {i} of {n1} + {n2}" + (f" + {n3}" if n3 else ""))
         if i < n1:
             self._block_args[i].M = rows
             self.h.mmp_block(self._block_args[i])
-        else:
+        elif i < n1 + n2:
             self._block2_args[i - n1].M = rows
             self.h.mmp_block2(self._block2_args[i - n1])
+        else:
+            self._block3_args[i - n1 - n2].M = rows
+            self.h.mmp_block3(self._block3_args[i - n1 - n2])
 
     def run_blocks(self, rows: int):
         """All blocks of layer1, one after the other, on the first ``rows`` rows of the fill's output. Returns the last one's
@@ -152,16 +194,25 @@ class MmpFrontEnd:
 
     def run_blocks2(self, rows: int):
         """All blocks of layer2, one after the other, on the first ``rows`` rows of what ``run_blocks`` left. Returns the last one's
-        ``[rows, *row]``."""
+        ``[rows, 32, H2, W2]`` (``[rows, *row]`` without blocks3)."""
         n1 = len(self._block_args)
         for i in range(len(self._block2_args)):
             self.run_block(n1 + i, rows)
+        row = (BLOCK2_CHANNELS,) + self._planes2[-1]
+        return self._pp2[(len(self._block2_args) - 1) % 2][:rows * int(np.prod(row))].view(rows, *row)
+
+    def run_blocks3(self, rows: int):
+        """All blocks of layer3, one after the other, on the first ``rows`` rows of what ``run_blocks2`` left. Returns the last one's
+        ``[rows, *row]``."""
+        n12 = len(self._block_args) + len(self._block2_args)
+        for i in range(len(self._block3_args)):
+            self.run_block(n12 + i, rows)
         return self._out.view(-1)[:rows * int(np.prod(self.row))].view(rows, *self.row)
 
     def run(self, hist: int, hcount: int, B: int, H: int, items, n: int, part=None):
         """One chunk: fill, then the blocks on its ``n * n_off`` rows (arguments as in ``fill``). ``part(name, call)``, if given,
         makes the launches in place of a plain ``call()`` and returns its result: ``"input"``, then with blocks ``"layer1"``, then with
-        blocks2 ``"layer2"``.
+        blocks2 ``"layer2"``, then with blocks3 ``"layer3"``.
         Returns the view ``[n * n_off, *row]`` the network is to be called on; the next ``run`` overwrites it."""
         part = part or (lambda name, call: call())
         x = part("input", lambda: self.fill(hist, hcount, B, H, items, n))
@@ -169,4 +220,6 @@ class MmpFrontEnd:
             x = part("layer1", lambda: self.run_blocks(n * self.n_off))
         if self._block2_args:
             x = part("layer2", lambda: self.run_blocks2(n * self.n_off))
+        if self._block3_args:
+            x = part("layer3", lambda: self.run_blocks3(n * self.n_off))
         return x

@@ -24,7 +24,13 @@ The second residual stage, ``resnet34.layer2`` = four ``BasicBlock`` s at 32 cha
 (``nmpc_mmp_block2_f32``, csrc/nmpc_mmp_block2.h): ``Block2Spec`` = ``BlockSpec`` 's fields plus ``stride`` (1 or 2, of the first
 convolution and the projection), ``fold_block2`` folds one block, ``split_network_layer2(net)`` returns the stem, the three blocks
 of layer1, the four of layer2 and the trunk from ``layer3`` on, for ``BatchEvaluator(..., mmp_stem=spec, mmp_blocks=blocks,
-mmp_blocks2=blocks2, network=trunk)`` and ``MmpInterface(trunk, stem=spec, blocks=blocks, blocks2=blocks2)``."""
+mmp_blocks2=blocks2, network=trunk)`` and ``MmpInterface(trunk, stem=spec, blocks=blocks, blocks2=blocks2)``.
+
+The third residual stage, ``resnet34.layer3`` = six ``BasicBlock`` s at 64 channels, the first ``32 -> 64`` at stride 2 with a
+1 x 1, stride-2 projection (19 x 21 from 37 x 42), goes through a third kernel family (``nmpc_mmp_block3_f32``,
+csrc/nmpc_mmp_block3.h): ``Block3Spec`` has ``Block2Spec`` 's fields, ``fold_block3`` folds one block,
+``split_network_layer3(net)`` returns the stem, the blocks of layer1, layer2 and layer3 and the trunk from ``layer4`` on, for
+``BatchEvaluator(..., mmp_blocks3=blocks3)`` and ``MmpInterface(..., blocks3=blocks3)``."""
 from __future__ import annotations
 
 from typing import Callable, NamedTuple, Optional, Tuple
@@ -72,6 +78,24 @@ class Block2Spec(NamedTuple):
 
 
 BLOCK2_CHANNELS = 32                # output channels of the fused strided block (csrc/nmpc_mmp_block2.h)
+
+
+class Block3Spec(NamedTuple):
+    w1: np.ndarray                  # [64, Cin, 3, 3] float32
+    s1: np.ndarray                  # [64] float32
+    b1: np.ndarray                  # [64] float32
+    slope_mid: float
+    w2: np.ndarray                  # [64, 64, 3, 3] float32
+    s2: np.ndarray                  # [64]
+    b2: np.ndarray                  # [64]
+    wd: Optional[np.ndarray]        # [64, Cin] float32, or None: the identity (Cin == 64 and stride == 1)
+    sd: Optional[np.ndarray]        # [64] or None
+    bd: Optional[np.ndarray]        # [64] or None
+    slope_out: float
+    stride: int                     # 1 or 2: of the first convolution and of the projection
+
+
+BLOCK3_CHANNELS = 64                # output channels of the third stage's fused block (csrc/nmpc_mmp_block3.h)
 
 
 def _pair(v):
@@ -295,12 +319,57 @@ def block2_plane(H: int, W: int, stride: int) -> Tuple[int, int]:
     return (int(H) - 1) // int(stride) + 1, (int(W) - 1) // int(stride) + 1
 
 
-def _conv2_is(name, conv, kernel, padding, stride):
+def _conv2_is(name, conv, kernel, padding, stride, fn="fold_block2"):
     if (_pair(conv.kernel_size) != (kernel, kernel) or _pair(conv.padding) != (padding, padding) or conv.groups != 1
             or _pair(conv.dilation) != (1, 1) or conv.padding_mode != "zeros"):
-        raise ValueError(f"fold_block2: '{name}' must have kernel {kernel}, padding {padding}, groups 1, dilation 1 and zero padding; got {conv}")
+        raise ValueError(f"{fn}: '{name}' must have kernel {kernel}, padding {padding}, groups 1, dilation 1 and zero padding; got {conv}")
     if _pair(conv.stride) != (stride, stride):
-        raise ValueError(f"fold_block2: '{name}' must have stride {stride}, got stride {_pair(conv.stride)}")
+        raise ValueError(f"{fn}: '{name}' must have stride {stride}, got stride {_pair(conv.stride)}")
+
+
+def _fold_strided(block, fn, C, Spec):
+    """``fold_block2`` / ``fold_block3``: one body; ``fn`` names the caller in the messages, ``C`` its output channels."""
+    for name in ("conv1", "conv2", "downsample", "leaky"):
+        if not hasattr(block, name):
+            raise ValueError(f"{fn}: the module has no {name!r}")
+    try:
+        c1, n1, act = _conv_norm("conv1", block.conv1, 3)
+        c2, n2 = _conv_norm("conv2", block.conv2, 2)
+        parts_d = None if block.downsample is None else _conv_norm("downsample", block.downsample, 2)
+    except ValueError as e:
+        raise ValueError(str(e).replace("fold_block:", f"{fn}:")) from None
+    stride = _pair(c1.stride)[0]
+    if _pair(c1.stride) not in ((1, 1), (2, 2)):
+        raise ValueError(f"{fn}: 'conv1' must have stride 1 or 2, got stride {_pair(c1.stride)}")
+    _conv2_is("conv1", c1, 3, 1, stride, fn)
+    _conv2_is("conv2", c2, 3, 1, 1, fn)
+    Cin = int(c1.in_channels)
+    if c1.out_channels != C or c2.in_channels != C or c2.out_channels != C:
+        raise ValueError(f"{fn}: the block must have {C} output channels, got {c1.out_channels} and {c2.in_channels} -> {c2.out_channels}")
+    if Cin < 8 or Cin > 256 or Cin % 8:
+        raise ValueError(f"{fn}: the block must have a multiple of 8 input channels from 8 to 256, got {Cin}")
+    try:
+        slope_mid, slope_out = _slope("conv1[2]", act), _slope("leaky", block.leaky)
+    except ValueError as e:
+        raise ValueError(str(e).replace("fold_block:", f"{fn}:")) from None
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    wd = sd = bd = None
+    if parts_d is not None:
+        cd, nd = parts_d
+        if _pair(cd.stride) != _pair(c1.stride):
+            raise ValueError(f"{fn}: mismatched strides: 'conv1' has stride {_pair(c1.stride)}, 'downsample' {_pair(cd.stride)}")
+        _conv2_is("downsample", cd, 1, 0, stride, fn)
+        if cd.in_channels != Cin or cd.out_channels != C:
+            raise ValueError(f"{fn}: 'downsample' must be {Cin} -> {C}, got {cd.in_channels} -> {cd.out_channels}")
+        wd, sd, bd = fold_doubles(cd, nd)
+        wd, sd, bd = f32(wd.reshape(C, Cin)), f32(sd), f32(bd)
+    elif stride != 1:
+        raise ValueError(f"{fn}: a block at stride 2 without 'downsample' has no identity of the output's shape to add")
+    elif Cin != C:
+        raise ValueError(f"{fn}: a block {Cin} -> {C} without 'downsample' has no identity to add")
+    w1, s1, b1 = fold_doubles(c1, n1)
+    w2, s2, b2 = fold_doubles(c2, n2)
+    return Spec(f32(w1), f32(s1), f32(b1), slope_mid, f32(w2), f32(s2), f32(b2), wd, sd, bd, slope_out, int(stride))
 
 
 def fold_block2(block) -> Block2Spec:
@@ -308,53 +377,16 @@ def fold_block2(block) -> Block2Spec:
     LeakyReLU)``, ``conv2 = Sequential(Conv2d 3 x 3, BatchNorm2d)``, ``downsample = None | Sequential(Conv2d 1 x 1 at conv1's stride,
     BatchNorm2d)``, ``leaky = LeakyReLU`` -- with 32 output channels -> :class:`Block2Spec`, folded in float64 (``fold_doubles``) and
     rounded once; ``ValueError`` for anything the kernel does not compute."""
-    for name in ("conv1", "conv2", "downsample", "leaky"):
-        if not hasattr(block, name):
-            raise ValueError(f"fold_block2: the module has no {name!r}")
-    try:
-        c1, n1, act = _conv_norm("conv1", block.conv1, 3)
-        c2, n2 = _conv_norm("conv2", block.conv2, 2)
-        parts_d = None if block.downsample is None else _conv_norm("downsample", block.downsample, 2)
-    except ValueError as e:
-        raise ValueError(str(e).replace("fold_block:", "fold_block2:")) from None
-    stride = _pair(c1.stride)[0]
-    if _pair(c1.stride) not in ((1, 1), (2, 2)):
-        raise ValueError(f"fold_block2: 'conv1' must have stride 1 or 2, got stride {_pair(c1.stride)}")
-    _conv2_is("conv1", c1, 3, 1, stride)
-    _conv2_is("conv2", c2, 3, 1, 1)
-    C, Cin = BLOCK2_CHANNELS, int(c1.in_channels)
-    if c1.out_channels != C or c2.in_channels != C or c2.out_channels != C:
-        raise ValueError(f"fold_block2: the block must have {C} output channels, got {c1.out_channels} and {c2.in_channels} -> {c2.out_channels}")
-    if Cin < 8 or Cin > 256 or Cin % 8:
-        raise ValueError(f"fold_block2: the block must have a multiple of 8 input channels from 8 to 256, got {Cin}")
-    try:
-        slope_mid, slope_out = _slope("conv1[2]", act), _slope("leaky", block.leaky)
-    except ValueError as e:
-        raise ValueError(str(e).replace("fold_block:", "fold_block2:")) from None
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    wd = sd = bd = None
-    if parts_d is not None:
-        cd, nd = parts_d
-        if _pair(cd.stride) != _pair(c1.stride):
-            raise ValueError(f"fold_block2: mismatched strides: 'conv1' has stride {_pair(c1.stride)}, 'downsample' {_pair(cd.stride)}")
-        _conv2_is("downsample", cd, 1, 0, stride)
-        if cd.in_channels != Cin or cd.out_channels != C:
-            raise ValueError(f"fold_block2: 'downsample' must be {Cin} -> {C}, got {cd.in_channels} -> {cd.out_channels}")
-        wd, sd, bd = fold_doubles(cd, nd)
-        wd, sd, bd = f32(wd.reshape(C, Cin)), f32(sd), f32(bd)
-    elif stride != 1:
-        raise ValueError("fold_block2: a block at stride 2 without 'downsample' has no identity of the output's shape to add")
-    elif Cin != C:
-        raise ValueError(f"fold_block2: a block {Cin} -> {C} without 'downsample' has no identity to add")
-    w1, s1, b1 = fold_doubles(c1, n1)
-    w2, s2, b2 = fold_doubles(c2, n2)
-    return Block2Spec(f32(w1), f32(s1), f32(b1), slope_mid, f32(w2), f32(s2), f32(b2), wd, sd, bd, slope_out, int(stride))
+    return _fold_strided(block, "fold_block2", BLOCK2_CHANNELS, Block2Spec)
 
 
-def check_block2(spec) -> Block2Spec:
-    """``spec`` with contiguous float32 arrays of consistent shapes and a stride of 1 or 2 (``ValueError`` otherwise)."""
+def fold_block3(block) -> Block3Spec:
+    """As ``fold_block2`` for a block with 64 output channels -> :class:`Block3Spec`: the same fold in float64, the same refusals."""
+    return _fold_strided(block, "fold_block3", BLOCK3_CHANNELS, Block3Spec)
+
+
+def _check_strided(spec, C, Spec):
     f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    C = BLOCK2_CHANNELS
     w1, s1, b1, w2, s2, b2 = (f32(v) for v in (spec.w1, spec.s1, spec.b1, spec.w2, spec.s2, spec.b2))
     Cin = w1.shape[1] if w1.ndim == 4 else -1
     stride = spec.stride
@@ -369,13 +401,23 @@ def check_block2(spec) -> Block2Spec:
         ok = not any(proj) and Cin == C and int(stride) == 1
     if not ok:
         shp = lambda v: None if v is None else np.shape(v)
-        raise ValueError(f"Block2Spec: w1 {w1.shape}, s1 {s1.shape}, b1 {b1.shape}, w2 {w2.shape}, s2 {s2.shape}, b2 {b2.shape}, wd {shp(spec.wd)}, "
-                         f"sd {shp(spec.sd)}, bd {shp(spec.bd)}, stride {stride!r}; expected [32, Cin, 3, 3], [32], [32], [32, 32, 3, 3], [32], [32] "
-                         "with Cin a multiple of 8 from 8 to 256, stride 1 or 2, and [32, Cin], [32], [32] or three None (Cin = 32, stride 1)")
+        raise ValueError(f"{Spec.__name__}: w1 {w1.shape}, s1 {s1.shape}, b1 {b1.shape}, w2 {w2.shape}, s2 {s2.shape}, b2 {b2.shape}, wd {shp(spec.wd)}, "
+                         f"sd {shp(spec.sd)}, bd {shp(spec.bd)}, stride {stride!r}; expected [{C}, Cin, 3, 3], [{C}], [{C}], [{C}, {C}, 3, 3], [{C}], [{C}] "
+                         f"with Cin a multiple of 8 from 8 to 256, stride 1 or 2, and [{C}, Cin], [{C}], [{C}] or three None (Cin = {C}, stride 1)")
     for name in ("slope_mid", "slope_out"):
         if not np.isfinite(float(getattr(spec, name))) or abs(float(getattr(spec, name))) > 1.0:
-            raise ValueError(f"Block2Spec: {name} = {getattr(spec, name)}")
-    return Block2Spec(w1, s1, b1, float(spec.slope_mid), w2, s2, b2, wd, sd, bd, float(spec.slope_out), int(stride))
+            raise ValueError(f"{Spec.__name__}: {name} = {getattr(spec, name)}")
+    return Spec(w1, s1, b1, float(spec.slope_mid), w2, s2, b2, wd, sd, bd, float(spec.slope_out), int(stride))
+
+
+def check_block2(spec) -> Block2Spec:
+    """``spec`` with contiguous float32 arrays of consistent shapes and a stride of 1 or 2 (``ValueError`` otherwise)."""
+    return _check_strided(spec, BLOCK2_CHANNELS, Block2Spec)
+
+
+def check_block3(spec) -> Block3Spec:
+    """As ``check_block2``, at 64 output channels."""
+    return _check_strided(spec, BLOCK3_CHANNELS, Block3Spec)
 
 
 def check_blocks2(blocks, blocks2) -> Tuple[Block2Spec, ...]:
@@ -416,3 +458,43 @@ def split_network_layer2(net) -> Tuple[StemSpec, Tuple[BlockSpec, ...], Tuple[Bl
             x = layer(x)
         return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
     return spec, blocks, blocks2, trunk
+
+
+def check_blocks3(blocks2, blocks3) -> Tuple[Block3Spec, ...]:
+    """The layer-3 blocks behind the (checked) layer-2 ``blocks2`` as a tuple of checked specs: the first takes the 32 channels layer2
+    gives, each later one is 64 -> 64."""
+    if not blocks2:
+        raise ValueError("mmp_blocks3: the blocks of layer2 are needed in front")
+    blocks3 = tuple(check_block3(b) for b in blocks3)
+    if not blocks3:
+        raise ValueError("mmp_blocks3: at least one Block3Spec is needed")
+    cin = BLOCK2_CHANNELS
+    for i, b in enumerate(blocks3):
+        if b.w1.shape[1] != cin:
+            raise ValueError(f"mmp_blocks3: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive "
+                             f"({'layer2 gives 32' if i == 0 else 'every block of layer3 gives 64'})")
+        cin = BLOCK3_CHANNELS
+    return blocks3
+
+
+def split_network_layer3(net) -> Tuple[StemSpec, Tuple[BlockSpec, ...], Tuple[Block2Spec, ...], Tuple[Block3Spec, ...], Callable]:
+    """As ``split_network_layer2``, with ``resnet34.layer3`` (six blocks, ``fold_block3``) taken off the trunk as well:
+    ``(StemSpec, blocks, blocks2, blocks3, trunk)``; the trunk, a callable on ``[M, 64, H3, W3]``, is ``layer4``, ``apool``,
+    flatten, ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
+    spec, blocks, blocks2, _ = split_network_layer2(net)
+    body = net.resnet34
+    try:
+        l3 = list(body.layer3)
+    except TypeError:
+        l3 = []
+    if len(l3) != 6:
+        raise ValueError("split_network_layer3: 'resnet34.layer3' is not a Sequential of six blocks")
+    blocks3 = check_blocks3(blocks2, [fold_block3(b) for b in l3])
+    layers = [getattr(body, n) for n in ("layer4", "apool")]
+    fc1, leaky, swarm = net.fc1, net.leaky, net.swarm
+
+    def trunk(x):
+        for layer in layers:
+            x = layer(x)
+        return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
+    return spec, blocks, blocks2, blocks3, trunk

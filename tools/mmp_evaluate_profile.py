@@ -30,8 +30,15 @@ trunk from layer2 on in torch); the new path hands the second residual stage (fo
 above, with HIP events around ``input``, ``layer1``, ``layer2``, ``network`` and the whole stage. Beside them: torch's own layer2,
 eager, alone on one chunk of the parent path's layer1 output, and the four launches alone on one chunk as fma per second against
 the fp32 peak and bytes per second against the copy rate, next to the model of csrc/nmpc_mmp_block2.h.
+
+``--fused-layer3``: and once more. The parent path is the new path of ``--fused-layer2`` (trunk from layer3 on in torch); the new
+path hands the third residual stage (six blocks at 64 channels, the first at stride 2, ``mmp_stem.fold_block3`` ->
+``nmpc_mmp_block3_f32``) to the device stage as well and keeps the trunk from layer4 on. Alternated as above, with HIP events
+around ``input``, ``layer1``, ``layer2``, ``layer3``, ``network`` and the whole stage. Measured first: torch's own layer3, eager,
+alone on one chunk of the parent path's layer2 output; then the six launches alone on that chunk, next to the model of
+csrc/nmpc_mmp_block3.h.
    usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]
-          [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS]]      (defaults 256 3 f32 4 20; 3)"""
+          [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS]]      (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
 import sys
@@ -306,29 +313,55 @@ def torch_layer2_alone(ev, layer2, n_item, reps=5):
     return dict(items=n_item, samples=rows, **t)
 
 
-def block2_kernel_rate(ev, n_item, reps=10):
-    """The four nmpc_mmp_block2_f32 launches alone on the layer1 output of ``n_item`` pedestrians: ms each and together, useful fma
-    per second (32 (9 Cin + 9 32 (+ Cin)) per output pixel) and bytes per second (x read once, out written once)."""
-    fe = ev.mmp_front
-    rows = _fill(ev, n_item)().shape[0]
-    fe.run_blocks(rows)
-    n1, (H, W) = len(fe.blocks), fe.fill_row[1:]
-    rec = {"items": n_item, "rows": rows, "blocks": []}
+def _strided_kernel_rate(fe, rows, reps, blocks, C, first, plane, run_all):
+    """The launches of one strided stage (``blocks`` at ``C`` output channels, ``run_block(first ..)``, input plane ``plane``) alone
+    on ``rows`` rows of what the stage in front left: ms each and together, useful fma per second (C (9 Cin + 9 C (+ Cin)) per
+    output pixel) and bytes per second (x read once, out written once)."""
+    H, W = plane
+    rec = {"rows": rows, "blocks": []}
     fma_all = bytes_all = 0
-    for i, b in enumerate(fe.blocks2):
+    for i, b in enumerate(blocks):
         Cin, proj, s = int(b.w1.shape[1]), b.wd is not None, int(b.stride)
         H2, W2 = (H - 1) // s + 1, (W - 1) // s + 1
-        fma = rows * H2 * W2 * 32 * (9 * Cin + 9 * 32 + (Cin if proj else 0))
-        nbytes = rows * 4 * (Cin * H * W + 32 * H2 * W2)
-        t = _timed(lambda: fe.run_block(n1 + i, rows), reps, warm=3)
+        fma = rows * H2 * W2 * C * (9 * Cin + 9 * C + (Cin if proj else 0))
+        nbytes = rows * 4 * (Cin * H * W + C * H2 * W2)
+        t = _timed(lambda: fe.run_block(first + i, rows), reps, warm=3)
         rec["blocks"].append(dict(Cin=Cin, stride=s, projection=proj, plane_in=[H, W], plane_out=[H2, W2], fma=fma, bytes=nbytes,
                                   TFMAps_median=fma / t["ms_median"] * 1e-9, share_of_fp32_peak=fma / t["ms_median"] * 1e-9 / PEAK_TFMAS,
                                   GBps_median=nbytes / t["ms_median"] * 1e-6, share_of_copy_rate=nbytes / t["ms_median"] * 1e-9 / COPY_TBS, **t))
         fma_all, bytes_all, H, W = fma_all + fma, bytes_all + nbytes, H2, W2
-    t = _timed(lambda: fe.run_blocks2(rows), reps, warm=3)
+    t = _timed(lambda: run_all(rows), reps, warm=3)
     rec.update(fma=fma_all, bytes=bytes_all, TFMAps_median=fma_all / t["ms_median"] * 1e-9, share_of_fp32_peak=fma_all / t["ms_median"] * 1e-9 / PEAK_TFMAS,
                GBps_median=bytes_all / t["ms_median"] * 1e-6, share_of_copy_rate=bytes_all / t["ms_median"] * 1e-9 / COPY_TBS, **t)
     return rec
+
+
+def block2_kernel_rate(ev, n_item, reps=10):
+    """The four nmpc_mmp_block2_f32 launches alone on the layer1 output of ``n_item`` pedestrians (``_strided_kernel_rate``)."""
+    fe = ev.mmp_front
+    rows = _fill(ev, n_item)().shape[0]
+    fe.run_blocks(rows)
+    return {"items": n_item, **_strided_kernel_rate(fe, rows, reps, fe.blocks2, 32, len(fe.blocks), fe.fill_row[1:], fe.run_blocks2)}
+
+
+def torch_layer3_alone(ev, layer3, n_item, reps=5):
+    """ms of torch's own layer3 (six blocks, eager) on the layer2 output of ``n_item`` pedestrians: one chunk of the parent path."""
+    fe = ev.mmp_front
+    rows = _fill(ev, n_item)().shape[0]
+    fe.run_blocks(rows)
+    x = fe.run_blocks2(rows)
+    with torch.no_grad():
+        t = _timed(lambda: layer3(x), reps)
+    return dict(items=n_item, samples=rows, **t)
+
+
+def block3_kernel_rate(ev, n_item, reps=10):
+    """The six nmpc_mmp_block3_f32 launches alone on the layer2 output of ``n_item`` pedestrians (``_strided_kernel_rate``)."""
+    fe = ev.mmp_front
+    rows = _fill(ev, n_item)().shape[0]
+    fe.run_blocks(rows)
+    plane = tuple(fe.run_blocks2(rows).shape[2:])
+    return {"items": n_item, **_strided_kernel_rate(fe, rows, reps, fe.blocks3, 64, len(fe.blocks) + len(fe.blocks2), plane, fe.run_blocks3)}
 
 
 def fused_layer2_main(out_path, B, steps, dt, n_ped, K, reps):
@@ -409,8 +442,88 @@ def fused_layer2_main(out_path, B, steps, dt, n_ped, K, reps):
                                           "block2_kernels_over_torch_layer2", "block2_kernels_over_model")}))
 
 
+MODEL3 = {"rows": 20480, "mfma_pipe_never_waits": 69.0, "useful_fma_at_fp32_peak": 44.3, "bytes_at_copy_rate": 4.3}   # csrc/nmpc_mmp_block3.h
+
+
+def fused_layer3_main(out_path, B, steps, dt, n_ped, K, reps):
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import fold_block, fold_block2, fold_block3, fold_stem
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    # the split, by hand, as in fused_layer2_main: net[2 .. 4] = layer1, net[5 .. 8] = layer2, net[9 .. 14] = layer3; the rest is the trunk
+    spec = fold_stem(net[0][0], net[0][1], net[0][2], net[1])
+    as_block = lambda b: SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)
+    blocks = tuple(fold_block(as_block(b)) for b in list(net)[2:5])
+    blocks2 = tuple(fold_block2(as_block(b)) for b in list(net)[5:9])
+    blocks3 = tuple(fold_block3(as_block(b)) for b in list(net)[9:15])
+    layer3, trunk3, trunk4 = torch.nn.Sequential(*list(net)[9:15]), torch.nn.Sequential(*list(net)[9:]), torch.nn.Sequential(*list(net)[15:])
+    paths = {"parent": dict(network=lambda x: trunk3(x) + 150.0, mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2),
+             "fused": dict(network=lambda x: trunk4(x) + 150.0, mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, mmp_blocks3=blocks3)}
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rows_step = B * n_ped * nm.default_config_struct().N_hor
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage: the parent path (fused first layer + "
+                   "fused layer1 + fused layer2 + trunk from layer3 on in torch) and the same with layer3 fused as well + trunk from layer4 on, "
+                   "alternated in one process; random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS, "fp32_peak_TFMAps": PEAK_TFMAS},
+           "model_of_the_header_per_lock_step_ms": MODEL3, "chunk_pedestrians": {}, "runs": {"parent": [], "fused": []}}
+    for path in paths:                                      # warm-up; torch's layer3 alone (the parent path) comes first
+        ev = evaluator(path)
+        rec["chunk_pedestrians"][path] = ev.mmp_chunk
+        try:
+            if path == "fused":
+                rec["block3_kernels"] = block3_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped))
+            else:
+                rec["torch_layer3_alone"] = torch_layer3_alone(ev, layer3, min(ev.mmp_chunk, B * n_ped))
+            ev.run(max_steps=1)
+        finally:
+            ev.close()
+        print(json.dumps({k: rec[k] for k in ("block3_kernels", "torch_layer3_alone") if k in rec}), flush=True)
+        with open(out_path, "w") as f:
+            json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = {"parent": ("input", "layer1", "layer2", "network"), "fused": ("input", "layer1", "layer2", "layer3", "network")}
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names[p]},
+                                              behind_layer2=med(p, lambda s, p=p: sum(s[k] for k in names[p][3:])),
+                                              stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    m = rec["median_per_lock_step_ms"]
+    rec["fused_layer3_over_parent"] = m["fused"]["stage"] / m["parent"]["stage"]
+    # torch's layer3 alone on one chunk, scaled to the rows of a lock-step: its share of the parent's network time; and the six
+    # block launches alone, scaled alike, against the header's model
+    tl, bk = rec["torch_layer3_alone"], rec["block3_kernels"]
+    rec["torch_layer3_per_lock_step_ms"] = tl["ms_median"] * (rows_step / tl["samples"])
+    rec["torch_layer3_share_of_parent_network"] = rec["torch_layer3_per_lock_step_ms"] / m["parent"]["network"]
+    rec["block3_kernels_per_lock_step_ms"] = bk["ms_median"] * (rows_step / bk["rows"])
+    rec["block3_kernels_over_torch_layer3"] = rec["block3_kernels_per_lock_step_ms"] / rec["torch_layer3_per_lock_step_ms"]
+    rec["block3_kernels_over_model"] = rec["block3_kernels_per_lock_step_ms"] * (20480 / rows_step) / MODEL3["mfma_pipe_never_waits"]
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "fused_layer3_over_parent", "torch_layer3_per_lock_step_ms",
+                                          "torch_layer3_share_of_parent_network", "block3_kernels_per_lock_step_ms",
+                                          "block3_kernels_over_torch_layer3", "block3_kernels_over_model")}))
+
+
 def main():
-    for flag, run in (("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+    for flag, run in (("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
         if flag in sys.argv:
             i = sys.argv.index(flag)
             reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
