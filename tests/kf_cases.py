@@ -60,10 +60,12 @@ def matrices(kind, rng):
 
 
 def fuzz_group(g):
-    """-> dict(dims, mats (A, C, Q, R), state, run): one call. Per pedestrian kf_len is drawn from {0, 1, 2, 3, cap - 1,
-    cap} (what fits into cap) and hcount = kf_len + {0, 1, 2}; the rows of kf_traj beyond kf_len hold SENTINEL."""
-    d = dict(FUZZ_GROUPS[g])
-    rng = np.random.default_rng([FUZZ_SEED, g])
+    """-> dict(dims, mats (A, C, Q, R), state, run): one call; ``g`` is an index into FUZZ_GROUPS, or a group of the same form
+    with a ``seed`` of its own (what other test modules use for shapes the fuzz set does not hold). Per pedestrian kf_len is
+    drawn from {0, 1, 2, 3, cap - 1, cap} (what fits into cap) and hcount = kf_len + {0, 1, 2}; the rows of kf_traj beyond
+    kf_len hold SENTINEL."""
+    d = dict(g) if isinstance(g, dict) else dict(FUZZ_GROUPS[g])
+    rng = np.random.default_rng([FUZZ_SEED, d.pop("seed") if isinstance(g, dict) else g])
     B, H, cap = d["B"], d["H"], d["cap"]
     A, C, Q, R = matrices(d["mats"], rng)
     lens = sorted({n for n in (0, 1, 2, 3, cap - 1, cap) if n <= cap})
