@@ -172,6 +172,23 @@ class NmpcMmpBlock3Args(C.Structure):
     stride 1)."""
     _fields_ = NmpcMmpBlock2Args._fields_
 
+
+class NmpcMmpBlock4Args(C.Structure):
+    """Mirror of ``struct nmpc_mmp_block4_args`` (device pointers): one residual block of the network's layer4, ``x`` [M, Cin, H, W]
+    -> ``out`` [M, 128, H2, W2]; the fields of ``NmpcMmpBlock3Args``; ``wd = None`` for the block without a projection (``Cin == 128``,
+    stride 1)."""
+    _fields_ = NmpcMmpBlock3Args._fields_
+
+
+class NmpcMmpHeadArgs(C.Structure):
+    """Mirror of ``struct nmpc_mmp_head_args`` (device pointers): the network's end, ``x`` [M, C, H, W] -> ``out`` [M, O] through the
+    2 x 2 average pool, ``w1`` [128, F], ``c1`` [128], the slope, ``w2`` [O, 128] and ``c2`` [O]."""
+    _fields_ = [("M", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("O", C.c_int32),
+                ("x", C.c_void_p), ("w1", C.c_void_p), ("c1", C.c_void_p), ("w2", C.c_void_p), ("c2", C.c_void_p),
+                ("slope", C.c_float), ("out", C.c_void_p)]
+
+MMP_HEAD_ROWS = 16                  # rows of the batch per workgroup of nmpc_mmp_head_f32 (kHeadRows, csrc/nmpc_mmp_head.h)
+
 # every symbol include/nmpc_hip.h declares (checked by the CPU test-suite against the built library)
 EXPORTED_SYMBOLS = (
     "nmpc_default_config", "nmpc_layout", "nmpc_create", "nmpc_destroy", "nmpc_param_len", "nmpc_set_stream", "nmpc_use_own_stream", "nmpc_set_pointer_mode",
@@ -183,7 +200,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
-    "nmpc_mmp_block2_f32", "nmpc_mmp_block3_f32",
+    "nmpc_mmp_block2_f32", "nmpc_mmp_block3_f32", "nmpc_mmp_block4_f32", "nmpc_mmp_head_f32",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
     "nmpc_last_error",
 )
@@ -276,6 +293,8 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     lib.nmpc_mmp_block_f32.argtypes = [vp, C.POINTER(NmpcMmpBlockArgs)]
     lib.nmpc_mmp_block2_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock2Args)]
     lib.nmpc_mmp_block3_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock3Args)]
+    lib.nmpc_mmp_block4_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock4Args)]
+    lib.nmpc_mmp_head_f32.argtypes = [vp, C.POINTER(NmpcMmpHeadArgs)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     lib.nmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.nmpc_kernel_info.argtypes = [vp] + [C.POINTER(i32)] * 5
@@ -519,6 +538,16 @@ class Handle:
         """``nmpc_mmp_block3_f32``: one fused residual block of the network's layer3 (as ``mmp_block2``, at 64 output channels),
         ``out[M, 64, H2, W2]`` from ``x[M, Cin, H, W]``, float32 under both dtypes, one launch enqueued on the handle's stream."""
         _check(self._lib.nmpc_mmp_block3_f32(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_block4(self, args: "NmpcMmpBlock4Args"):
+        """``nmpc_mmp_block4_f32``: one fused residual block of the network's layer4 (as ``mmp_block3``, at 128 output channels),
+        ``out[M, 128, H2, W2]`` from ``x[M, Cin, H, W]``, float32 under both dtypes, one launch enqueued on the handle's stream."""
+        _check(self._lib.nmpc_mmp_block4_f32(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_head(self, args: "NmpcMmpHeadArgs"):
+        """``nmpc_mmp_head_f32``: the network's end -- 2 x 2 average pool, flatten, ``Linear(F, 128)``, the slope, ``Linear(128, O)`` --
+        ``out[M, O]`` from ``x[M, C, H, W]``, float32 under both dtypes, one launch enqueued on the handle's stream."""
+        _check(self._lib.nmpc_mmp_head_f32(self._h, C.byref(args) if args is not None else None))
 
     def hypotheses_to_ellipses(self, dtype, hypos, cur, dyn_out, n_obs_out=None, human_size=0.2, eps=1.0, enlarge=2.0,
                                extra_margin=0.0):

@@ -31,6 +31,8 @@
 #include "nmpc_mmp_block.h"
 #include "nmpc_mmp_block2.h"
 #include "nmpc_mmp_block3.h"
+#include "nmpc_mmp_block4.h"
+#include "nmpc_mmp_head.h"
 
 using namespace nmpc_plan;
 
@@ -1854,6 +1856,104 @@ int mmp_block3(nmpc_handle_s* h, const nmpc_mmp_block3_args* g)
     return 0;
 }
 
+int mmp_block4(nmpc_handle_s* h, const nmpc_mmp_block4_args* g)
+{
+    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if (g->M < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: M = %d < 0", g->M);
+    if (g->H < 1 || g->W < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: plane %d x %d", g->H, g->W);
+    if (g->stride != 1 && g->stride != 2) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: stride = %d is neither 1 nor 2", g->stride);
+    if (g->Cin < 8 || g->Cin > 256 || g->Cin % 8)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: Cin = %d is no multiple of 8 from 8 to 256", g->Cin);
+    if (!g->wd && (g->Cin != nmpc::kB4C || g->stride != 1))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: Cin = %d, stride = %d without a projection (the identity needs Cin = 128 and stride 1)",
+                    g->Cin, g->stride);
+    if (!std::isfinite(g->slope_mid) || !std::isfinite(g->slope_out) || std::fabs(g->slope_mid) > 1.0f || std::fabs(g->slope_out) > 1.0f)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: slope_mid = %g, slope_out = %g (finite, |slope| <= 1)", (double)g->slope_mid,
+                    (double)g->slope_out);
+    if (!g->x || !g->w1 || !g->s1 || !g->b1 || !g->w2 || !g->s2 || !g->b2 || (g->wd && (!g->sd || !g->bd)) || !g->out)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: a required array is NULL");
+    if (reinterpret_cast<uintptr_t>(g->out) % 4 || reinterpret_cast<uintptr_t>(g->x) % 4)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: x or out is not aligned to float");
+    if (g->M == 0) return 0;
+    // (the kernel's pixel coordinates are ints: 2 (tile origin + 11) + 1 must not wrap)
+    if (g->H > (1 << 30) || g->W > (1 << 30)) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block4: plane %d x %d over 2^30", g->H, g->W);
+    nmpc::MmpBlock4Params p;
+    std::memset(&p, 0, sizeof p);
+    p.H2 = (g->H - 1) / g->stride + 1, p.W2 = (g->W - 1) / g->stride + 1;
+    // (a side that fits the tile's plane of m is one tile without a halo; a longer one is cut with a halo of one)
+    const long long ty = nmpc::mmp_b4_tiles(p.H2, nmpc::kB4MH), tx = nmpc::mmp_b4_tiles(p.W2, nmpc::kB4MW);
+    p.oy = p.H2 <= nmpc::kB4MH ? 1 : 2, p.ox = p.W2 <= nmpc::kB4MW ? 1 : 2;
+    const long long tiles = ty * tx; // < 2^56
+    if (tiles > 0x7fffffffLL || tiles * g->M > 0x7fffffffLL) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block4: %lld x %d workgroups", tiles, g->M);
+    const long long groups = tiles * g->M;
+    p.ty = (int)ty, p.tx = (int)tx;
+    // out must not overlap x: a tile's halo is read after the neighbouring tiles have been written
+    // (H2 W2 M <= 110 x 2^31 after the test above, H W <= 4 H2 W2: no overflow)
+    const unsigned long long xb = (unsigned long long)g->H * g->W * g->M * 4 * g->Cin, ob = (unsigned long long)p.H2 * p.W2 * g->M * 4 * nmpc::kB4C;
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(g->x), o0 = reinterpret_cast<uintptr_t>(g->out);
+    if (x0 < o0 + ob && o0 < x0 + xb) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: out overlaps x");
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    // (a host pointer here would fault inside the kernel)
+    if (h->ptr_mode != NMPC_PTR_DEVICE) {
+        const void* ptrs[] = {g->x, g->w1, g->s1, g->b1, g->w2, g->s2, g->b2, g->out, g->wd, g->sd, g->bd};
+        for (int i = 0; i < (g->wd ? 11 : 8); ++i)
+            if (!is_device_ptr(ptrs[i])) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: every array must be a device pointer");
+    }
+    p.M = g->M, p.Cin = g->Cin, p.H = g->H, p.W = g->W;
+    p.x = g->x, p.w1 = g->w1, p.s1 = g->s1, p.b1 = g->b1, p.w2 = g->w2, p.s2 = g->s2, p.b2 = g->b2;
+    p.wd = g->wd, p.sd = g->sd, p.bd = g->bd, p.slope_mid = g->slope_mid, p.slope_out = g->slope_out, p.out = g->out;
+    const dim3 grid((unsigned)groups), block(nmpc::kB4Threads);
+    if (g->stride == 2)
+        hipLaunchKernelGGL((nmpc::mmp_blk4_kernel<2, true>), grid, block, 0, h->stream, p);
+    else if (g->wd)
+        hipLaunchKernelGGL((nmpc::mmp_blk4_kernel<1, true>), grid, block, 0, h->stream, p);
+    else
+        hipLaunchKernelGGL((nmpc::mmp_blk4_kernel<1, false>), grid, block, 0, h->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mmp_head(nmpc_handle_s* h, const nmpc_mmp_head_args* g)
+{
+    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if (g->M < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: M = %d < 0", g->M);
+    if (g->H < 2 || g->W < 2) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: plane %d x %d has no 2 x 2 window", g->H, g->W);
+    if (g->C < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: C = %d < 1", g->C);
+    if (g->O < 2 || g->O > 512 || g->O % 2) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: O = %d is no even number from 2 to 512", g->O);
+    if (!std::isfinite(g->slope) || std::fabs(g->slope) > 1.0f)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: slope = %g (finite, |slope| <= 1)", (double)g->slope);
+    if (!g->x || !g->w1 || !g->c1 || !g->w2 || !g->c2 || !g->out) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: a required array is NULL");
+    {
+        const void* ptrs[] = {g->x, g->w1, g->c1, g->w2, g->c2, g->out};
+        for (const void* q : ptrs)
+            if (reinterpret_cast<uintptr_t>(q) % 4) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: an array is not aligned to float");
+    }
+    if (g->M == 0) return 0;
+    // (the kernel's feature index is an int)
+    const long long F = (long long)g->C * (g->H / 2) * (long long)(g->W / 2);
+    if (g->H > (1 << 30) || g->W > (1 << 30) || F > (1 << 24)) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_head: %lld features over 2^24", F);
+    // out must not overlap x: a group's rows of out are written while other groups read theirs of x
+    // (C H W <= 9 F <= 9 x 2^24 after the test above: no overflow)
+    const unsigned long long xb = (unsigned long long)g->C * g->H * g->W * 4 * g->M, ob = (unsigned long long)g->O * 4 * g->M;
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(g->x), o0 = reinterpret_cast<uintptr_t>(g->out);
+    if (x0 < o0 + ob && o0 < x0 + xb) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: out overlaps x");
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    // (a host pointer here would fault inside the kernel)
+    if (h->ptr_mode != NMPC_PTR_DEVICE) {
+        const void* ptrs[] = {g->x, g->w1, g->c1, g->w2, g->c2, g->out};
+        for (const void* q : ptrs)
+            if (!is_device_ptr(q)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_head: every array must be a device pointer");
+    }
+    nmpc::MmpHeadParams p;
+    std::memset(&p, 0, sizeof p);
+    p.M = g->M, p.C = g->C, p.H = g->H, p.W = g->W, p.O = g->O, p.F = (int)F;
+    p.x = g->x, p.w1 = g->w1, p.c1 = g->c1, p.w2 = g->w2, p.c2 = g->c2, p.slope = g->slope, p.out = g->out;
+    const dim3 grid((unsigned)(((long long)g->M + nmpc::kHeadRows - 1) / nmpc::kHeadRows)), block(nmpc::kHeadThreads);
+    hipLaunchKernelGGL(nmpc::mmp_head_kernel, grid, block, 0, h->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // largest nv * nw a scenario's window can give: per axis the window is at most min(range, 2 acc ts) wide and np.arange's
 // count is ceil of a quotient that rounding can lift past an integer, so floor(...) + 1 (host only)
 static long long dwa_axis_bound(double range, double acc, double ts, double res)
@@ -2314,6 +2414,8 @@ int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_s
 int nmpc_mmp_block_f32(nmpc_handle h, const nmpc_mmp_block_args* a) { return mmp_block(h, a); }
 int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return mmp_block2(h, a); }
 int nmpc_mmp_block3_f32(nmpc_handle h, const nmpc_mmp_block3_args* a) { return mmp_block3(h, a); }
+int nmpc_mmp_block4_f32(nmpc_handle h, const nmpc_mmp_block4_args* a) { return mmp_block4(h, a); }
+int nmpc_mmp_head_f32(nmpc_handle h, const nmpc_mmp_head_args* a) { return mmp_head(h, a); }
 int nmpc_mmp_stem_shape(int32_t Hm, int32_t Wm, int32_t* Hp, int32_t* Wp)
 {
     if (Hm < 1 || Wm < 1 || !Hp || !Wp) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem_shape: map %d x %d or a NULL output", Hm, Wm);

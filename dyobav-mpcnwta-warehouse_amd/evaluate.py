@@ -30,7 +30,8 @@ scenarios still running:
    (fused path only -- its independent check is tests/kf_reference.py);
    with ``predictor="mmp"``: ``_mmp_predict`` = the device front end (``mmp_front.MmpFrontEnd.run``: ``nmpc_mmp_input_*``,
    ``csrc/nmpc_mmp.h``, or with ``mmp_stem`` the fused first layer ``nmpc_mmp_stem_*``, then with ``mmp_blocks`` the fused blocks
-   of layer1, ``nmpc_mmp_block_f32``, then with ``mmp_blocks2`` those of layer2, ``nmpc_mmp_block2_f32``, then with ``mmp_blocks3`` those of layer3, ``nmpc_mmp_block3_f32``; its structs, weights and buffers are stated there, once) -> the caller's network ->
+   of layer1, ``nmpc_mmp_block_f32``, then with ``mmp_blocks2`` those of layer2, ``nmpc_mmp_block2_f32``, then with ``mmp_blocks3`` those of layer3, ``nmpc_mmp_block3_f32``, then with ``mmp_blocks4`` those of layer4, ``nmpc_mmp_block4_f32``; its structs, weights and buffers are stated there, once) -> the caller's network
+   (or, with ``mmp_head``, ``nmpc_mmp_head_f32`` in the front end and no network at all) ->
    ``nmpc_snap_hypotheses_*`` -> ``nmpc_hypotheses_to_ellipses_*`` (row f2), whose ``Ndynobs`` rows per scenario replace
    ``loop_pre``'s as the input of f1 (``MainBase.run_wta_prediction``, main_base.py:175-208, ``MmpInterface``,
    interfaces/mmp_interface.py:20-70; its independent check is tests/mmp_reference.py);
@@ -127,7 +128,8 @@ class BatchEvaluator:
                  compact: Optional[bool] = None, fused: bool = True, n_hyp: int = 1, hyp_fan: float = 0.15,
                  hyp_radius_growth: float = 0.05, predictor: Optional[str] = "cvmp", kf_Q=None, kf_R=None, kf_P0=None,
                  tracker: str = "mpc", dwa_config=None, network=None, mmp_hyp: int = 20, mmp_chunk: Optional[int] = None,
-                 ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None, mmp_blocks=None, mmp_blocks2=None, mmp_blocks3=None):
+                 ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None, mmp_blocks=None, mmp_blocks2=None, mmp_blocks3=None,
+                 mmp_blocks4=None, mmp_head=None):
         """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
@@ -175,6 +177,16 @@ class BatchEvaluator:
         ``layer4`` on, called on ``[M, 64, H3, W3]`` (19 x 21 for the warehouse map). Measured in the same setting
         (``profiles/mmp_layer3_evaluate.json``, DESIGN.md section 7): the stage takes 420 ms per lock-step against 467 ms without;
         the six launches 122 ms where torch's own layer3 took 170.
+        ``mmp_blocks4`` (needs ``mmp_blocks3``): the :class:`.mmp_stem.Block4Spec` s of the fourth residual stage
+        (``mmp_stem.split_network_layer4``: three for the reference's ``resnet34.layer4``, the first 64 -> 128 at stride 2), one fused
+        kernel per block (``nmpc_mmp_block4_f32``, csrc/nmpc_mmp_block4.h) between two 128-channel buffers that lie inside the stem's
+        output behind layer3's where everything fits (the chunk stays at 22 pedestrians); ``network`` is then the trunk from
+        ``apool`` on, called on ``[M, 128, H4, W4]`` (10 x 11 for the warehouse map). ``mmp_head`` (needs ``mmp_blocks4``): the
+        :class:`.mmp_stem.HeadSpec` of the network's end (``mmp_stem.split_network_whole``), one launch (``nmpc_mmp_head_f32``,
+        csrc/nmpc_mmp_head.h); ``network`` must then be ``None`` -- nothing of the stage is a torch module any more -- and
+        ``mmp_hyp`` must be half the head's outputs. Measured in the same setting (``profiles/mmp_layer4_evaluate.json``, DESIGN.md
+        section 7): the stage takes 389 ms per lock-step against 420 ms without; the three launches 58 ms where torch's own layer4
+        took 95, the head 4.4 ms where torch's pool and linear layers took 3.0.
 
         ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the
@@ -193,12 +205,19 @@ class BatchEvaluator:
             raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; mmp with tracker = 'mpc'; None with tracker = 'dwa')")
         if mmp_stem is not None and predictor != "mmp":
             raise ValueError("mmp_stem needs predictor = 'mmp'")
-        mmp_stem, mmp_blocks, mmp_blocks2, mmp_blocks3 = MmpFrontEnd.check_specs(mmp_stem, mmp_blocks, prefix="mmp_", blocks2=mmp_blocks2,
-                                                                                 blocks3=mmp_blocks3)
+        mmp_stem, mmp_blocks, mmp_blocks2, mmp_blocks3, mmp_blocks4, mmp_head = MmpFrontEnd.check_specs(
+            mmp_stem, mmp_blocks, prefix="mmp_", blocks2=mmp_blocks2, blocks3=mmp_blocks3, blocks4=mmp_blocks4, head=mmp_head)
         if predictor == "mmp":
             if self.n_hyp != 1 or not fused:
                 raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
-            if not callable(network) or ref_image is None or transform is None:
+            if mmp_head is not None:
+                if network is not None:
+                    raise ValueError("mmp_head is the network's end: network must be None with it")
+                if ref_image is None or transform is None:
+                    raise ValueError("predictor = 'mmp' needs ref_image and transform")
+                if 2 * int(mmp_hyp) != mmp_head.w2.shape[0]:
+                    raise ValueError(f"mmp_hyp = {mmp_hyp}, but mmp_head gives {mmp_head.w2.shape[0]} outputs = {mmp_head.w2.shape[0] // 2} hypotheses (x, y)")
+            elif not callable(network) or ref_image is None or transform is None:
                 raise ValueError("predictor = 'mmp' needs network (a callable), ref_image and transform")
             if int(mmp_hyp) < 1 or (mmp_chunk is not None and int(mmp_chunk) < 1) or not float(rescale) != 0.0:
                 raise ValueError(f"mmp_hyp = {mmp_hyp}, mmp_chunk = {mmp_chunk}, rescale = {rescale}")
@@ -219,7 +238,7 @@ class BatchEvaluator:
         self.kf_Q, self.kf_R, self.kf_P0 = eye(kf_Q, 4), eye(kf_R, 2), eye(kf_P0, 4)
         # time_predictor / time_tracker: HIP events around every nmpc_kf_predict / nmpc_dwa_step call; run() leaves the
         # times (ms) in predictor_ms / tracker_ms
-        # (predictor "mmp": time_predictor_parts adds events around its four parts -- five with mmp_blocks: "layer1", six with mmp_blocks2: "layer2", seven with mmp_blocks3: "layer3" --;
+        # (predictor "mmp": time_predictor_parts adds events around its four parts -- five with mmp_blocks: "layer1", six with mmp_blocks2: "layer2", seven with mmp_blocks3: "layer3", eight with mmp_blocks4: "layer4"; with mmp_head "head" in place of "network" --;
         # predictor_part_ms: name -> ms per step)
         self.time_predictor, self.time_tracker, self.time_predictor_parts = False, False, False
         self.predictor_ms, self.tracker_ms, self.predictor_part_ms = [], [], {}
@@ -293,7 +312,7 @@ class BatchEvaluator:
         else:
             self._init_dwa(robot_paths)
         if predictor == "mmp":
-            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_stem, mmp_blocks, mmp_blocks2, mmp_blocks3)
+            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_stem, mmp_blocks, mmp_blocks2, mmp_blocks3, mmp_blocks4, mmp_head)
 
     def _tensor(self, x):
         return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
@@ -354,10 +373,11 @@ class BatchEvaluator:
         self._info, self._evals = self._full(B, 8), self._full(B)
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
 
-    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem, blocks=None, blocks2=None, blocks3=None):
+    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem, blocks=None, blocks2=None, blocks3=None, blocks4=None,
+                  head=None):
         """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the device front
         end (``mmp_front``: its kernels, weights and buffers) and from it the shape of one row of the network's input -- the stack's
-        [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind fused blocks [16, Hp, Wp], or behind those of layer2 [32, H2, W2], or of layer3 [64, H3, W3] -- and the chunk."""
+        [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind fused blocks [16, Hp, Wp], or behind those of layer2 [32, H2, W2], or of layer3 [64, H3, W3], or of layer4 [128, H4, W4], or with a head the network's output [O] -- and the chunk."""
         img = np.ascontiguousarray(ref_image, dtype=np.float32)
         if img.ndim != 2:
             raise ValueError(f"ref_image must be [Hm, Wm], got {img.shape}")
@@ -369,9 +389,9 @@ class BatchEvaluator:
         # mmp_interface.py:60 snaps on 255 - ref_image; its grey levels decide the edges (Handle.set_map)
         self.h.set_map(255.0 - img.astype(np.float64))
         fe = self.mmp_front = MmpFrontEnd(self.h, self.dt, self.dev, self.mmp_Hm, self.mmp_Wm, self.N, transform, self.mmp_rescale, MMP_SIGMA,
-                                          self.mmp_ref, stem, blocks, blocks2, blocks3)
+                                          self.mmp_ref, stem, blocks, blocks2, blocks3, blocks4, head)
         self.mmp_row, self.mmp_stem, self.mmp_blocks, self.mmp_blocks2 = fe.row, fe.stem, fe.blocks, fe.blocks2  # (the specs with their arrays on the device)
-        self.mmp_blocks3 = fe.blocks3
+        self.mmp_blocks3, self.mmp_blocks4, self.mmp_head = fe.blocks3, fe.blocks4, fe.head
         self.mmp_chunk = int(mmp_chunk) if mmp_chunk is not None else max(1, MMP_INPUT_BYTES // fe.bytes_per_item)
 
     def _init_dwa(self, robot_paths):
@@ -589,7 +609,7 @@ class BatchEvaluator:
     def _mmp_predict(self, r, fe, kt, idx, nA):
         """The multi-hypothesis predictor for the ``nA`` running scenarios (``idx``, None = all), MainBase.run_wta_prediction
         (main_base.py:175-208): per chunk of pedestrians the device front end (``MmpFrontEnd.run``: input stack, or the fused first
-        layer's output, then the fused blocks of layer1, layer2 and layer3) -> network; then, per scenario with its pedestrians' segments concatenated
+        layer's output, then the fused blocks of layer1 to layer4) -> network (with ``mmp_head`` the front end's last launch instead); then, per scenario with its pedestrians' segments concatenated
         in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]``."""
         torch, N, H, K = self.torch, self.N, self.H, self.mmp_hyp
 
@@ -607,8 +627,11 @@ class BatchEvaluator:
         for c0 in range(0, n_ped, self.mmp_chunk):
             n = min(self.mmp_chunk, n_ped - c0)
             x = fe.run(self.hist.data_ptr(), self.hcount.data_ptr(), self.B, H, items[c0:].data_ptr(), n, part)
-            with torch.no_grad():
-                out = part("network", lambda: self.network(x))
+            if self.mmp_head is not None:
+                out = x                                             # (the head was the front end's last launch)
+            else:
+                with torch.no_grad():
+                    out = part("network", lambda: self.network(x))
             if out.numel() != n * N * K * 2:
                 raise ValueError(f"the network returned {tuple(out.shape)} for {n * N} inputs; expected {K} hypotheses (x, y) each")
             r.mmp_raw_p[c0:c0 + n] = out.reshape(n, N, K, 2)

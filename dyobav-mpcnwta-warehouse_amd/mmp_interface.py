@@ -11,7 +11,9 @@ What the reference does on the host around the network runs on the device: the i
 the copy per time offset) through ``nmpc_mmp_input_f64`` with one item (with ``stem=``, a :class:`.mmp_stem.StemSpec`, the
 stack and the network's first layer in one kernel, ``nmpc_mmp_stem_f64``, and ``network`` = the trunk; with ``blocks=`` as well, the
 first residual stage behind it, one ``nmpc_mmp_block_f32`` per block; with ``blocks2=`` on top, the second, strided one,
-one ``nmpc_mmp_block2_f32`` per block; with ``blocks3=`` on top, the third, one ``nmpc_mmp_block3_f32`` per block),
+one ``nmpc_mmp_block2_f32`` per block; with ``blocks3=`` on top, the third, one ``nmpc_mmp_block3_f32`` per block; with
+``blocks4=`` the fourth, one ``nmpc_mmp_block4_f32`` per block; with ``head=`` the pool and the linear layers,
+``nmpc_mmp_head_f32``, and ``network=None``),
 ``get_closest_edge_point(...) / rescale`` through
 ``nmpc_snap_hypotheses_f64`` with the identity transform. There is no host implementation of either in this package. The kernels
 in front of the network are driven through :class:`.mmp_front.MmpFrontEnd`, the same object the evaluator uses, with
@@ -35,7 +37,7 @@ OBSV_LEN = 5        # config.obsv_len of the reference's network configurations
 
 
 class MmpInterface:
-    def __init__(self, network: Callable, stem=None, blocks=None, blocks2=None, blocks3=None):
+    def __init__(self, network: Optional[Callable] = None, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None):
         """``stem``: a :class:`.mmp_stem.StemSpec` = the network's first layer, computed on the device without the input stack
         (``nmpc_mmp_stem_f64``); ``network`` is then the trunk behind it, a callable on ``[M, C, Hp, Wp]``. ``blocks`` (needs
         ``stem``): the :class:`.mmp_stem.BlockSpec` s of the residual stage behind the stem (``mmp_stem.split_network_layer1``),
@@ -44,12 +46,19 @@ class MmpInterface:
         fused kernel each (``nmpc_mmp_block2_f32``); ``network`` is then the trunk from ``layer3`` on, called on ``[M, 32, H2, W2]``.
         ``blocks3`` (needs ``blocks2``): the :class:`.mmp_stem.Block3Spec` s of the third residual stage
         (``mmp_stem.split_network_layer3``), one fused kernel each (``nmpc_mmp_block3_f32``); ``network`` is then the trunk from
-        ``layer4`` on, called on ``[M, 64, H3, W3]``."""
-        if not callable(network):
+        ``layer4`` on, called on ``[M, 64, H3, W3]``. ``blocks4`` (needs ``blocks3``): the :class:`.mmp_stem.Block4Spec` s of the fourth
+        (``mmp_stem.split_network_layer4``, ``nmpc_mmp_block4_f32``); ``network`` is then the trunk from ``apool`` on, called on
+        ``[M, 128, H4, W4]``. ``head`` (needs ``blocks4``): the :class:`.mmp_stem.HeadSpec` of the network's end
+        (``mmp_stem.split_network_whole``, ``nmpc_mmp_head_f32``); ``network`` must then be ``None``, and ``batch_size`` no longer
+        splits anything."""
+        if head is not None and network is not None:
+            raise TypeError("head is the network's end: network must be None with it")
+        if head is None and not callable(network):
             raise TypeError(f"network must be a callable, got {type(network)}")
         self._prt_name = "MMPInterface"
         self.network = network
-        self.stem, self.blocks, self.blocks2, self.blocks3 = MmpFrontEnd.check_specs(stem, blocks, blocks2=blocks2, blocks3=blocks3)
+        self.stem, self.blocks, self.blocks2, self.blocks3, self.blocks4, self.head = MmpFrontEnd.check_specs(
+            stem, blocks, blocks2=blocks2, blocks3=blocks3, blocks4=blocks4, head=head)
         self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)
         self._map_of = {}         # pred_offset -> the ref_image its map was set from
         self._fronts = {}         # (pred_offset, Hm, Wm, rescale) -> device front end: the weights are uploaded once, the buffers reused
@@ -96,13 +105,17 @@ class MmpInterface:
         key = (N, Hm, Wm, float(rescale))
         if key not in self._fronts:
             d_ref = torch.empty(Hm, Wm, dtype=torch.float32, device=d_hist.device)
-            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, self.stem, self.blocks, self.blocks2, self.blocks3)
+            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, self.stem, self.blocks, self.blocks2, self.blocks3,
+                                            self.blocks4, self.head)
             self._fronts[key].allocate(1)
         fe = self._fronts[key]
         fe.ref.copy_(torch.from_numpy(img))
         stack = fe.run(d_hist.data_ptr(), d_count.data_ptr(), 1, 1, None, 1)
-        with torch.no_grad():
-            outs = [self.network(stack[i:i + bs]) for i in range(0, N, bs)]
+        if self.head is not None:
+            outs = [stack]                                      # (the head was the front end's last launch: [N, O])
+        else:
+            with torch.no_grad():
+                outs = [self.network(stack[i:i + bs]) for i in range(0, N, bs)]
         raw = torch.cat([o.reshape(o.shape[0], -1, 2) for o in outs], dim=0).to(torch.float64)
         if raw.shape[0] != N or raw.shape[1] < 1 or raw.shape[1] > 256:
             raise ValueError(f"the network returned {tuple(raw.shape)} for {N} inputs")

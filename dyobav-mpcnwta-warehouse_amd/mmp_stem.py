@@ -30,7 +30,16 @@ The third residual stage, ``resnet34.layer3`` = six ``BasicBlock`` s at 64 chann
 1 x 1, stride-2 projection (19 x 21 from 37 x 42), goes through a third kernel family (``nmpc_mmp_block3_f32``,
 csrc/nmpc_mmp_block3.h): ``Block3Spec`` has ``Block2Spec`` 's fields, ``fold_block3`` folds one block,
 ``split_network_layer3(net)`` returns the stem, the blocks of layer1, layer2 and layer3 and the trunk from ``layer4`` on, for
-``BatchEvaluator(..., mmp_blocks3=blocks3)`` and ``MmpInterface(..., blocks3=blocks3)``."""
+``BatchEvaluator(..., mmp_blocks3=blocks3)`` and ``MmpInterface(..., blocks3=blocks3)``.
+
+The fourth residual stage, ``resnet34.layer4`` = three ``BasicBlock`` s at 128 channels, the first ``64 -> 128`` at stride 2 with a
+1 x 1, stride-2 projection (10 x 11 from 19 x 21), goes through a fourth kernel family (``nmpc_mmp_block4_f32``,
+csrc/nmpc_mmp_block4.h): ``Block4Spec`` has ``Block3Spec`` 's fields, ``fold_block4`` folds one block,
+``split_network_layer4(net)`` returns the stem, the blocks of layer1 to layer4 and the trunk from ``apool`` on. The network's end
+-- ``AvgPool2d(2, 2)``, flatten, ``fc1 = Linear(F, 128)``, ``leaky``, ``swarm.layer_hypos = Linear(128, 2 K)`` -- is one launch
+(``nmpc_mmp_head_f32``, csrc/nmpc_mmp_head.h): ``HeadSpec(w1, c1, slope, w2, c2)`` from ``fold_head``, and
+``split_network_whole(net)`` returns the stem, the four tuples of blocks and the head with NO trunk left, for
+``BatchEvaluator(..., mmp_blocks4=blocks4, mmp_head=head)`` and ``MmpInterface(None, ..., blocks4=blocks4, head=head)``."""
 from __future__ import annotations
 
 from typing import Callable, NamedTuple, Optional, Tuple
@@ -96,6 +105,35 @@ class Block3Spec(NamedTuple):
 
 
 BLOCK3_CHANNELS = 64                # output channels of the third stage's fused block (csrc/nmpc_mmp_block3.h)
+
+
+class Block4Spec(NamedTuple):
+    w1: np.ndarray                  # [128, Cin, 3, 3] float32
+    s1: np.ndarray                  # [128] float32
+    b1: np.ndarray                  # [128] float32
+    slope_mid: float
+    w2: np.ndarray                  # [128, 128, 3, 3] float32
+    s2: np.ndarray                  # [128]
+    b2: np.ndarray                  # [128]
+    wd: Optional[np.ndarray]        # [128, Cin] float32, or None: the identity (Cin == 128 and stride == 1)
+    sd: Optional[np.ndarray]        # [128] or None
+    bd: Optional[np.ndarray]        # [128] or None
+    slope_out: float
+    stride: int                     # 1 or 2: of the first convolution and of the projection
+
+
+BLOCK4_CHANNELS = 128               # output channels of the fourth stage's fused block (csrc/nmpc_mmp_block4.h)
+
+
+class HeadSpec(NamedTuple):
+    w1: np.ndarray                  # [128, F] float32: fc1 on the pooled planes flattened [c][h][w]
+    c1: np.ndarray                  # [128] float32
+    slope: float                    # of the LeakyReLU between the two layers
+    w2: np.ndarray                  # [O, 128] float32: the hypothesis layer, O = 2 K
+    c2: np.ndarray                  # [O] float32
+
+
+HEAD_FEATURES = 128                 # outputs of the head's first linear layer (csrc/nmpc_mmp_head.h)
 
 
 def _pair(v):
@@ -385,6 +423,11 @@ def fold_block3(block) -> Block3Spec:
     return _fold_strided(block, "fold_block3", BLOCK3_CHANNELS, Block3Spec)
 
 
+def fold_block4(block) -> Block4Spec:
+    """As ``fold_block2`` for a block with 128 output channels -> :class:`Block4Spec`: the same fold in float64, the same refusals."""
+    return _fold_strided(block, "fold_block4", BLOCK4_CHANNELS, Block4Spec)
+
+
 def _check_strided(spec, C, Spec):
     f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
     w1, s1, b1, w2, s2, b2 = (f32(v) for v in (spec.w1, spec.s1, spec.b1, spec.w2, spec.s2, spec.b2))
@@ -418,6 +461,11 @@ def check_block2(spec) -> Block2Spec:
 def check_block3(spec) -> Block3Spec:
     """As ``check_block2``, at 64 output channels."""
     return _check_strided(spec, BLOCK3_CHANNELS, Block3Spec)
+
+
+def check_block4(spec) -> Block4Spec:
+    """As ``check_block2``, at 128 output channels."""
+    return _check_strided(spec, BLOCK4_CHANNELS, Block4Spec)
 
 
 def check_blocks2(blocks, blocks2) -> Tuple[Block2Spec, ...]:
@@ -498,3 +546,109 @@ def split_network_layer3(net) -> Tuple[StemSpec, Tuple[BlockSpec, ...], Tuple[Bl
             x = layer(x)
         return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
     return spec, blocks, blocks2, blocks3, trunk
+
+
+def check_blocks4(blocks3, blocks4) -> Tuple[Block4Spec, ...]:
+    """The layer-4 blocks behind the (checked) layer-3 ``blocks3`` as a tuple of checked specs: the first takes the 64 channels layer3
+    gives, each later one is 128 -> 128."""
+    if not blocks3:
+        raise ValueError("mmp_blocks4: the blocks of layer3 are needed in front")
+    blocks4 = tuple(check_block4(b) for b in blocks4)
+    if not blocks4:
+        raise ValueError("mmp_blocks4: at least one Block4Spec is needed")
+    cin = BLOCK3_CHANNELS
+    for i, b in enumerate(blocks4):
+        if b.w1.shape[1] != cin:
+            raise ValueError(f"mmp_blocks4: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive "
+                             f"({'layer3 gives 64' if i == 0 else 'every block of layer4 gives 128'})")
+        cin = BLOCK4_CHANNELS
+    return blocks4
+
+
+def _linear(fn, name, layer, n_in, n_out):
+    """(weight [out, in], bias [out]) of a ``torch.nn.Linear`` -like ``layer`` as float32; a missing bias is zeros."""
+    import torch
+    w = getattr(layer, "weight", None)
+    if not isinstance(layer, torch.nn.Linear):
+        raise ValueError(f"{fn}: '{name}' must be a Linear, got {layer}")
+    if (n_in is not None and w.shape[1] != n_in) or (n_out is not None and w.shape[0] != n_out):
+        want = f"Linear({'F' if n_in is None else n_in}, {'O' if n_out is None else n_out})"
+        raise ValueError(f"{fn}: '{name}' must be a {want}, got {w.shape[1]} -> {w.shape[0]}")
+    f32 = lambda a: np.ascontiguousarray(a.detach().cpu().numpy(), dtype=np.float32)
+    b = getattr(layer, "bias", None)
+    return f32(w), (np.zeros(w.shape[0], dtype=np.float32) if b is None else f32(b))
+
+
+def fold_head(apool, fc1, leaky, swarm) -> HeadSpec:
+    """The network's end -> :class:`HeadSpec`: ``apool`` must be ``AvgPool2d(2, 2)`` with padding 0, no ``ceil_mode`` and no
+    ``divisor_override``; ``fc1`` a ``Linear(F, 128)``; ``leaky`` a ``LeakyReLU``; ``swarm`` a ``Linear(128, O)`` or a module whose
+    ``layer_hypos`` is one (the reference's swarm head). ``ValueError`` naming the offender otherwise; a missing bias folds to
+    zeros."""
+    import torch
+    if (not isinstance(apool, torch.nn.AvgPool2d) or _pair(apool.kernel_size) != (2, 2)
+            or _pair(apool.stride if apool.stride is not None else apool.kernel_size) != (2, 2)
+            or _pair(apool.padding) != (0, 0) or apool.ceil_mode or apool.divisor_override is not None):
+        raise ValueError(f"fold_head: 'apool' must be AvgPool2d(2, 2) with padding 0, no ceil_mode and no divisor_override; got {apool}")
+    w1, c1 = _linear("fold_head", "fc1", fc1, None, HEAD_FEATURES)
+    try:
+        slope = _slope("leaky", leaky)
+    except ValueError as e:
+        raise ValueError(str(e).replace("fold_block:", "fold_head:")) from None
+    hyp = getattr(swarm, "layer_hypos", swarm)
+    try:
+        w2, c2 = _linear("fold_head", "swarm", hyp, HEAD_FEATURES, None)
+    except ValueError:
+        raise ValueError(f"fold_head: 'swarm' must be a Linear(128, O) or have such a 'layer_hypos', got {swarm}") from None
+    return check_head(HeadSpec(w1, c1, slope, w2, c2))
+
+
+def check_head(spec) -> HeadSpec:
+    """``spec`` with contiguous float32 arrays of consistent shapes, an even ``O`` from 2 to 512 and a finite slope of magnitude at most
+    1 (``ValueError`` otherwise)."""
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    w1, c1, w2, c2 = (f32(v) for v in (spec.w1, spec.c1, spec.w2, spec.c2))
+    O = w2.shape[0] if w2.ndim == 2 else -1
+    if not (w1.ndim == 2 and w1.shape[0] == HEAD_FEATURES and w1.shape[1] >= 1 and c1.shape == (HEAD_FEATURES,)
+            and w2.ndim == 2 and w2.shape[1] == HEAD_FEATURES and 2 <= O <= 512 and O % 2 == 0 and c2.shape == (O,)):
+        raise ValueError(f"HeadSpec: w1 {w1.shape}, c1 {c1.shape}, w2 {w2.shape}, c2 {c2.shape}; expected [128, F], [128], [O, 128], [O] "
+                         "with O even from 2 to 512")
+    if not np.isfinite(float(spec.slope)) or abs(float(spec.slope)) > 1.0:
+        raise ValueError(f"HeadSpec: slope = {spec.slope}")
+    return HeadSpec(w1, c1, float(spec.slope), w2, c2)
+
+
+def head_features(C: int, H: int, W: int) -> int:
+    """F of the head on a ``[C, H, W]`` plane: the 2 x 2 pool drops an odd last row and column."""
+    return int(C) * (int(H) // 2) * (int(W) // 2)
+
+
+def _layer4(net, fn):
+    try:
+        l4 = list(net.resnet34.layer4)
+    except TypeError:
+        l4 = []
+    if len(l4) != 3:
+        raise ValueError(f"{fn}: 'resnet34.layer4' is not a Sequential of three blocks")
+    return l4
+
+
+def split_network_layer4(net):
+    """As ``split_network_layer3``, with ``resnet34.layer4`` (three blocks, ``fold_block4``) taken off the trunk as well:
+    ``(StemSpec, blocks, blocks2, blocks3, blocks4, trunk)``; the trunk, a callable on ``[M, 128, H4, W4]``, is ``apool``, flatten,
+    ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
+    spec, blocks, blocks2, blocks3, _ = split_network_layer3(net)
+    blocks4 = check_blocks4(blocks3, [fold_block4(b) for b in _layer4(net, "split_network_layer4")])
+    apool, fc1, leaky, swarm = net.resnet34.apool, net.fc1, net.leaky, net.swarm
+
+    def trunk(x):
+        x = apool(x)
+        return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
+    return spec, blocks, blocks2, blocks3, blocks4, trunk
+
+
+def split_network_whole(net):
+    """The whole network as folded weights, with no torch module left to call: ``(StemSpec, blocks, blocks2, blocks3, blocks4,
+    HeadSpec)`` -- ``split_network_layer4`` with its trunk folded by ``fold_head``."""
+    spec, blocks, blocks2, blocks3, _ = split_network_layer3(net)
+    blocks4 = check_blocks4(blocks3, [fold_block4(b) for b in _layer4(net, "split_network_whole")])
+    return spec, blocks, blocks2, blocks3, blocks4, fold_head(net.resnet34.apool, net.fc1, net.leaky, net.swarm)

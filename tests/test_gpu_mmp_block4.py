@@ -1,0 +1,205 @@
+"""GPU tests of the fused 128-channel residual block of the multi-hypothesis predictor's network (nmpc_mmp_block4_f32,
+csrc/nmpc_mmp_block4.h) through the C ABI, against the float64 restatement of tests/mmp_block4_reference.py and its derived bound
+(see there; the controls of that bound are checked without a device in tests/test_mmp_block4_cpu.py).
+
+The cases are ``mmp_block4_reference.CASES``: input planes named from the kernel's tile (10 x 11 outputs where the plane fits, 8 x 9
+per tile along a longer side), at stride 2 with 8 and 64 input channels (half a streamed chunk of sixteen channels, and four) and
+at stride 1 with 128 (no projection), 256 (projection, eight chunks of thirty-two) and 48 (a last chunk with channels missing);
+and the two warehouse planes of layer4, 19 x 21 at stride 2 and 10 x 11 at stride 1, once each with M = 2. Every call writes into
+a buffer with 64 sentinel floats in front and behind.
+
+Worst |out - ref| / bound measured on an MI355X: 0.0032 (20 x 22, Cin 8, stride 2); 0.0004 and 0.0002 on the two warehouse planes."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import dyobav_mpcnwta_warehouse_amd as nm
+import mmp_block4_reference as b4
+import oracle
+from conftest import config_for
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -777.0
+POINTERS = ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
+
+
+@pytest.fixture(scope="module")
+def handle():
+    with nm.Handle(config_for(oracle.Problem())) as h:
+        h.set_stream(torch.cuda.current_stream().cuda_stream)
+        yield h
+
+
+def _block_args(x, spec):
+    """NmpcMmpBlock4Args of x [M, Cin, H, W] (numpy) and a Block4Spec, everything uploaded; ``out`` is left to the caller."""
+    a = nm._capi.NmpcMmpBlock4Args()
+    keep = {"x": torch.from_numpy(np.array(x, dtype=np.float32)).cuda()}
+    a.M, a.Cin, a.H, a.W = (int(v) for v in x.shape)
+    a.stride = int(spec.stride)
+    a.x = keep["x"].data_ptr()
+    for name in POINTERS:
+        v = getattr(spec, name)
+        if v is not None:
+            keep[name] = torch.from_numpy(np.array(v, dtype=np.float32)).cuda()
+            setattr(a, name, keep[name].data_ptr())
+    a.slope_mid, a.slope_out = spec.slope_mid, spec.slope_out
+    return a, keep
+
+
+def _run(h, x, spec, shift=0):
+    """The kernel's output [M, 128, H2, W2] float32. It lies ``shift`` floats into a buffer with 64 sentinel floats in front and
+    behind, which must come back untouched."""
+    a, keep = _block_args(x, spec)
+    shape = (x.shape[0], 128) + b4.out_plane(x.shape[2], x.shape[3], spec.stride)
+    n = int(np.prod(shape))
+    buf = torch.full((64 + shift + n + 64,), SENTINEL, dtype=torch.float32, device="cuda")
+    a.out = buf.data_ptr() + 4 * (64 + shift)
+    h.mmp_block4(a)
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    assert (got[:64 + shift] == SENTINEL).all() and (got[64 + shift + n:] == SENTINEL).all(), "written outside the output"
+    return got[64 + shift:64 + shift + n].reshape(shape)
+
+
+# ---- 1. the kernel against the restatement ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("M", [1, 3])
+@pytest.mark.parametrize("c", b4.CASES, ids=b4.case_id)
+def test_kernel_against_the_restatement(handle, c, M):
+    """The worst |out - ref| / bound is printed per case. The bound is a worst case over every order of summation, so a correct
+    kernel sits far below it (as torch's own float32 ops on the CPU do); the wrong variants exceed it
+    (tests/test_mmp_block4_cpu.py)."""
+    H, W, Cin, stride, projection = c
+    x, spec, want, bound = b4.case("random", *c)
+    assert (x < 0).any() and (x > 0).any() and (spec.s1 < 0).any() and (spec.s1 > 0).any() and (spec.b1 != 0).all()
+    assert (spec.wd is not None) == projection and spec.slope_mid == 0.1 and spec.slope_out == 0.01 and spec.stride == stride
+    got = _run(handle, x[:M], spec)
+    assert got.shape == (M, 128) + b4.out_plane(H, W, stride) and got.dtype == np.float32 and np.isfinite(got).all()
+    ratio = np.abs(got - want[:M]) / bound[:M]
+    print(f"{b4.case_id(c)} M {M}: worst |out - ref| / bound = {ratio.max():.4f}")
+    assert ratio.max() <= 1.0
+
+
+@pytest.mark.parametrize("c", b4.REAL, ids=b4.case_id)
+def test_warehouse_planes_in_full(handle, c):
+    x, spec, want, bound = b4.case("random", *c, 2)
+    got = _run(handle, x, spec)
+    ratio = np.abs(got - want) / bound
+    print(f"{b4.case_id(c)} M 2: worst |out - ref| / bound = {ratio.max():.4f}")
+    assert got.shape == want.shape and np.isfinite(got).all() and ratio.max() <= 1.0
+
+
+# ---- 2. exact: integer weights and inputs, every tap, both border rules, both phases and the channel mapping bit for bit ------------------
+@pytest.mark.parametrize("c", b4.CASES + b4.REAL, ids=b4.case_id)
+def test_integer_block_is_exact(handle, c):
+    x, spec, want, _ = b4.case("integer", *c, 2 if c in b4.REAL else b4.M_MAX)
+    units = b4.integer_units(x, spec)
+    assert units < 2.0 ** 24, units                       # no order of summation can round
+    assert np.array_equal(want.astype(np.float32).astype(np.float64), want) and np.array_equal(x, np.round(x)) and np.abs(x).max() == 1
+    assert spec.slope_mid == 0.125 and spec.slope_out == 0.25 and set(np.unique(spec.w1)) <= {-1.0, 0.0, 1.0}
+    got = _run(handle, x, spec)
+    assert np.array_equal(got, want.astype(np.float32)), (c, np.abs(got - want).max())
+
+
+def test_exact_blocks_double_and_duplicate(handle):
+    x = np.abs(b4.random_x(2, 128, 11, 12, seed=5))
+    assert np.array_equal(_run(handle, x, b4.doubling_block4()), x + x)
+    x = np.abs(b4.random_x(2, 64, 21, 23, seed=6))
+    half = x[:, :, ::2, ::2]
+    assert np.array_equal(_run(handle, x, b4.duplicate_and_double_block4()), np.concatenate([half + half, half + half], axis=1))
+
+
+# ---- 3. independence: the batch, the alignment of out and the other rows do not change a bit ----------------------------------------------
+@pytest.mark.parametrize("c", [(21, 23, 64, 2, True), (11, 12, 256, 1, True), (11, 12, 128, 1, False)], ids=b4.case_id)
+def test_bits_do_not_depend_on_batch_alignment_or_other_rows(handle, c):
+    x, spec, _, _ = b4.case("random", *c)
+    full = _run(handle, x, spec)
+    for k in range(3):
+        assert np.array_equal(_run(handle, x[k:k + 1], spec)[0], full[k]), k
+    for shift in (1, 2, 3):                                # out offset by 4, 8 and 12 bytes: with 0, four float alignments
+        assert np.array_equal(_run(handle, x, spec, shift), full), shift
+    other = x.copy()
+    other[2] = b4.random_x(1, *x.shape[1:], seed=99)[0]
+    got = _run(handle, other, spec)
+    assert np.array_equal(got[:2], full[:2]) and not np.array_equal(got[2], full[2])
+
+
+# ---- 4. argument errors: refused on the host side, nothing is launched --------------------------------------------------------------------
+def test_errors(handle):
+    H, W = 17, 29
+    H2, W2 = b4.out_plane(H, W, 2)
+    x8, proj = b4.random_x(2, 8, H, W, seed=1), b4.random_block4(8, 2, 2, True)
+    x128, plain = b4.random_x(2, 128, H2, W2, seed=3), b4.random_block4(128, 4, 1, False)
+    n_out = 2 * 128 * H2 * W2
+    out = torch.full((64 + n_out + 64,), SENTINEL, dtype=torch.float32, device="cuda")
+    o0 = out.data_ptr() + 256
+
+    def make(x_=x8, spec_=proj, **over):
+        a, keep = _block_args(x_, spec_)
+        a.out = o0
+        for k, v in over.items():
+            setattr(a, k, v)
+        return a, keep
+
+    def code(a):
+        with pytest.raises(nm.NmpcError) as e:
+            handle.mmp_block4(a)
+        assert str(e.value)                                # each refusal carries a message
+        return e.value.code
+    bad = {name + " = NULL": dict(**{name: None}) for name in ("x", "out") + POINTERS}
+    bad.update({"Cin = 0": dict(Cin=0), "Cin = 4": dict(Cin=4), "Cin = 12": dict(Cin=12), "Cin = 264": dict(Cin=264), "Cin < 0": dict(Cin=-8),
+                "H = 0": dict(H=0), "W = 0": dict(W=0), "M < 0": dict(M=-1), "stride = 0": dict(stride=0), "stride = 3": dict(stride=3),
+                "stride = -1": dict(stride=-1), "slope_mid = nan": dict(slope_mid=float("nan")),
+                "slope_mid = inf": dict(slope_mid=float("inf")), "slope_out = nan": dict(slope_out=float("nan")),
+                "slope_out = -inf": dict(slope_out=float("-inf")), "slope_mid = 1.5": dict(slope_mid=1.5), "slope_out = -2": dict(slope_out=-2.0),
+                "out misaligned": dict(out=o0 + 2)})
+    for what, over in bad.items():
+        a, keep = make(**over)
+        assert code(a) == -1, what
+    # wd = NULL above was refused because Cin = 8 at stride 2 has no identity; so are Cin = 64 at stride 1 and Cin = 128 at stride 2
+    a, keep = make(x_=b4.random_x(1, 64, H2, W2, seed=5), spec_=b4.random_block4(64, 6, 1, False))
+    assert code(a) == -1
+    a, keep = make(x_=x128, spec_=plain, stride=2)
+    assert code(a) == -1
+    for name in ("x", "out", "w1", "s1", "b1", "w2", "s2", "b2"):      # sd / bd only count with wd
+        a, keep = make(x_=x128, spec_=plain, **{name: None})
+        assert code(a) == -1, name
+    # out overlapping x, by one float at either end, with the extents M Cin H W of x and M 128 H2 W2 of out
+    a, keep = make(x_=x128, spec_=plain)
+    for o in (a.x, a.x + n_out * 4 - 4, a.x - n_out * 4 + 4):
+        a.out = o
+        assert code(a) == -1, o - a.x
+    a, keep = make()                                       # stride 2: x has 2 * 8 * H * W floats, out 2 * 128 * H2 * W2
+    n_x = 2 * 8 * H * W
+    for o in (a.x, a.x + n_x * 4 - 4, a.x - n_out * 4 + 4):
+        a.out = o
+        assert code(a) == -1, o - a.x
+    # more than 2^31 - 1 workgroups: refused as unsupported before anything is looked at on the device
+    a, keep = make(M=1 << 16, H=4096, W=4096 * 4)
+    assert code(a) == -4
+    # (no int overflow on the way to the count, or in the kernel's pixel coordinates)
+    for over in (dict(H=2 ** 31 - 1, W=4096), dict(H=4096, W=2 ** 31 - 1), dict(M=2 ** 31 - 1, H=2 ** 31 - 1, W=2 ** 31 - 1)):
+        a, keep = make(**over)
+        assert code(a) == -4, over
+    lib = nm.load_library()
+    a, keep = make()
+    assert lib.nmpc_mmp_block4_f32(None, ctypes.byref(a)) == -1 and lib.nmpc_mmp_block4_f32(handle._h, None) == -1
+    # a host pointer is refused, not dereferenced
+    host = np.zeros(128 * 8 * 9, dtype=np.float32)
+    for name in ("w1", "bd"):
+        a, keep = make(**{name: host.ctypes.data})
+        assert code(a) == -1, name
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all()), "a refused call wrote to the output"
+    a, keep = make(M=0)
+    handle.mmp_block4(a)
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all())
+    for x, spec in ((x8, proj), (x128, plain)):
+        a, keep = make(x_=x, spec_=spec)
+        handle.mmp_block4(a)
+        torch.cuda.synchronize()
+        assert bool((out[64:-64] != SENTINEL).all()) and bool((out[:64] == SENTINEL).all()) and bool((out[-64:] == SENTINEL).all())
+        out.fill_(SENTINEL)

@@ -1,0 +1,286 @@
+"""GPU tests of the whole network on the device inside the closed loop: ``BatchEvaluator(predictor="mmp", network=None,
+mmp_stem=, mmp_blocks=, mmp_blocks2=, mmp_blocks3=, mmp_blocks4=, mmp_head=)`` and ``MmpInterface(None, ..., blocks4=, head=)``
+against the ``mmp_blocks3`` path with the same layers as a torch trunk, bit for bit; and of ``MmpFrontEnd`` with ``blocks4`` and
+``head`` in the manner of tests/test_gpu_mmp_block3_loop.py, whose exact network this one continues.
+
+Behind that test's layer3 (2^13 x the pooled stack at every fourth pixel, four times over) layer4 is three exact blocks of
+``mmp_block4_reference``: the first at stride 2 duplicates the 64 channels to 128 through delta weights in ``w1`` and ``wd`` (out =
+2 x[::2, ::2] on non-negative input), then two doublings: 2^16 in total on the 10 x 11 plane. The head: every row of ``W1`` selects
+ONE of the 3 200 pooled values with weight +1 or -1 (``c1 = 0``, slope 1/4), every row of ``W2`` selects ONE feature with weight
+2^-16, and ``c2`` puts the hypotheses of a pedestrian on a fan round a point of the map: every sum has one non-zero term, so the
+only rounding is the addition of ``c2``, the same on both sides. The torch trunk is that expression written with slices,
+``cat``, ``x + x``, the four-term pool in the kernel's order, gathers, one product with a power of two and one addition: no
+convolution and no matrix product, so no library algorithm can round."""
+import numpy as np
+import pytest
+import torch
+
+import dyobav_mpcnwta_warehouse_amd as nm
+import mmp_block4_reference as b4
+import mmp_cases as mc
+import mmp_head_reference as hr
+import mmp_reference as mr
+from dyobav_mpcnwta_warehouse_amd.evaluate import BatchEvaluator
+from dyobav_mpcnwta_warehouse_amd.mmp_front import MmpFrontEnd
+from dyobav_mpcnwta_warehouse_amd.mmp_stem import HeadSpec
+from test_gpu_mmp_block3_loop import (BLOCKS, BLOCKS2, BLOCKS3, CHUNK, FB, FBLOCKS2, FBLOCKS3, FH, FRESCALE, FTF, H3, HM, HP, ITEMS, N_OFF,
+                                      POINTERS, RESCALE, SIGMA, SPEC, STEPS, TF, W3, WM, WP, _assert_equal_runs, _front_blocks,
+                                      _integer_stem, _scenarios, fworld, handle, world)  # noqa: F401 (fixtures)
+
+pytestmark = pytest.mark.gpu
+
+BLOCKS4 = (b4.duplicate_and_double_block4(64),) + (b4.doubling_block4(),) * 2
+PLANE4, POOLED = (10, 11), (5, 5)                        # layer4's plane on the warehouse map, and the pool's
+F_WAREHOUSE = 128 * POOLED[0] * POOLED[1]
+W2_VALUE = 2.0 ** -16
+
+
+def exact_head(K, seed, F=F_WAREHOUSE):
+    """(HeadSpec, sel1 [128], sign [128], sel2 [2 K]): one non-zero per row of W1 (+-1) and of W2 (2^-16); c2 = a point of the map
+    plus the fan, multiples of 1/8 pixel."""
+    rng = np.random.default_rng(4000 + seed)
+    sel1, sign = rng.integers(0, F, 128), rng.choice([-1.0, 1.0], 128).astype(np.float32)
+    sel2 = rng.integers(0, 128, 2 * K)
+    w1, w2 = np.zeros((128, F), dtype=np.float32), np.zeros((2 * K, 128), dtype=np.float32)
+    w1[np.arange(128), sel1] = sign
+    w2[np.arange(2 * K), sel2] = W2_VALUE
+    c2 = (np.array([160.0, 140.0], dtype=np.float32)[None, :] + mr.fan(K, seed)).reshape(-1).astype(np.float32)
+    return HeadSpec(w1, np.zeros(128, dtype=np.float32), 0.25, w2, c2), sel1, sign, sel2
+
+
+def head_in_torch(head, sel1, sign, sel2):
+    """The exact head as a callable on [M, 128, H4, W4]: the pool in the kernel's order, two gathers, no matrix product."""
+    def trunk(x):
+        assert x.shape[1] == 128 and x.dtype == torch.float32
+        t = lambda a, dt=torch.float32: torch.as_tensor(np.asarray(a), device=x.device).to(dt)
+        v = x[:, :, :x.shape[2] // 2 * 2, :x.shape[3] // 2 * 2]
+        p = 0.25 * ((v[..., 0::2, 0::2] + v[..., 0::2, 1::2]) + (v[..., 1::2, 0::2] + v[..., 1::2, 1::2]))
+        f = p.reshape(x.shape[0], -1)[:, t(sel1, torch.long)] * t(sign)[None]
+        f = torch.where(f > 0, f, f * head.slope)
+        return f[:, t(sel2, torch.long)] * W2_VALUE + t(head.c2)[None]
+    return trunk
+
+
+def layer4_in_torch(trunk4):
+    """The exact layer4 in front of ``trunk4``, on [M, 64, H3, W3]: slice, cat, three doublings."""
+    def trunk(x):
+        assert x.shape[1] == 64
+        y = x[..., ::2, ::2]
+        y = torch.cat([y, y], dim=1)
+        for _ in range(3):
+            y = y + y
+        return trunk4(y)
+    return trunk
+
+
+FRONT = dict(mmp_stem=SPEC, mmp_blocks=BLOCKS, mmp_blocks2=BLOCKS2, mmp_blocks3=BLOCKS3)
+
+
+def _run(world, H, K, path, dtype, sc=None, **kw):
+    head, *sel = exact_head(K, H)
+    trunk4 = head_in_torch(head, *sel)
+    net = {"whole": dict(network=None, mmp_blocks4=BLOCKS4, mmp_head=head, **FRONT),
+           "blocks4": dict(network=trunk4, mmp_blocks4=BLOCKS4, **FRONT),
+           "blocks3": dict(network=layer4_in_torch(trunk4), **FRONT)}[path]
+    ev = BatchEvaluator(nm.default_config_struct(), dtype=dtype, predictor="mmp", mmp_hyp=K, ref_image=world["ref"], transform=TF,
+                        rescale=RESCALE, **net, **kw, **(sc or _scenarios(H)))
+    rec = []
+    try:
+        res = ev.run(max_steps=STEPS, record=rec)
+    finally:
+        ev.close()
+    return ev, res, rec
+
+
+# ---- 1. the closed loop with the whole network on the device equals the layer3 path with a torch trunk, bit for bit -------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("shape", [(2, 5), (4, 20)], ids=["P10", "P80"])
+def test_whole_network_loop_equals_the_layer3_loop(world, shape, dtype):
+    H, K = shape
+    whole, parent = (_run(world, H, K, p, dtype, compact=False) for p in ("whole", "blocks3"))
+    assert whole[0].mmp_row == (2 * K,) and parent[0].mmp_row == (64, 19, 21) and whole[0].network is None
+    # (a 16-channel stem's output is too small for the buffers behind it: they are allocated, and counted; so is the head's output)
+    per_row = ((16 + 32) * 74 * 83 + 64 * 37 * 42 + 128 * 19 * 21) * 4
+    assert parent[0].mmp_chunk == (1 << 30) // (parent[0].N * per_row)
+    assert whole[0].mmp_chunk == (1 << 30) // (whole[0].N * (per_row + 256 * 10 * 11 * 4 + 2 * K * 4))
+    _assert_equal_runs(whole, parent)
+    if shape == (2, 5) and dtype is np.float32:              # blocks4 without a head: the trunk is the pool and the linear layers
+        middle = _run(world, H, K, "blocks4", dtype, compact=False)
+        assert middle[0].mmp_row == (128,) + PLANE4
+        _assert_equal_runs(middle, parent)
+
+
+# ---- 2. compaction and chunking leave the bits alone ---------------------------------------------------------------------------------------
+def test_whole_network_loop_with_compaction_and_with_a_chunk_of_one(world):
+    H, K, dead = 4, 20, 1
+    sc = _scenarios(H, dead=dead)
+    whole, parent = (_run(world, H, K, p, np.float64, sc=sc, compact=True) for p in ("whole", "blocks3"))
+    assert whole[1].collision[dead] and whole[1].steps[dead] < STEPS, "the scenario was meant to leave early"
+    _assert_equal_runs(whole, parent)
+    one = _run(world, H, K, "whole", np.float64, sc=sc, compact=True, mmp_chunk=1)
+    assert one[0].mmp_chunk == 1
+    _assert_equal_runs(one, whole)
+
+
+# ---- 3. the timing parts; what the evaluator refuses -----------------------------------------------------------------------------------------
+def test_parts_and_refusals(world):
+    head, *sel = exact_head(5, 2)
+    sc = _scenarios(2)
+    common = dict(dtype=np.float32, predictor="mmp", mmp_hyp=5, ref_image=world["ref"], transform=TF, rescale=RESCALE, **sc)
+    ev = BatchEvaluator(nm.default_config_struct(), **FRONT, mmp_blocks4=BLOCKS4, mmp_head=head, **common)
+    ev.time_predictor = ev.time_predictor_parts = True
+    try:
+        ev.run(max_steps=2)
+    finally:
+        ev.close()
+    assert set(ev.predictor_part_ms) == {"input", "layer1", "layer2", "layer3", "layer4", "head", "snap", "f2"}
+    assert all(len(v) == 2 for v in ev.predictor_part_ms.values())
+    assert len(ev.mmp_blocks4) == 3 and ev.mmp_blocks4[0].w1.is_cuda and ev.mmp_head.w1.is_cuda and len(ev.mmp_blocks3) == 6
+    cfg, trunk = nm.default_config_struct(), head_in_torch(head, *sel)
+    with pytest.raises(ValueError, match="mmp_blocks4 needs mmp_blocks3"):
+        BatchEvaluator(cfg, mmp_stem=SPEC, mmp_blocks=BLOCKS, mmp_blocks2=BLOCKS2, mmp_blocks4=BLOCKS4, network=trunk, **common)
+    with pytest.raises(ValueError, match="mmp_head needs mmp_blocks4"):
+        BatchEvaluator(cfg, **FRONT, mmp_head=head, **common)
+    with pytest.raises(ValueError, match="network must be None"):
+        BatchEvaluator(cfg, **FRONT, mmp_blocks4=BLOCKS4, mmp_head=head, network=trunk, **common)
+    with pytest.raises(ValueError, match="mmp_hyp = 4, but mmp_head gives 10 outputs"):
+        BatchEvaluator(cfg, **FRONT, mmp_blocks4=BLOCKS4, mmp_head=head, **dict(common, mmp_hyp=4))
+    with pytest.raises(ValueError, match="HeadSpec: fc1 takes F = 3328 values"):
+        BatchEvaluator(cfg, **FRONT, mmp_blocks4=BLOCKS4, mmp_head=head._replace(w1=np.zeros((128, 3328), dtype=np.float32)), **common)
+    with pytest.raises(ValueError, match="block 0 takes 128 channels, but 64 arrive"):
+        BatchEvaluator(cfg, **FRONT, mmp_blocks4=BLOCKS4[1:], network=trunk, **common)
+    with pytest.raises(ValueError, match="block 1 takes 64 channels, but 128 arrive"):
+        BatchEvaluator(cfg, **FRONT, mmp_blocks4=BLOCKS4[:1] * 2, network=trunk, **common)
+    with pytest.raises(ValueError, match="needs network \\(a callable\\)"):      # without a head, as before
+        BatchEvaluator(cfg, **FRONT, mmp_blocks4=BLOCKS4, **common)
+
+
+# ---- 4. the drop-in interface ------------------------------------------------------------------------------------------------------------------
+def test_interface_without_a_network_equals_the_layer3_interface(golden_dir):
+    from dyobav_mpcnwta_warehouse_amd.mmp_interface import MmpInterface
+    ref = torch.from_numpy(mc.load_maps(golden_dir)["warehouse"].astype(np.float64))
+    head, *sel = exact_head(20, 7)
+    trunk = layer4_in_torch(head_in_torch(head, *sel))
+    front = dict(stem=SPEC, blocks=BLOCKS, blocks2=BLOCKS2, blocks3=BLOCKS3)
+    with pytest.raises(TypeError, match="network must be None"):
+        MmpInterface(trunk, **front, blocks4=BLOCKS4, head=head)
+    with pytest.raises(TypeError, match="network must be a callable"):
+        MmpInterface(None, **front, blocks4=BLOCKS4)
+    with pytest.raises(ValueError, match="head needs blocks4"):
+        MmpInterface(None, **front, head=head)
+    with pytest.raises(ValueError, match="blocks4 needs blocks3"):
+        MmpInterface(trunk, stem=SPEC, blocks=BLOCKS, blocks2=BLOCKS2, blocks4=BLOCKS4)
+    whole, parent = MmpInterface(None, **front, blocks4=BLOCKS4, head=head), MmpInterface(trunk, **front)
+    try:
+        traj = [(150.25 + 0.75 * i, 120.125 + 0.25 * i) for i in range(7)]
+        for bs in (1, 3):                                  # (with a head batch_size splits nothing; the second call reuses everything)
+            got = whole.get_motion_prediction(traj, ref, 5, RESCALE, batch_size=bs)
+            want = parent.get_motion_prediction(traj, ref, 5, RESCALE, batch_size=bs)
+            assert len(got) == len(want) == 5 and all(g.shape == (20, 2) and g.dtype == np.float64 for g in got)
+            assert np.array_equal(np.stack(got), np.stack(want))
+    finally:
+        whole.close()
+        parent.close()
+
+
+# ---- 5. MmpFrontEnd with blocks4 and a head: the wiring ---------------------------------------------------------------------------------------
+# The 37 x 41 map of the layer3 test (layer3 gives 3 x 3, layer4 2 x 2, the pool 1 x 1: F = 128), integer-valued weights. Two stems:
+# 8 channels -- nothing fits its output, the buffers of layer4 are allocated -- and 64 channels, where 2 x 32 x 5 x 6 + 2 x 64 x 3 x 3 +
+# 2 x 128 x 2 x 2 floats lie inside its 64 x 10 x 11, as for the real network.
+H4, W4, O = 2, 2, 40
+FBLOCKS4 = (b4.integer_block4(64, 21, 2, True),) + tuple(b4.integer_block4(128, 22 + i, 1, False) for i in range(2))
+FHEAD = hr.integer_head(128, H4, W4, O, 31)
+
+
+def _front(handle, fworld, C, blocks4=FBLOCKS4, head=FHEAD, blocks3=FBLOCKS3):
+    return MmpFrontEnd(handle, dtype=np.float64, device=fworld["d_ref"].device, Hm=HM, Wm=WM, n_off=N_OFF, transform=FTF, rescale=FRESCALE,
+                       sigma=SIGMA, ref_image=fworld["d_ref"], stem=_integer_stem(C), blocks=_front_blocks(C), blocks2=FBLOCKS2,
+                       blocks3=blocks3, blocks4=blocks4, head=head)
+
+
+def _direct(handle, x):
+    """FBLOCKS4 and FHEAD through the C ABI on x [M, 64, H3, W3], a buffer of its own per launch."""
+    keep = []
+    for b in FBLOCKS4:
+        g = nm._capi.NmpcMmpBlock4Args()
+        g.M, g.Cin, g.H, g.W = (int(v) for v in x.shape)
+        g.stride = b.stride
+        out = torch.empty(g.M, 128, *b4.out_plane(g.H, g.W, b.stride), dtype=torch.float32, device="cuda")
+        for name in POINTERS:
+            if getattr(b, name) is not None:
+                keep.append(torch.from_numpy(np.ascontiguousarray(getattr(b, name))).cuda())
+                setattr(g, name, keep[-1].data_ptr())
+        g.slope_mid, g.slope_out, g.x, g.out = b.slope_mid, b.slope_out, x.data_ptr(), out.data_ptr()
+        handle.mmp_block4(g)
+        keep.append(x)
+        x = out
+    g = nm._capi.NmpcMmpHeadArgs()
+    g.M, g.C, g.H, g.W = (int(v) for v in x.shape)
+    g.O, g.slope = O, FHEAD.slope
+    out = torch.empty(g.M, O, dtype=torch.float32, device="cuda")
+    for name in ("w1", "c1", "w2", "c2"):
+        keep.append(torch.from_numpy(np.ascontiguousarray(getattr(FHEAD, name))).cuda())
+        setattr(g, name, keep[-1].data_ptr())
+    g.x, g.out = x.data_ptr(), out.data_ptr()
+    handle.mmp_head(g)
+    torch.cuda.synchronize()
+    return x, out
+
+
+@pytest.mark.parametrize("C", [8, 64], ids=["allocated", "inside-the-stem-output"])
+def test_front_end_with_blocks4_and_head(handle, fworld, C):
+    items = torch.tensor(ITEMS, dtype=torch.long, device="cuda")
+    fe, parent = _front(handle, fworld, C), _front(handle, fworld, C, blocks4=None, head=None)
+    inside = C == 64
+    # without the new arguments nothing moves: the row, the parts and the bytes are those of the layer3 front end
+    assert parent.row == (64, H3, W3) and parent.blocks4 is None and parent.head is None and not parent._pp4_in_fill
+    assert parent.bytes_per_item == N_OFF * (C + 32) * HP * WP * 4 + (0 if inside else N_OFF * (2 * 32 * 5 * 6 + 2 * 64 * H3 * W3) * 4)
+    assert fe._pp4_in_fill == inside and fe.row == (O,) and fe.fill_row == (C, HP, WP)
+    assert fe.bytes_per_item == parent.bytes_per_item + (0 if inside else N_OFF * 2 * 128 * H4 * W4 * 4) + N_OFF * O * 4
+    fe.allocate(CHUNK)
+    parent.allocate(CHUNK)
+    if inside:                                             # behind layer3's two buffers, inside the stem's output
+        hi = fe._fill_buf.data_ptr() + fe._fill_buf.numel() * 4
+        assert fe._pp4.data_ptr() == fe._pp3.data_ptr() + fe._pp3.numel() * 4 and fe._pp4.data_ptr() + fe._pp4.numel() * 4 <= hi
+    args = (fworld["d_hist"].data_ptr(), fworld["d_hcount"].data_ptr(), FB, FH)
+    chunks = []
+    for c0 in range(0, len(ITEMS), CHUNK):
+        n, names, pnames = min(CHUNK, len(ITEMS) - c0), [], []
+        got = fe.run(*args, items[c0:].data_ptr(), n, lambda what, call: (names.append(what), call())[1])
+        assert names == ["input", "layer1", "layer2", "layer3", "layer4", "head"]
+        mid = parent.run(*args, items[c0:].data_ptr(), n, lambda what, call: (pnames.append(what), call())[1])
+        assert pnames == ["input", "layer1", "layer2", "layer3"] and mid.shape == (n * N_OFF, 64, H3, W3)
+        planes, want = _direct(handle, mid)
+        assert got.shape == want.shape == (n * N_OFF, O) and got.dtype == torch.float32 and got.is_contiguous()
+        assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0 and torch.equal(got, want), c0
+        chunks.append((planes, got.clone()))
+    assert not torch.equal(chunks[0][1][:N_OFF], chunks[0][1][N_OFF:])
+    # one index space for run_block: 0 .. 2 layer1, 3 .. 6 layer2, 7 .. 12 layer3, 13 .. 15 layer4; the stages' own calls
+    fe.fill(*args, items.data_ptr(), CHUNK)
+    for i in range(16):
+        fe.run_block(i, CHUNK * N_OFF)
+    assert torch.equal(fe.run_head(CHUNK * N_OFF), chunks[0][1])
+    fe.fill(*args, items.data_ptr(), CHUNK)
+    fe.run_blocks(CHUNK * N_OFF)
+    fe.run_blocks2(CHUNK * N_OFF)
+    mid = fe.run_blocks3(CHUNK * N_OFF)
+    assert mid.shape == (CHUNK * N_OFF, 64, H3, W3) and torch.equal(mid, parent.run(*args, items.data_ptr(), CHUNK))
+    assert torch.equal(fe.run_blocks4(CHUNK * N_OFF), chunks[0][0]) and chunks[0][0].shape == (CHUNK * N_OFF, 128, H4, W4)
+    assert torch.equal(fe.run_head(CHUNK * N_OFF), chunks[0][1])
+    with pytest.raises(IndexError):
+        fe.run_block(16, 1)
+    with pytest.raises(IndexError):
+        parent.run_block(13, 1)
+    with pytest.raises(ValueError, match="no head"):
+        parent.run_head(1)
+    with pytest.raises(ValueError, match="allocate"):
+        fe.run(*args, None, CHUNK + 1)
+    assert fe.chunk == CHUNK and all(b.w1.is_cuda for b in fe.blocks4) and fe.blocks4[1].wd is None and fe.blocks4[0].stride == 2
+    with pytest.raises(ValueError, match="blocks4 needs blocks3"):
+        _front(handle, fworld, C, blocks3=None)
+    with pytest.raises(ValueError, match="head needs blocks4"):
+        _front(handle, fworld, C, blocks4=None)
+    with pytest.raises(ValueError, match="block 0 takes 128 channels"):
+        _front(handle, fworld, C, blocks4=FBLOCKS4[1:])
+    with pytest.raises(ValueError, match="HeadSpec: fc1 takes F = 256 values"):
+        _front(handle, fworld, C, head=hr.integer_head(256, H4, W4, O, 31))

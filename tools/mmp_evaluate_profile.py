@@ -37,8 +37,16 @@ path hands the third residual stage (six blocks at 64 channels, the first at str
 around ``input``, ``layer1``, ``layer2``, ``layer3``, ``network`` and the whole stage. Measured first: torch's own layer3, eager,
 alone on one chunk of the parent path's layer2 output; then the six launches alone on that chunk, next to the model of
 csrc/nmpc_mmp_block3.h.
+
+``--fused-layer4``: the last step. The parent path is the new path of ``--fused-layer3`` (trunk from layer4 on in torch); the new
+path is ``mmp_stem.split_network_whole``: the fourth residual stage (three blocks at 128 channels, ``nmpc_mmp_block4_f32``) and
+the pool with both linear layers (``nmpc_mmp_head_f32``) on the device as well, and NO torch module in the stage. Alternated as
+above, with HIP events around ``input``, ``layer1`` .. ``layer4``, ``head`` / ``network`` and the whole stage. Measured first:
+torch's own layer4 and its pool and linear layers, eager, each alone on one chunk of the parent path's layer3 output; then the
+three block launches and the head launch alone on that chunk, next to the model of csrc/nmpc_mmp_block4.h.
    usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]
-          [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS]]      (defaults 256 3 f32 4 20; 3)"""
+          [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS] | --fused-layer4 [REPS]]
+          (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
 import sys
@@ -522,8 +530,134 @@ def fused_layer3_main(out_path, B, steps, dt, n_ped, K, reps):
                                           "block3_kernels_over_torch_layer3", "block3_kernels_over_model")}))
 
 
+MODEL4 = {"rows": 20480, "mfma_pipe_never_waits": 27.3, "useful_fma_at_fp32_peak": 23.5, "bytes_at_copy_rate": 1.3,
+          "head_vector_memory_instructions": 0.64}    # csrc/nmpc_mmp_block4.h; the head: the FIRST model of nmpc_mmp_head.h
+
+
+def _layer3_output(ev, n_item):
+    fe = ev.mmp_front
+    rows = _fill(ev, n_item)().shape[0]
+    fe.run_blocks(rows)
+    fe.run_blocks2(rows)
+    return rows, fe.run_blocks3(rows)
+
+
+def torch_layer4_and_head_alone(ev, layer4, end, n_item, reps=5):
+    """ms of torch's own layer4 (three blocks, eager) on the layer3 output of ``n_item`` pedestrians -- one chunk of the parent path --
+    and of its pool, flatten and linear layers on what layer4 gives."""
+    rows, x = _layer3_output(ev, n_item)
+    with torch.no_grad():
+        t4 = _timed(lambda: layer4(x), reps)
+        y = layer4(x)
+        te = _timed(lambda: end(y), reps)
+    return dict(items=n_item, samples=rows, **t4), dict(items=n_item, samples=rows, **te)
+
+
+def block4_and_head_kernel_rate(ev, n_item, reps=10):
+    """The three nmpc_mmp_block4_f32 launches alone on the layer3 output of ``n_item`` pedestrians (``_strided_kernel_rate``), then the
+    nmpc_mmp_head_f32 launch alone on what they leave: ms, useful fma per second (F x 128 + 128 x O per row) and bytes per second
+    (x read once, W1 and W2 once per group of 16 rows -- from L2 --, out written once)."""
+    fe = ev.mmp_front
+    rows, x = _layer3_output(ev, n_item)
+    first = len(fe.blocks) + len(fe.blocks2) + len(fe.blocks3)
+    blocks = {"items": n_item, **_strided_kernel_rate(fe, rows, reps, fe.blocks4, 128, first, tuple(x.shape[2:]), fe.run_blocks4)}
+    y = fe.run_blocks4(rows)
+    F, O = int(fe.head.w1.shape[1]), int(fe.head.w2.shape[0])
+    t = _timed(lambda: fe.run_head(rows), reps, warm=3)
+    fma, groups = rows * (F * 128 + 128 * O), -(-rows // 16)
+    nbytes = 4 * (rows * int(np.prod(y.shape[1:])) + groups * (F * 128 + 128 * O) + rows * O)
+    head = dict(items=n_item, rows=rows, F=F, O=O, fma=fma, bytes=nbytes, TFMAps_median=fma / t["ms_median"] * 1e-9,
+                GBps_median=nbytes / t["ms_median"] * 1e-6, **t)
+    return blocks, head
+
+
+def fused_layer4_main(out_path, B, steps, dt, n_ped, K, reps):
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import split_network_whole
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    # the module here is a plain Sequential: net[0], net[1] = the first layer, net[2 .. 4] = layer1, net[5 .. 8] = layer2, net[9 .. 14]
+    # = layer3, net[15 .. 17] = layer4, net[18] = the pool, net[20 .. 22] = fc1, leaky, the hypothesis layer. Named as
+    # split_network_whole wants it (Block: a, b, skip, act)
+    as_block = lambda b: SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)
+    L = list(net)
+    shaped = SimpleNamespace(resnet34=SimpleNamespace(stem=SimpleNamespace(conv1=L[0], pooling=L[1]), layer1=[as_block(b) for b in L[2:5]],
+                                                      layer2=[as_block(b) for b in L[5:9]], layer3=[as_block(b) for b in L[9:15]],
+                                                      layer4=[as_block(b) for b in L[15:18]], apool=L[18]), fc1=L[20], leaky=L[21], swarm=L[22])
+    spec, blocks, blocks2, blocks3, blocks4, head = split_network_whole(shaped)
+    head = head._replace(c2=head.c2 + np.float32(150.0))   # (the "+ 150" that puts the random network's hypotheses on the map)
+    layer4, end, trunk4 = torch.nn.Sequential(*L[15:18]), torch.nn.Sequential(*L[18:]), torch.nn.Sequential(*L[15:])
+    front = dict(mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, mmp_blocks3=blocks3)
+    paths = {"parent": dict(network=lambda x: trunk4(x) + 150.0, **front), "fused": dict(network=None, mmp_blocks4=blocks4, mmp_head=head, **front)}
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rows_step = B * n_ped * nm.default_config_struct().N_hor
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage: the parent path (fused first layer + "
+                   "fused layer1 .. layer3 + trunk from layer4 on in torch) and the whole network on the device (layer4 and the head fused as "
+                   "well, no torch module), alternated in one process; random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS, "fp32_peak_TFMAps": PEAK_TFMAS},
+           "model_of_the_headers_per_lock_step_ms": MODEL4, "chunk_pedestrians": {}, "runs": {"parent": [], "fused": []}}
+    for path in paths:                                      # warm-up; torch's layer4 and end alone (the parent path) come first
+        ev = evaluator(path)
+        rec["chunk_pedestrians"][path] = ev.mmp_chunk
+        try:
+            if path == "fused":
+                rec["block4_kernels"], rec["head_kernel"] = block4_and_head_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped))
+            else:
+                rec["torch_layer4_alone"], rec["torch_pool_and_head_alone"] = torch_layer4_and_head_alone(ev, layer4, end, min(ev.mmp_chunk, B * n_ped))
+            ev.run(max_steps=1)
+        finally:
+            ev.close()
+        print(json.dumps({k: rec[k] for k in ("block4_kernels", "head_kernel", "torch_layer4_alone", "torch_pool_and_head_alone") if k in rec}), flush=True)
+        with open(out_path, "w") as f:
+            json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = {"parent": ("input", "layer1", "layer2", "layer3", "network"), "fused": ("input", "layer1", "layer2", "layer3", "layer4", "head")}
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names[p]},
+                                              behind_layer3=med(p, lambda s, p=p: sum(s[k] for k in names[p][4:])),
+                                              stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    # the spread between the alternations: the median stage of every single run
+    rec["stage_median_of_each_run_ms"] = {p: [float(np.median([s["stage_ms"] for s in run])) for run in rec["runs"][p]] for p in paths}
+    m = rec["median_per_lock_step_ms"]
+    rec["fused_layer4_over_parent"] = m["fused"]["stage"] / m["parent"]["stage"]
+    scale = lambda r, rows: r["ms_median"] * (rows_step / rows)
+    tl, te, bk, hk = rec["torch_layer4_alone"], rec["torch_pool_and_head_alone"], rec["block4_kernels"], rec["head_kernel"]
+    rec["torch_layer4_per_lock_step_ms"], rec["torch_pool_and_head_per_lock_step_ms"] = scale(tl, tl["samples"]), scale(te, te["samples"])
+    rec["block4_kernels_per_lock_step_ms"], rec["head_kernel_per_lock_step_ms"] = scale(bk, bk["rows"]), scale(hk, hk["rows"])
+    rec["block4_kernels_over_torch_layer4"] = rec["block4_kernels_per_lock_step_ms"] / rec["torch_layer4_per_lock_step_ms"]
+    rec["head_kernel_over_torch_pool_and_head"] = rec["head_kernel_per_lock_step_ms"] / rec["torch_pool_and_head_per_lock_step_ms"]
+    rec["block4_kernels_over_model"] = rec["block4_kernels_per_lock_step_ms"] * (20480 / rows_step) / MODEL4["mfma_pipe_never_waits"]
+    rec["head_kernel_over_model"] = rec["head_kernel_per_lock_step_ms"] * (20480 / rows_step) / MODEL4["head_vector_memory_instructions"]
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "stage_median_of_each_run_ms", "chunk_pedestrians", "fused_layer4_over_parent",
+                                          "torch_layer4_per_lock_step_ms", "torch_pool_and_head_per_lock_step_ms", "block4_kernels_per_lock_step_ms",
+                                          "head_kernel_per_lock_step_ms", "block4_kernels_over_torch_layer4", "head_kernel_over_torch_pool_and_head",
+                                          "block4_kernels_over_model", "head_kernel_over_model")}))
+    print(json.dumps({"block4": [(b["Cin"], b["stride"], b["ms_median"], b["TFMAps_median"]) for b in bk["blocks"]], "all": (bk["ms_median"], bk["TFMAps_median"])}))
+
+
 def main():
-    for flag, run in (("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+    for flag, run in (("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
         if flag in sys.argv:
             i = sys.argv.index(flag)
             reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
