@@ -1701,6 +1701,7 @@ int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g)
     return 0;
 }
 
+// (layer1's entry, on its own: no stride, and -- on record, unlike mmp_strided below -- neither |slope| <= 1 nor planes up to 2^30 are demanded)
 int mmp_block(nmpc_handle_s* h, const nmpc_mmp_block_args* g)
 {
     if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
@@ -1746,169 +1747,98 @@ int mmp_block(nmpc_handle_s* h, const nmpc_mmp_block_args* g)
     return 0;
 }
 
-int mmp_block2(nmpc_handle_s* h, const nmpc_mmp_block2_args* g)
-{
-    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
-    if (g->M < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: M = %d < 0", g->M);
-    if (g->H < 1 || g->W < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: plane %d x %d", g->H, g->W);
-    if (g->stride != 1 && g->stride != 2) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: stride = %d is neither 1 nor 2", g->stride);
-    if (g->Cin < 8 || g->Cin > 256 || g->Cin % 8)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: Cin = %d is no multiple of 8 from 8 to 256", g->Cin);
-    if (!g->wd && (g->Cin != nmpc::kB2C || g->stride != 1))
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: Cin = %d, stride = %d without a projection (the identity needs Cin = 32 and stride 1)",
-                    g->Cin, g->stride);
-    if (!std::isfinite(g->slope_mid) || !std::isfinite(g->slope_out) || std::fabs(g->slope_mid) > 1.0f || std::fabs(g->slope_out) > 1.0f)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: slope_mid = %g, slope_out = %g (finite, |slope| <= 1)", (double)g->slope_mid,
-                    (double)g->slope_out);
-    if (!g->x || !g->w1 || !g->s1 || !g->b1 || !g->w2 || !g->s2 || !g->b2 || (g->wd && (!g->sd || !g->bd)) || !g->out)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: a required array is NULL");
-    if (reinterpret_cast<uintptr_t>(g->out) % 4 || reinterpret_cast<uintptr_t>(g->x) % 4)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: x or out is not aligned to float");
-    if (g->M == 0) return 0;
-    // (the kernel's pixel coordinates are ints: 2 (tile origin + 11) + 1 must not wrap)
-    if (g->H > (1 << 30) || g->W > (1 << 30)) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block2: plane %d x %d over 2^30", g->H, g->W);
-    nmpc::MmpBlock2Params p;
-    std::memset(&p, 0, sizeof p);
-    p.H2 = (g->H - 1) / g->stride + 1, p.W2 = (g->W - 1) / g->stride + 1;
-    const long long ty = ((long long)p.H2 + nmpc::kB2TH - 1) / nmpc::kB2TH, tx = ((long long)p.W2 + nmpc::kB2TW - 1) / nmpc::kB2TW;
-    const long long tiles = ty * tx; // < 2^56
-    if (tiles > 0x7fffffffLL || tiles * g->M > 0x7fffffffLL) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block2: %lld x %d workgroups", tiles, g->M);
-    const long long groups = tiles * g->M;
-    p.ty = (int)ty, p.tx = (int)tx;
-    // out must not overlap x: a tile's halo is read after the neighbouring tiles have been written
-    // (H2 W2 M <= 352 x 2^31 after the test above, H W <= 4 H2 W2: no overflow)
-    const unsigned long long xb = (unsigned long long)g->H * g->W * g->M * 4 * g->Cin, ob = (unsigned long long)p.H2 * p.W2 * g->M * 4 * nmpc::kB2C;
-    const uintptr_t x0 = reinterpret_cast<uintptr_t>(g->x), o0 = reinterpret_cast<uintptr_t>(g->out);
-    if (x0 < o0 + ob && o0 < x0 + xb) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: out overlaps x");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    // (a host pointer here would fault inside the kernel)
-    if (h->ptr_mode != NMPC_PTR_DEVICE) {
-        const void* ptrs[] = {g->x, g->w1, g->s1, g->b1, g->w2, g->s2, g->b2, g->out, g->wd, g->sd, g->bd};
-        for (int i = 0; i < (g->wd ? 11 : 8); ++i)
-            if (!is_device_ptr(ptrs[i])) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block2: every array must be a device pointer");
+// The three strided stages (layer2 .. layer4) behind one entry, mmp_strided<Stage>. A Stage says what differs: the name in the
+// messages, the structs, the output channels C, the threads of a workgroup, how the plane of outputs H2 x W2 is cut into ty x tx
+// tiles, and the kernels <stride 2, projection>, <stride 1, projection>, <stride 1, identity>. Two numbers of the entry follow from
+// a stage's tile: the kernels' pixel coordinates are ints and reach 2 (tile origin + reach) + 1, which must not wrap -- hence no
+// plane over 2^30 --, and once the workgroup count has passed H2 W2 M <= (outputs of a tile) x 2^31, with H W <= 4 H2 W2: the byte
+// counts of the overlap test do not overflow.
+struct MmpLayer2 {
+    using Args = nmpc_mmp_block2_args;
+    using Params = nmpc::MmpBlock2Params;
+    static constexpr const char* name = "nmpc_mmp_block2";
+    static constexpr int C = nmpc::kB2C, threads = nmpc::kB2Threads;
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk2_kernel<2, true>, nmpc::mmp_blk2_kernel<1, true>, nmpc::mmp_blk2_kernel<1, false>};
+    // tiles of 8 x 44 = 352 outputs; reach 11
+    static void tile(Params& p, long long& ty, long long& tx)
+    {
+        ty = ((long long)p.H2 + nmpc::kB2TH - 1) / nmpc::kB2TH, tx = ((long long)p.W2 + nmpc::kB2TW - 1) / nmpc::kB2TW;
     }
-    p.M = g->M, p.Cin = g->Cin, p.H = g->H, p.W = g->W;
-    p.x = g->x, p.w1 = g->w1, p.s1 = g->s1, p.b1 = g->b1, p.w2 = g->w2, p.s2 = g->s2, p.b2 = g->b2;
-    p.wd = g->wd, p.sd = g->sd, p.bd = g->bd, p.slope_mid = g->slope_mid, p.slope_out = g->slope_out, p.out = g->out;
-    const dim3 grid((unsigned)groups), block(nmpc::kB2Threads);
-    if (g->stride == 2)
-        hipLaunchKernelGGL((nmpc::mmp_blk2_kernel<2, true>), grid, block, 0, h->stream, p);
-    else if (g->wd)
-        hipLaunchKernelGGL((nmpc::mmp_blk2_kernel<1, true>), grid, block, 0, h->stream, p);
-    else
-        hipLaunchKernelGGL((nmpc::mmp_blk2_kernel<1, false>), grid, block, 0, h->stream, p);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
+};
 
-int mmp_block3(nmpc_handle_s* h, const nmpc_mmp_block3_args* g)
-{
-    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
-    if (g->M < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: M = %d < 0", g->M);
-    if (g->H < 1 || g->W < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: plane %d x %d", g->H, g->W);
-    if (g->stride != 1 && g->stride != 2) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: stride = %d is neither 1 nor 2", g->stride);
-    if (g->Cin < 8 || g->Cin > 256 || g->Cin % 8)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: Cin = %d is no multiple of 8 from 8 to 256", g->Cin);
-    if (!g->wd && (g->Cin != nmpc::kB3C || g->stride != 1))
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: Cin = %d, stride = %d without a projection (the identity needs Cin = 64 and stride 1)",
-                    g->Cin, g->stride);
-    if (!std::isfinite(g->slope_mid) || !std::isfinite(g->slope_out) || std::fabs(g->slope_mid) > 1.0f || std::fabs(g->slope_out) > 1.0f)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: slope_mid = %g, slope_out = %g (finite, |slope| <= 1)", (double)g->slope_mid,
-                    (double)g->slope_out);
-    if (!g->x || !g->w1 || !g->s1 || !g->b1 || !g->w2 || !g->s2 || !g->b2 || (g->wd && (!g->sd || !g->bd)) || !g->out)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: a required array is NULL");
-    if (reinterpret_cast<uintptr_t>(g->out) % 4 || reinterpret_cast<uintptr_t>(g->x) % 4)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: x or out is not aligned to float");
-    if (g->M == 0) return 0;
-    // (the kernel's pixel coordinates are ints: 2 (tile origin + 10) + 1 must not wrap)
-    if (g->H > (1 << 30) || g->W > (1 << 30)) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block3: plane %d x %d over 2^30", g->H, g->W);
-    nmpc::MmpBlock3Params p;
-    std::memset(&p, 0, sizeof p);
-    p.H2 = (g->H - 1) / g->stride + 1, p.W2 = (g->W - 1) / g->stride + 1;
-    const long long ty = ((long long)p.H2 + nmpc::kB3TH - 1) / nmpc::kB3TH, tx = ((long long)p.W2 + nmpc::kB3TW - 1) / nmpc::kB3TW;
-    const long long tiles = ty * tx; // < 2^56
-    if (tiles > 0x7fffffffLL || tiles * g->M > 0x7fffffffLL) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block3: %lld x %d workgroups", tiles, g->M);
-    const long long groups = tiles * g->M;
-    p.ty = (int)ty, p.tx = (int)tx;
-    // out must not overlap x: a tile's halo is read after the neighbouring tiles have been written
-    // (H2 W2 M <= 147 x 2^31 after the test above, H W <= 4 H2 W2: no overflow)
-    const unsigned long long xb = (unsigned long long)g->H * g->W * g->M * 4 * g->Cin, ob = (unsigned long long)p.H2 * p.W2 * g->M * 4 * nmpc::kB3C;
-    const uintptr_t x0 = reinterpret_cast<uintptr_t>(g->x), o0 = reinterpret_cast<uintptr_t>(g->out);
-    if (x0 < o0 + ob && o0 < x0 + xb) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: out overlaps x");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    // (a host pointer here would fault inside the kernel)
-    if (h->ptr_mode != NMPC_PTR_DEVICE) {
-        const void* ptrs[] = {g->x, g->w1, g->s1, g->b1, g->w2, g->s2, g->b2, g->out, g->wd, g->sd, g->bd};
-        for (int i = 0; i < (g->wd ? 11 : 8); ++i)
-            if (!is_device_ptr(ptrs[i])) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block3: every array must be a device pointer");
+struct MmpLayer3 {
+    using Args = nmpc_mmp_block3_args;
+    using Params = nmpc::MmpBlock3Params;
+    static constexpr const char* name = "nmpc_mmp_block3";
+    static constexpr int C = nmpc::kB3C, threads = nmpc::kB3Threads;
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk3_kernel<2, true>, nmpc::mmp_blk3_kernel<1, true>, nmpc::mmp_blk3_kernel<1, false>};
+    // tiles of 7 x 21 = 147 outputs; reach 10
+    static void tile(Params& p, long long& ty, long long& tx)
+    {
+        ty = ((long long)p.H2 + nmpc::kB3TH - 1) / nmpc::kB3TH, tx = ((long long)p.W2 + nmpc::kB3TW - 1) / nmpc::kB3TW;
     }
-    p.M = g->M, p.Cin = g->Cin, p.H = g->H, p.W = g->W;
-    p.x = g->x, p.w1 = g->w1, p.s1 = g->s1, p.b1 = g->b1, p.w2 = g->w2, p.s2 = g->s2, p.b2 = g->b2;
-    p.wd = g->wd, p.sd = g->sd, p.bd = g->bd, p.slope_mid = g->slope_mid, p.slope_out = g->slope_out, p.out = g->out;
-    const dim3 grid((unsigned)groups), block(nmpc::kB3Threads);
-    if (g->stride == 2)
-        hipLaunchKernelGGL((nmpc::mmp_blk3_kernel<2, true>), grid, block, 0, h->stream, p);
-    else if (g->wd)
-        hipLaunchKernelGGL((nmpc::mmp_blk3_kernel<1, true>), grid, block, 0, h->stream, p);
-    else
-        hipLaunchKernelGGL((nmpc::mmp_blk3_kernel<1, false>), grid, block, 0, h->stream, p);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
+};
 
-int mmp_block4(nmpc_handle_s* h, const nmpc_mmp_block4_args* g)
+struct MmpLayer4 {
+    using Args = nmpc_mmp_block4_args;
+    using Params = nmpc::MmpBlock4Params;
+    static constexpr const char* name = "nmpc_mmp_block4";
+    static constexpr int C = nmpc::kB4C, threads = nmpc::kB4Threads;
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk4_kernel<2, true>, nmpc::mmp_blk4_kernel<1, true>, nmpc::mmp_blk4_kernel<1, false>};
+    // tiles of at most 10 x 11 = 110 outputs; reach 11. A side that fits the tile's plane of m is one tile without a halo; a longer
+    // one is cut with a halo of one
+    static void tile(Params& p, long long& ty, long long& tx)
+    {
+        ty = nmpc::mmp_b4_tiles(p.H2, nmpc::kB4MH), tx = nmpc::mmp_b4_tiles(p.W2, nmpc::kB4MW);
+        p.oy = p.H2 <= nmpc::kB4MH ? 1 : 2, p.ox = p.W2 <= nmpc::kB4MW ? 1 : 2;
+    }
+};
+
+template <typename Stage>
+int mmp_strided(nmpc_handle_s* h, const typename Stage::Args* g)
 {
+    const char* fn = Stage::name;
     if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
-    if (g->M < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: M = %d < 0", g->M);
-    if (g->H < 1 || g->W < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: plane %d x %d", g->H, g->W);
-    if (g->stride != 1 && g->stride != 2) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: stride = %d is neither 1 nor 2", g->stride);
-    if (g->Cin < 8 || g->Cin > 256 || g->Cin % 8)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: Cin = %d is no multiple of 8 from 8 to 256", g->Cin);
-    if (!g->wd && (g->Cin != nmpc::kB4C || g->stride != 1))
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: Cin = %d, stride = %d without a projection (the identity needs Cin = 128 and stride 1)",
-                    g->Cin, g->stride);
+    if (g->M < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: M = %d < 0", fn, g->M);
+    if (g->H < 1 || g->W < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: plane %d x %d", fn, g->H, g->W);
+    if (g->stride != 1 && g->stride != 2) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: stride = %d is neither 1 nor 2", fn, g->stride);
+    if (g->Cin < 8 || g->Cin > 256 || g->Cin % 8) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: Cin = %d is no multiple of 8 from 8 to 256", fn, g->Cin);
+    if (!g->wd && (g->Cin != Stage::C || g->stride != 1))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: Cin = %d, stride = %d without a projection (the identity needs Cin = %d and stride 1)", fn, g->Cin,
+                    g->stride, Stage::C);
     if (!std::isfinite(g->slope_mid) || !std::isfinite(g->slope_out) || std::fabs(g->slope_mid) > 1.0f || std::fabs(g->slope_out) > 1.0f)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: slope_mid = %g, slope_out = %g (finite, |slope| <= 1)", (double)g->slope_mid,
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: slope_mid = %g, slope_out = %g (finite, |slope| <= 1)", fn, (double)g->slope_mid,
                     (double)g->slope_out);
     if (!g->x || !g->w1 || !g->s1 || !g->b1 || !g->w2 || !g->s2 || !g->b2 || (g->wd && (!g->sd || !g->bd)) || !g->out)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: a required array is NULL");
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: a required array is NULL", fn);
     if (reinterpret_cast<uintptr_t>(g->out) % 4 || reinterpret_cast<uintptr_t>(g->x) % 4)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: x or out is not aligned to float");
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: x or out is not aligned to float", fn);
     if (g->M == 0) return 0;
-    // (the kernel's pixel coordinates are ints: 2 (tile origin + 11) + 1 must not wrap)
-    if (g->H > (1 << 30) || g->W > (1 << 30)) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block4: plane %d x %d over 2^30", g->H, g->W);
-    nmpc::MmpBlock4Params p;
+    if (g->H > (1 << 30) || g->W > (1 << 30)) return fail(NMPC_ERR_UNSUPPORTED, "%s: plane %d x %d over 2^30", fn, g->H, g->W);
+    typename Stage::Params p;
     std::memset(&p, 0, sizeof p);
     p.H2 = (g->H - 1) / g->stride + 1, p.W2 = (g->W - 1) / g->stride + 1;
-    // (a side that fits the tile's plane of m is one tile without a halo; a longer one is cut with a halo of one)
-    const long long ty = nmpc::mmp_b4_tiles(p.H2, nmpc::kB4MH), tx = nmpc::mmp_b4_tiles(p.W2, nmpc::kB4MW);
-    p.oy = p.H2 <= nmpc::kB4MH ? 1 : 2, p.ox = p.W2 <= nmpc::kB4MW ? 1 : 2;
+    long long ty, tx;
+    Stage::tile(p, ty, tx);
     const long long tiles = ty * tx; // < 2^56
-    if (tiles > 0x7fffffffLL || tiles * g->M > 0x7fffffffLL) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_mmp_block4: %lld x %d workgroups", tiles, g->M);
+    if (tiles > 0x7fffffffLL || tiles * g->M > 0x7fffffffLL) return fail(NMPC_ERR_UNSUPPORTED, "%s: %lld x %d workgroups", fn, tiles, g->M);
     const long long groups = tiles * g->M;
     p.ty = (int)ty, p.tx = (int)tx;
     // out must not overlap x: a tile's halo is read after the neighbouring tiles have been written
-    // (H2 W2 M <= 110 x 2^31 after the test above, H W <= 4 H2 W2: no overflow)
-    const unsigned long long xb = (unsigned long long)g->H * g->W * g->M * 4 * g->Cin, ob = (unsigned long long)p.H2 * p.W2 * g->M * 4 * nmpc::kB4C;
+    const unsigned long long xb = (unsigned long long)g->H * g->W * g->M * 4 * g->Cin, ob = (unsigned long long)p.H2 * p.W2 * g->M * 4 * Stage::C;
     const uintptr_t x0 = reinterpret_cast<uintptr_t>(g->x), o0 = reinterpret_cast<uintptr_t>(g->out);
-    if (x0 < o0 + ob && o0 < x0 + xb) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: out overlaps x");
+    if (x0 < o0 + ob && o0 < x0 + xb) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: out overlaps x", fn);
     HIP_TRY(hipSetDevice(h->cfg.device_id));
     // (a host pointer here would fault inside the kernel)
     if (h->ptr_mode != NMPC_PTR_DEVICE) {
         const void* ptrs[] = {g->x, g->w1, g->s1, g->b1, g->w2, g->s2, g->b2, g->out, g->wd, g->sd, g->bd};
         for (int i = 0; i < (g->wd ? 11 : 8); ++i)
-            if (!is_device_ptr(ptrs[i])) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_block4: every array must be a device pointer");
+            if (!is_device_ptr(ptrs[i])) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: every array must be a device pointer", fn);
     }
     p.M = g->M, p.Cin = g->Cin, p.H = g->H, p.W = g->W;
     p.x = g->x, p.w1 = g->w1, p.s1 = g->s1, p.b1 = g->b1, p.w2 = g->w2, p.s2 = g->s2, p.b2 = g->b2;
     p.wd = g->wd, p.sd = g->sd, p.bd = g->bd, p.slope_mid = g->slope_mid, p.slope_out = g->slope_out, p.out = g->out;
-    const dim3 grid((unsigned)groups), block(nmpc::kB4Threads);
-    if (g->stride == 2)
-        hipLaunchKernelGGL((nmpc::mmp_blk4_kernel<2, true>), grid, block, 0, h->stream, p);
-    else if (g->wd)
-        hipLaunchKernelGGL((nmpc::mmp_blk4_kernel<1, true>), grid, block, 0, h->stream, p);
-    else
-        hipLaunchKernelGGL((nmpc::mmp_blk4_kernel<1, false>), grid, block, 0, h->stream, p);
+    hipLaunchKernelGGL(Stage::kernels[g->stride == 2 ? 0 : g->wd ? 1 : 2], dim3((unsigned)groups), dim3(Stage::threads), 0, h->stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2412,9 +2342,9 @@ int nmpc_mmp_input_f64(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input
 int nmpc_mmp_stem_f32(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<float>(h, a); }
 int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<double>(h, a); }
 int nmpc_mmp_block_f32(nmpc_handle h, const nmpc_mmp_block_args* a) { return mmp_block(h, a); }
-int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return mmp_block2(h, a); }
-int nmpc_mmp_block3_f32(nmpc_handle h, const nmpc_mmp_block3_args* a) { return mmp_block3(h, a); }
-int nmpc_mmp_block4_f32(nmpc_handle h, const nmpc_mmp_block4_args* a) { return mmp_block4(h, a); }
+int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return mmp_strided<MmpLayer2>(h, a); }
+int nmpc_mmp_block3_f32(nmpc_handle h, const nmpc_mmp_block3_args* a) { return mmp_strided<MmpLayer3>(h, a); }
+int nmpc_mmp_block4_f32(nmpc_handle h, const nmpc_mmp_block4_args* a) { return mmp_strided<MmpLayer4>(h, a); }
 int nmpc_mmp_head_f32(nmpc_handle h, const nmpc_mmp_head_args* a) { return mmp_head(h, a); }
 int nmpc_mmp_stem_shape(int32_t Hm, int32_t Wm, int32_t* Hp, int32_t* Wp)
 {

@@ -54,7 +54,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from .mmp_front import MmpFrontEnd
+from .mmp_front import SPEC_NAMES, MmpFrontEnd
 from .trajectory_tracker import TrajectoryTracker
 
 HUMAN_SIZE = 0.2   # main_base.py:75, main_pre.py:18
@@ -205,8 +205,9 @@ class BatchEvaluator:
             raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; mmp with tracker = 'mpc'; None with tracker = 'dwa')")
         if mmp_stem is not None and predictor != "mmp":
             raise ValueError("mmp_stem needs predictor = 'mmp'")
-        mmp_stem, mmp_blocks, mmp_blocks2, mmp_blocks3, mmp_blocks4, mmp_head = MmpFrontEnd.check_specs(
-            mmp_stem, mmp_blocks, prefix="mmp_", blocks2=mmp_blocks2, blocks3=mmp_blocks3, blocks4=mmp_blocks4, head=mmp_head)
+        mmp_specs = MmpFrontEnd.check_specs(mmp_stem, mmp_blocks, prefix="mmp_", blocks2=mmp_blocks2, blocks3=mmp_blocks3, blocks4=mmp_blocks4,
+                                            head=mmp_head)
+        mmp_head = mmp_specs[-1]
         if predictor == "mmp":
             if self.n_hyp != 1 or not fused:
                 raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
@@ -312,7 +313,7 @@ class BatchEvaluator:
         else:
             self._init_dwa(robot_paths)
         if predictor == "mmp":
-            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_stem, mmp_blocks, mmp_blocks2, mmp_blocks3, mmp_blocks4, mmp_head)
+            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_specs)
 
     def _tensor(self, x):
         return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
@@ -373,11 +374,12 @@ class BatchEvaluator:
         self._info, self._evals = self._full(B, 8), self._full(B)
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
 
-    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, stem, blocks=None, blocks2=None, blocks3=None, blocks4=None,
-                  head=None):
+    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, specs):
         """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the device front
         end (``mmp_front``: its kernels, weights and buffers) and from it the shape of one row of the network's input -- the stack's
-        [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind fused blocks [16, Hp, Wp], or behind those of layer2 [32, H2, W2], or of layer3 [64, H3, W3], or of layer4 [128, H4, W4], or with a head the network's output [O] -- and the chunk."""
+        [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind the last fused stage its [channels, H, W], or with a
+        head the network's output [O] -- and the chunk. ``specs``: the six checked specs (``mmp_front.SPEC_NAMES``); they are kept as
+        ``mmp_stem``, ``mmp_blocks`` .. ``mmp_head`` with their arrays on the device."""
         img = np.ascontiguousarray(ref_image, dtype=np.float32)
         if img.ndim != 2:
             raise ValueError(f"ref_image must be [Hm, Wm], got {img.shape}")
@@ -389,9 +391,10 @@ class BatchEvaluator:
         # mmp_interface.py:60 snaps on 255 - ref_image; its grey levels decide the edges (Handle.set_map)
         self.h.set_map(255.0 - img.astype(np.float64))
         fe = self.mmp_front = MmpFrontEnd(self.h, self.dt, self.dev, self.mmp_Hm, self.mmp_Wm, self.N, transform, self.mmp_rescale, MMP_SIGMA,
-                                          self.mmp_ref, stem, blocks, blocks2, blocks3, blocks4, head)
-        self.mmp_row, self.mmp_stem, self.mmp_blocks, self.mmp_blocks2 = fe.row, fe.stem, fe.blocks, fe.blocks2  # (the specs with their arrays on the device)
-        self.mmp_blocks3, self.mmp_blocks4, self.mmp_head = fe.blocks3, fe.blocks4, fe.head
+                                          self.mmp_ref, *specs)
+        self.mmp_row = fe.row
+        for name in SPEC_NAMES:
+            setattr(self, "mmp_" + name, getattr(fe, name))
         self.mmp_chunk = int(mmp_chunk) if mmp_chunk is not None else max(1, MMP_INPUT_BYTES // fe.bytes_per_item)
 
     def _init_dwa(self, robot_paths):

@@ -29,7 +29,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from . import _capi
-from .mmp_front import MmpFrontEnd
+from .mmp_front import SPEC_NAMES, MmpFrontEnd
 from .snap import WorldTransform
 
 SIGMA = 20.0        # pre_load.py:128
@@ -57,8 +57,9 @@ class MmpInterface:
             raise TypeError(f"network must be a callable, got {type(network)}")
         self._prt_name = "MMPInterface"
         self.network = network
-        self.stem, self.blocks, self.blocks2, self.blocks3, self.blocks4, self.head = MmpFrontEnd.check_specs(
-            stem, blocks, blocks2=blocks2, blocks3=blocks3, blocks4=blocks4, head=head)
+        self._specs = MmpFrontEnd.check_specs(stem, blocks, blocks2=blocks2, blocks3=blocks3, blocks4=blocks4, head=head)
+        for name, spec in zip(SPEC_NAMES, self._specs):
+            setattr(self, name, spec)
         self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)
         self._map_of = {}         # pred_offset -> the ref_image its map was set from
         self._fronts = {}         # (pred_offset, Hm, Wm, rescale) -> device front end: the weights are uploaded once, the buffers reused
@@ -105,8 +106,7 @@ class MmpInterface:
         key = (N, Hm, Wm, float(rescale))
         if key not in self._fronts:
             d_ref = torch.empty(Hm, Wm, dtype=torch.float32, device=d_hist.device)
-            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, self.stem, self.blocks, self.blocks2, self.blocks3,
-                                            self.blocks4, self.head)
+            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, *self._specs)
             self._fronts[key].allocate(1)
         fe = self._fronts[key]
         fe.ref.copy_(torch.from_numpy(img))

@@ -11,35 +11,27 @@ The fold is done in float64 and rounded once to float: ``scale = gamma / sqrt(va
 (+ ``scale * bias`` for a convolution with a bias). It is only valid for a norm in inference mode: batch statistics couple the
 rows of a batch, which a per-pedestrian kernel cannot reproduce.
 
-The first residual stage behind the stem, ``resnet34.layer1`` = three ``BasicBlock`` s at 16 channels on the stem's
-resolution (net_module/net.py:45-61), can go the same way (``nmpc_mmp_block_f32``, csrc/nmpc_mmp_block.h): ``BlockSpec`` = both
-3 x 3 convolutions with their folded norms, the 1 x 1 projection of the first block (``None`` for the other two) and the two
-slopes -- 0.1 inside the block (``compact_conv_layer``), 0.01 behind the addition (a default ``nn.LeakyReLU``).
-``fold_block`` folds one block, ``split_network_layer1(net)`` returns the stem, the three blocks and the trunk from
-``layer2`` on, for ``BatchEvaluator(..., mmp_stem=spec, mmp_blocks=blocks, network=trunk)`` and
-``MmpInterface(trunk, stem=spec, blocks=blocks)``.
+The four residual stages behind the stem (net_module/net.py:45-61) go the same way, one fused kernel per ``BasicBlock``;
+``STAGES`` below is their table:
 
-The second residual stage, ``resnet34.layer2`` = four ``BasicBlock`` s at 32 channels, the first ``16 -> 32`` at stride 2 with a
-1 x 1, stride-2 projection (37 x 42 from 74 x 83 on the warehouse map), goes the same way through a second kernel family
-(``nmpc_mmp_block2_f32``, csrc/nmpc_mmp_block2.h): ``Block2Spec`` = ``BlockSpec`` 's fields plus ``stride`` (1 or 2, of the first
-convolution and the projection), ``fold_block2`` folds one block, ``split_network_layer2(net)`` returns the stem, the three blocks
-of layer1, the four of layer2 and the trunk from ``layer3`` on, for ``BatchEvaluator(..., mmp_stem=spec, mmp_blocks=blocks,
-mmp_blocks2=blocks2, network=trunk)`` and ``MmpInterface(trunk, stem=spec, blocks=blocks, blocks2=blocks2)``.
+    resnet34   channels   blocks   spec         fold          kernel                 header                  plane (warehouse)
+    layer1     16         3        BlockSpec    fold_block    nmpc_mmp_block_f32     csrc/nmpc_mmp_block.h   74 x 83
+    layer2     32         4        Block2Spec   fold_block2   nmpc_mmp_block2_f32    csrc/nmpc_mmp_block2.h  37 x 42
+    layer3     64         6        Block3Spec   fold_block3   nmpc_mmp_block3_f32    csrc/nmpc_mmp_block3.h  19 x 21
+    layer4     128        3        Block4Spec   fold_block4   nmpc_mmp_block4_f32    csrc/nmpc_mmp_block4.h  10 x 11
 
-The third residual stage, ``resnet34.layer3`` = six ``BasicBlock`` s at 64 channels, the first ``32 -> 64`` at stride 2 with a
-1 x 1, stride-2 projection (19 x 21 from 37 x 42), goes through a third kernel family (``nmpc_mmp_block3_f32``,
-csrc/nmpc_mmp_block3.h): ``Block3Spec`` has ``Block2Spec`` 's fields, ``fold_block3`` folds one block,
-``split_network_layer3(net)`` returns the stem, the blocks of layer1, layer2 and layer3 and the trunk from ``layer4`` on, for
-``BatchEvaluator(..., mmp_blocks3=blocks3)`` and ``MmpInterface(..., blocks3=blocks3)``.
-
-The fourth residual stage, ``resnet34.layer4`` = three ``BasicBlock`` s at 128 channels, the first ``64 -> 128`` at stride 2 with a
-1 x 1, stride-2 projection (10 x 11 from 19 x 21), goes through a fourth kernel family (``nmpc_mmp_block4_f32``,
-csrc/nmpc_mmp_block4.h): ``Block4Spec`` has ``Block3Spec`` 's fields, ``fold_block4`` folds one block,
-``split_network_layer4(net)`` returns the stem, the blocks of layer1 to layer4 and the trunk from ``apool`` on. The network's end
--- ``AvgPool2d(2, 2)``, flatten, ``fc1 = Linear(F, 128)``, ``leaky``, ``swarm.layer_hypos = Linear(128, 2 K)`` -- is one launch
-(``nmpc_mmp_head_f32``, csrc/nmpc_mmp_head.h): ``HeadSpec(w1, c1, slope, w2, c2)`` from ``fold_head``, and
-``split_network_whole(net)`` returns the stem, the four tuples of blocks and the head with NO trunk left, for
-``BatchEvaluator(..., mmp_blocks4=blocks4, mmp_head=head)`` and ``MmpInterface(None, ..., blocks4=blocks4, head=head)``."""
+A spec holds both 3 x 3 convolutions with their folded norms, the 1 x 1 projection of the stage's first block (``None`` for a block
+that adds the identity) and the two slopes -- 0.1 inside the block (``compact_conv_layer``), 0.01 behind the addition (a default
+``nn.LeakyReLU``). Layer1 runs at stride 1; the first block of each later stage halves the plane, so their specs also hold
+``stride`` (1 or 2, of the first convolution and of the projection). ``check_blocks`` .. ``check_blocks4`` check one stage's specs
+against what the stage in front gives. ``split_network_layer1`` .. ``split_network_layer4`` walk the table up to their stage and
+return the stem, one tuple of specs per stage and the trunk, a callable made of whatever remains, for ``BatchEvaluator(...,
+mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, ..., network=trunk)`` and ``MmpInterface(trunk, stem=spec, blocks=blocks,
+blocks2=blocks2, ...)``. The network's end -- ``AvgPool2d(2, 2)``, flatten,
+``fc1 = Linear(F, 128)``, ``leaky``, ``swarm.layer_hypos = Linear(128, 2 K)`` -- is one launch (``nmpc_mmp_head_f32``,
+csrc/nmpc_mmp_head.h): ``HeadSpec(w1, c1, slope, w2, c2)`` from ``fold_head``, and ``split_network_whole(net)`` returns the stem,
+the four tuples of blocks and the head with NO trunk left, for ``BatchEvaluator(..., mmp_blocks4=blocks4, mmp_head=head)`` and
+``MmpInterface(None, ..., blocks4=blocks4, head=head)``."""
 from __future__ import annotations
 
 from typing import Callable, NamedTuple, Optional, Tuple
@@ -71,57 +63,15 @@ class BlockSpec(NamedTuple):
 BLOCK_CHANNELS = 16                 # output channels of the fused block (csrc/nmpc_mmp_block.h)
 
 
-class Block2Spec(NamedTuple):
-    w1: np.ndarray                  # [32, Cin, 3, 3] float32
-    s1: np.ndarray                  # [32] float32
-    b1: np.ndarray                  # [32] float32
-    slope_mid: float
-    w2: np.ndarray                  # [32, 32, 3, 3] float32
-    s2: np.ndarray                  # [32]
-    b2: np.ndarray                  # [32]
-    wd: Optional[np.ndarray]        # [32, Cin] float32, or None: the identity (Cin == 32 and stride == 1)
-    sd: Optional[np.ndarray]        # [32] or None
-    bd: Optional[np.ndarray]        # [32] or None
-    slope_out: float
-    stride: int                     # 1 or 2: of the first convolution and of the projection
-
+# The strided stages' specs: BlockSpec's fields with C = 32 / 64 / 128 in place of 16 (the identity: Cin == C and stride == 1), then
+# ``stride`` = 1 or 2, of the first convolution and of the projection. One class per stage: its name is what the messages print.
+_STRIDED_FIELDS = [*BlockSpec.__annotations__.items(), ("stride", int)]
+Block2Spec = NamedTuple("Block2Spec", _STRIDED_FIELDS)
+Block3Spec = NamedTuple("Block3Spec", _STRIDED_FIELDS)
+Block4Spec = NamedTuple("Block4Spec", _STRIDED_FIELDS)
 
 BLOCK2_CHANNELS = 32                # output channels of the fused strided block (csrc/nmpc_mmp_block2.h)
-
-
-class Block3Spec(NamedTuple):
-    w1: np.ndarray                  # [64, Cin, 3, 3] float32
-    s1: np.ndarray                  # [64] float32
-    b1: np.ndarray                  # [64] float32
-    slope_mid: float
-    w2: np.ndarray                  # [64, 64, 3, 3] float32
-    s2: np.ndarray                  # [64]
-    b2: np.ndarray                  # [64]
-    wd: Optional[np.ndarray]        # [64, Cin] float32, or None: the identity (Cin == 64 and stride == 1)
-    sd: Optional[np.ndarray]        # [64] or None
-    bd: Optional[np.ndarray]        # [64] or None
-    slope_out: float
-    stride: int                     # 1 or 2: of the first convolution and of the projection
-
-
 BLOCK3_CHANNELS = 64                # output channels of the third stage's fused block (csrc/nmpc_mmp_block3.h)
-
-
-class Block4Spec(NamedTuple):
-    w1: np.ndarray                  # [128, Cin, 3, 3] float32
-    s1: np.ndarray                  # [128] float32
-    b1: np.ndarray                  # [128] float32
-    slope_mid: float
-    w2: np.ndarray                  # [128, 128, 3, 3] float32
-    s2: np.ndarray                  # [128]
-    b2: np.ndarray                  # [128]
-    wd: Optional[np.ndarray]        # [128, Cin] float32, or None: the identity (Cin == 128 and stride == 1)
-    sd: Optional[np.ndarray]        # [128] or None
-    bd: Optional[np.ndarray]        # [128] or None
-    slope_out: float
-    stride: int                     # 1 or 2: of the first convolution and of the projection
-
-
 BLOCK4_CHANNELS = 128               # output channels of the fourth stage's fused block (csrc/nmpc_mmp_block4.h)
 
 
@@ -211,14 +161,24 @@ def split_network(net) -> Tuple[StemSpec, Callable]:
     if len(parts) != 3:
         raise ValueError("split_network: 'resnet34.stem.conv1' is not Sequential(Conv2d, BatchNorm2d, LeakyReLU)")
     spec = fold_stem(parts[0], parts[1], parts[2], pool)
-    layers = [need(net, "resnet34." + n) for n in ("layer1", "layer2", "layer3", "layer4", "apool")]
-    fc1, leaky, swarm = need(net, "fc1"), need(net, "leaky"), need(net, "swarm")
+    for path in [*("resnet34." + n for n in _BODY), "fc1", "leaky", "swarm"]:
+        need(net, path)
+    return spec, _trunk(net, 0)
+
+
+_BODY = ("layer1", "layer2", "layer3", "layer4", "apool")       # of ``net.resnet34``, behind the stem
+
+
+def _trunk(net, n):
+    """The network from the ``n`` th member of ``_BODY`` on as a callable on that member's input (parameters shared with ``net``)."""
+    layers = [getattr(net.resnet34, name) for name in _BODY[n:]]
+    fc1, leaky, swarm = net.fc1, net.leaky, net.swarm
 
     def trunk(x):
         for layer in layers:
             x = layer(x)
         return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
-    return spec, trunk
+    return trunk
 
 
 def _conv_norm(name, seq, n_parts):
@@ -313,43 +273,6 @@ def check_block(spec) -> BlockSpec:
         if not np.isfinite(float(getattr(spec, name))) or abs(float(getattr(spec, name))) > 1.0:
             raise ValueError(f"BlockSpec: {name} = {getattr(spec, name)}")
     return BlockSpec(w1, s1, b1, float(spec.slope_mid), w2, s2, b2, wd, sd, bd, float(spec.slope_out))
-
-
-def check_blocks(stem: StemSpec, blocks) -> Tuple[BlockSpec, ...]:
-    """The blocks behind ``stem`` as a tuple of checked specs: the first takes the stem's channels, each later one is 16 -> 16."""
-    blocks = tuple(check_block(b) for b in blocks)
-    if not blocks:
-        raise ValueError("mmp_blocks: at least one BlockSpec is needed")
-    cin = int(stem.weight.shape[0])
-    for i, b in enumerate(blocks):
-        if b.w1.shape[1] != cin:
-            raise ValueError(f"mmp_blocks: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive "
-                             f"({'the stem has C = ' + str(cin) if i == 0 else 'every block gives 16'})")
-        cin = BLOCK_CHANNELS
-    return blocks
-
-
-def split_network_layer1(net) -> Tuple[StemSpec, Tuple[BlockSpec, BlockSpec, BlockSpec], Callable]:
-    """As ``split_network``, with ``resnet34.layer1`` (three blocks, ``fold_block``) taken off the trunk as well:
-    ``(StemSpec, (BlockSpec, BlockSpec, BlockSpec), trunk)``; the trunk, a callable on ``[M, 16, Hp, Wp]``, is ``layer2 .. layer4``,
-    ``apool``, flatten, ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
-    spec, _ = split_network(net)
-    body = net.resnet34
-    try:
-        l1 = list(body.layer1)
-    except TypeError:
-        l1 = []
-    if len(l1) != 3:
-        raise ValueError("split_network_layer1: 'resnet34.layer1' is not a Sequential of three blocks")
-    blocks = check_blocks(spec, [fold_block(b) for b in l1])
-    layers = [getattr(body, n) for n in ("layer2", "layer3", "layer4", "apool")]
-    fc1, leaky, swarm = net.fc1, net.leaky, net.swarm
-
-    def trunk(x):
-        for layer in layers:
-            x = layer(x)
-        return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
-    return spec, blocks, trunk
 
 
 def block2_plane(H: int, W: int, stride: int) -> Tuple[int, int]:
@@ -468,103 +391,6 @@ def check_block4(spec) -> Block4Spec:
     return _check_strided(spec, BLOCK4_CHANNELS, Block4Spec)
 
 
-def check_blocks2(blocks, blocks2) -> Tuple[Block2Spec, ...]:
-    """The layer-2 blocks behind the (checked) layer-1 ``blocks`` as a tuple of checked specs: the first takes the 16 channels layer1
-    gives, each later one is 32 -> 32."""
-    if not blocks:
-        raise ValueError("mmp_blocks2: the blocks of layer1 are needed in front")
-    blocks2 = tuple(check_block2(b) for b in blocks2)
-    if not blocks2:
-        raise ValueError("mmp_blocks2: at least one Block2Spec is needed")
-    cin = BLOCK_CHANNELS
-    for i, b in enumerate(blocks2):
-        if b.w1.shape[1] != cin:
-            raise ValueError(f"mmp_blocks2: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive "
-                             f"({'layer1 gives 16' if i == 0 else 'every block of layer2 gives 32'})")
-        cin = BLOCK2_CHANNELS
-    return blocks2
-
-
-def split_network_layer2(net) -> Tuple[StemSpec, Tuple[BlockSpec, ...], Tuple[Block2Spec, ...], Callable]:
-    """As ``split_network_layer1``, with ``resnet34.layer2`` (four blocks, ``fold_block2``) taken off the trunk as well:
-    ``(StemSpec, blocks, blocks2, trunk)``; the trunk, a callable on ``[M, 32, H2, W2]``, is ``layer3``, ``layer4``, ``apool``,
-    flatten, ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
-    spec, blocks, _ = split_network_layer1(net)
-    body = net.resnet34
-    try:
-        l2 = list(body.layer2)
-    except TypeError:
-        l2 = []
-    if len(l2) != 4:
-        raise ValueError("split_network_layer2: 'resnet34.layer2' is not a Sequential of four blocks")
-    blocks2 = check_blocks2(blocks, [fold_block2(b) for b in l2])
-    layers = [getattr(body, n) for n in ("layer3", "layer4", "apool")]
-    fc1, leaky, swarm = net.fc1, net.leaky, net.swarm
-
-    def trunk(x):
-        for layer in layers:
-            x = layer(x)
-        return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
-    return spec, blocks, blocks2, trunk
-
-
-def check_blocks3(blocks2, blocks3) -> Tuple[Block3Spec, ...]:
-    """The layer-3 blocks behind the (checked) layer-2 ``blocks2`` as a tuple of checked specs: the first takes the 32 channels layer2
-    gives, each later one is 64 -> 64."""
-    if not blocks2:
-        raise ValueError("mmp_blocks3: the blocks of layer2 are needed in front")
-    blocks3 = tuple(check_block3(b) for b in blocks3)
-    if not blocks3:
-        raise ValueError("mmp_blocks3: at least one Block3Spec is needed")
-    cin = BLOCK2_CHANNELS
-    for i, b in enumerate(blocks3):
-        if b.w1.shape[1] != cin:
-            raise ValueError(f"mmp_blocks3: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive "
-                             f"({'layer2 gives 32' if i == 0 else 'every block of layer3 gives 64'})")
-        cin = BLOCK3_CHANNELS
-    return blocks3
-
-
-def split_network_layer3(net) -> Tuple[StemSpec, Tuple[BlockSpec, ...], Tuple[Block2Spec, ...], Tuple[Block3Spec, ...], Callable]:
-    """As ``split_network_layer2``, with ``resnet34.layer3`` (six blocks, ``fold_block3``) taken off the trunk as well:
-    ``(StemSpec, blocks, blocks2, blocks3, trunk)``; the trunk, a callable on ``[M, 64, H3, W3]``, is ``layer4``, ``apool``,
-    flatten, ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
-    spec, blocks, blocks2, _ = split_network_layer2(net)
-    body = net.resnet34
-    try:
-        l3 = list(body.layer3)
-    except TypeError:
-        l3 = []
-    if len(l3) != 6:
-        raise ValueError("split_network_layer3: 'resnet34.layer3' is not a Sequential of six blocks")
-    blocks3 = check_blocks3(blocks2, [fold_block3(b) for b in l3])
-    layers = [getattr(body, n) for n in ("layer4", "apool")]
-    fc1, leaky, swarm = net.fc1, net.leaky, net.swarm
-
-    def trunk(x):
-        for layer in layers:
-            x = layer(x)
-        return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
-    return spec, blocks, blocks2, blocks3, trunk
-
-
-def check_blocks4(blocks3, blocks4) -> Tuple[Block4Spec, ...]:
-    """The layer-4 blocks behind the (checked) layer-3 ``blocks3`` as a tuple of checked specs: the first takes the 64 channels layer3
-    gives, each later one is 128 -> 128."""
-    if not blocks3:
-        raise ValueError("mmp_blocks4: the blocks of layer3 are needed in front")
-    blocks4 = tuple(check_block4(b) for b in blocks4)
-    if not blocks4:
-        raise ValueError("mmp_blocks4: at least one Block4Spec is needed")
-    cin = BLOCK3_CHANNELS
-    for i, b in enumerate(blocks4):
-        if b.w1.shape[1] != cin:
-            raise ValueError(f"mmp_blocks4: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive "
-                             f"({'layer3 gives 64' if i == 0 else 'every block of layer4 gives 128'})")
-        cin = BLOCK4_CHANNELS
-    return blocks4
-
-
 def _linear(fn, name, layer, n_in, n_out):
     """(weight [out, in], bias [out]) of a ``torch.nn.Linear`` -like ``layer`` as float32; a missing bias is zeros."""
     import torch
@@ -622,33 +448,108 @@ def head_features(C: int, H: int, W: int) -> int:
     return int(C) * (int(H) // 2) * (int(W) // 2)
 
 
-def _layer4(net, fn):
-    try:
-        l4 = list(net.resnet34.layer4)
-    except TypeError:
-        l4 = []
-    if len(l4) != 3:
-        raise ValueError(f"{fn}: 'resnet34.layer4' is not a Sequential of three blocks")
-    return l4
+class Stage(NamedTuple):
+    """One residual stage as the device runs it."""
+    layer: str          # its attribute on ``net.resnet34``
+    arg: str            # its specs in the callers' keywords (``mmp_`` + arg in ``BatchEvaluator``) and in the messages
+    channels: int       # output channels of each of its blocks
+    count: int          # blocks the reference's network has
+    word: str           # ... in the messages
+    Spec: type
+    fold: Callable      # one block module -> Spec
+    check: Callable     # one spec -> Spec, checked
+
+
+STAGES = (Stage("layer1", "blocks", BLOCK_CHANNELS, 3, "three", BlockSpec, fold_block, check_block),
+          Stage("layer2", "blocks2", BLOCK2_CHANNELS, 4, "four", Block2Spec, fold_block2, check_block2),
+          Stage("layer3", "blocks3", BLOCK3_CHANNELS, 6, "six", Block3Spec, fold_block3, check_block3),
+          Stage("layer4", "blocks4", BLOCK4_CHANNELS, 3, "three", Block4Spec, fold_block4, check_block4))
+
+
+def check_stage(k: int, front, blocks) -> tuple:
+    """The specs of ``STAGES[k]`` checked one by one and as a chain: the first block takes the channels that arrive from ``front`` --
+    the (checked) ``StemSpec`` for layer1, the (checked) specs of ``STAGES[k - 1]`` otherwise --, each later one what a block gives."""
+    st = STAGES[k]
+    if k == 0:
+        cin = int(front.weight.shape[0])
+        arrives, gives = f"the stem has C = {cin}", f"every block gives {st.channels}"
+    else:
+        prev = STAGES[k - 1]
+        if not front:
+            raise ValueError(f"mmp_{st.arg}: the blocks of {prev.layer} are needed in front")
+        cin, arrives, gives = prev.channels, f"{prev.layer} gives {prev.channels}", f"every block of {st.layer} gives {st.channels}"
+    blocks = tuple(st.check(b) for b in blocks)
+    if not blocks:
+        raise ValueError(f"mmp_{st.arg}: at least one {st.Spec.__name__} is needed")
+    for i, b in enumerate(blocks):
+        if b.w1.shape[1] != cin:
+            raise ValueError(f"mmp_{st.arg}: block {i} takes {b.w1.shape[1]} channels, but {cin} arrive ({arrives if i == 0 else gives})")
+        cin = st.channels
+    return blocks
+
+
+def check_blocks(stem: StemSpec, blocks) -> Tuple[BlockSpec, ...]:
+    """The blocks behind ``stem`` as a tuple of checked specs: the first takes the stem's channels, each later one is 16 -> 16."""
+    return check_stage(0, stem, blocks)
+
+
+def check_blocks2(blocks, blocks2) -> Tuple[Block2Spec, ...]:
+    """The layer-2 blocks behind the (checked) layer-1 ``blocks``: the first takes the 16 channels layer1 gives, each later one is 32 -> 32."""
+    return check_stage(1, blocks, blocks2)
+
+
+def check_blocks3(blocks2, blocks3) -> Tuple[Block3Spec, ...]:
+    """The layer-3 blocks behind the (checked) layer-2 ``blocks2``: the first takes 32 channels, each later one is 64 -> 64."""
+    return check_stage(2, blocks2, blocks3)
+
+
+def check_blocks4(blocks3, blocks4) -> Tuple[Block4Spec, ...]:
+    """The layer-4 blocks behind the (checked) layer-3 ``blocks3``: the first takes 64 channels, each later one is 128 -> 128."""
+    return check_stage(3, blocks3, blocks4)
+
+
+def _walk(net, n: int, fn: Optional[str] = None) -> list:
+    """``[StemSpec, specs of STAGES[0], ..., specs of STAGES[n - 1]]`` of a module shaped as ``split_network`` takes it. A refusal
+    names the function that takes the offending stage off first, ``split_network_<layer>`` -- or ``fn`` for the last stage."""
+    out = [split_network(net)[0]]
+    for k, st in enumerate(STAGES[:n]):
+        try:
+            members = list(getattr(net.resnet34, st.layer))
+        except TypeError:
+            members = []
+        if len(members) != st.count:
+            raise ValueError(f"{fn if fn and k == n - 1 else 'split_network_' + st.layer}: 'resnet34.{st.layer}' is not a Sequential of "
+                             f"{st.word} blocks")
+        out.append(check_stage(k, out[-1], [st.fold(b) for b in members]))
+    return out
+
+
+def split_network_layer1(net) -> Tuple[StemSpec, Tuple[BlockSpec, BlockSpec, BlockSpec], Callable]:
+    """As ``split_network``, with ``resnet34.layer1`` (three blocks, ``fold_block``) taken off the trunk as well:
+    ``(StemSpec, (BlockSpec, BlockSpec, BlockSpec), trunk)``; the trunk, a callable on ``[M, 16, Hp, Wp]``, is ``layer2 .. layer4``,
+    ``apool``, flatten, ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
+    return (*_walk(net, 1), _trunk(net, 1))
+
+
+def split_network_layer2(net) -> Tuple[StemSpec, Tuple[BlockSpec, ...], Tuple[Block2Spec, ...], Callable]:
+    """With ``resnet34.layer2`` (four blocks, ``fold_block2``) taken off as well: ``(StemSpec, blocks, blocks2, trunk)``; the trunk, a
+    callable on ``[M, 32, H2, W2]``, starts at ``layer3``."""
+    return (*_walk(net, 2), _trunk(net, 2))
+
+
+def split_network_layer3(net) -> Tuple[StemSpec, Tuple[BlockSpec, ...], Tuple[Block2Spec, ...], Tuple[Block3Spec, ...], Callable]:
+    """With ``resnet34.layer3`` (six blocks, ``fold_block3``) taken off as well: ``(StemSpec, blocks, blocks2, blocks3, trunk)``; the
+    trunk, a callable on ``[M, 64, H3, W3]``, starts at ``layer4``."""
+    return (*_walk(net, 3), _trunk(net, 3))
 
 
 def split_network_layer4(net):
-    """As ``split_network_layer3``, with ``resnet34.layer4`` (three blocks, ``fold_block4``) taken off the trunk as well:
-    ``(StemSpec, blocks, blocks2, blocks3, blocks4, trunk)``; the trunk, a callable on ``[M, 128, H4, W4]``, is ``apool``, flatten,
-    ``fc1``, ``leaky``, ``swarm`` (parameters shared with ``net``)."""
-    spec, blocks, blocks2, blocks3, _ = split_network_layer3(net)
-    blocks4 = check_blocks4(blocks3, [fold_block4(b) for b in _layer4(net, "split_network_layer4")])
-    apool, fc1, leaky, swarm = net.resnet34.apool, net.fc1, net.leaky, net.swarm
-
-    def trunk(x):
-        x = apool(x)
-        return swarm(leaky(fc1(x.reshape(x.shape[0], -1))))
-    return spec, blocks, blocks2, blocks3, blocks4, trunk
+    """With ``resnet34.layer4`` (three blocks, ``fold_block4``) taken off as well: ``(StemSpec, blocks, blocks2, blocks3, blocks4,
+    trunk)``; the trunk, a callable on ``[M, 128, H4, W4]``, is ``apool``, flatten, ``fc1``, ``leaky``, ``swarm``."""
+    return (*_walk(net, 4), _trunk(net, 4))
 
 
 def split_network_whole(net):
     """The whole network as folded weights, with no torch module left to call: ``(StemSpec, blocks, blocks2, blocks3, blocks4,
     HeadSpec)`` -- ``split_network_layer4`` with its trunk folded by ``fold_head``."""
-    spec, blocks, blocks2, blocks3, _ = split_network_layer3(net)
-    blocks4 = check_blocks4(blocks3, [fold_block4(b) for b in _layer4(net, "split_network_whole")])
-    return spec, blocks, blocks2, blocks3, blocks4, fold_head(net.resnet34.apool, net.fc1, net.leaky, net.swarm)
+    return (*_walk(net, 4, "split_network_whole"), fold_head(net.resnet34.apool, net.fc1, net.leaky, net.swarm))

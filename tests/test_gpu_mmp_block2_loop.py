@@ -261,7 +261,7 @@ def test_front_end_with_blocks2(handle, fworld, C):
     items = torch.tensor(ITEMS, dtype=torch.long, device="cuda")
     fe, parent = _front(handle, fworld, C), _front(handle, fworld, C, blocks2=None)
     inside = C == 64
-    assert fe._pp2_in_fill == inside and fe.row == (32, H2, W2) and fe.fill_row == (C, HP, WP) and parent.row == (16, HP, WP)
+    assert fe.stage("layer2").in_fill == inside and fe.row == (32, H2, W2) and fe.fill_row == (C, HP, WP) and parent.row == (16, HP, WP)
     assert parent.bytes_per_item == N_OFF * (C + 32) * HP * WP * 4
     assert fe.bytes_per_item == parent.bytes_per_item + (0 if inside else N_OFF * 2 * 32 * H2 * W2 * 4)
     fe.allocate(CHUNK)

@@ -274,15 +274,16 @@ def test_front_end_with_blocks3(handle, fworld, C):
     fe, parent = _front(handle, fworld, C), _front(handle, fworld, C, blocks3=None)
     inside = C == 64
     # without blocks3 nothing moves: the row, the parts and the bytes are those of the layer2 front end
-    assert parent._pp2_in_fill == inside and not parent._pp3_in_fill and parent.row == (32, H2, W2) and parent.blocks3 is None
+    assert parent.stage("layer2").in_fill == inside and parent.stage("layer3") is None and parent.row == (32, H2, W2) and parent.blocks3 is None
     assert parent.bytes_per_item == N_OFF * (C + 32) * HP * WP * 4 + (0 if inside else N_OFF * 2 * 32 * H2 * W2 * 4)
-    assert fe._pp3_in_fill == inside and fe._pp2_in_fill == inside and fe.row == (64, H3, W3) and fe.fill_row == (C, HP, WP)
+    assert fe.stage("layer3").in_fill == inside and fe.stage("layer2").in_fill == inside and fe.row == (64, H3, W3) and fe.fill_row == (C, HP, WP)
     assert fe.bytes_per_item == parent.bytes_per_item + (0 if inside else N_OFF * 2 * 64 * H3 * W3 * 4)
     fe.allocate(CHUNK)
     parent.allocate(CHUNK)
     if inside:                                             # behind layer2's two buffers, inside the stem's output
         lo, hi = fe._fill_buf.data_ptr(), fe._fill_buf.data_ptr() + fe._fill_buf.numel() * 4
-        assert fe._pp3.data_ptr() == fe._pp2.data_ptr() + fe._pp2.numel() * 4 and lo == fe._pp2.data_ptr() and fe._pp3.data_ptr() + fe._pp3.numel() * 4 <= hi
+        pp2, pp3 = fe.stage("layer2").pp, fe.stage("layer3").pp
+        assert pp3.data_ptr() == pp2.data_ptr() + pp2.numel() * 4 and lo == pp2.data_ptr() and pp3.data_ptr() + pp3.numel() * 4 <= hi
     args = (fworld["d_hist"].data_ptr(), fworld["d_hcount"].data_ptr(), FB, FH)
     chunks = []
     for c0 in range(0, len(ITEMS), CHUNK):

@@ -233,15 +233,16 @@ def test_front_end_with_blocks4_and_head(handle, fworld, C):
     fe, parent = _front(handle, fworld, C), _front(handle, fworld, C, blocks4=None, head=None)
     inside = C == 64
     # without the new arguments nothing moves: the row, the parts and the bytes are those of the layer3 front end
-    assert parent.row == (64, H3, W3) and parent.blocks4 is None and parent.head is None and not parent._pp4_in_fill
+    assert parent.row == (64, H3, W3) and parent.blocks4 is None and parent.head is None and parent.stage("layer4") is None
     assert parent.bytes_per_item == N_OFF * (C + 32) * HP * WP * 4 + (0 if inside else N_OFF * (2 * 32 * 5 * 6 + 2 * 64 * H3 * W3) * 4)
-    assert fe._pp4_in_fill == inside and fe.row == (O,) and fe.fill_row == (C, HP, WP)
+    assert fe.stage("layer4").in_fill == inside and fe.row == (O,) and fe.fill_row == (C, HP, WP)
     assert fe.bytes_per_item == parent.bytes_per_item + (0 if inside else N_OFF * 2 * 128 * H4 * W4 * 4) + N_OFF * O * 4
     fe.allocate(CHUNK)
     parent.allocate(CHUNK)
     if inside:                                             # behind layer3's two buffers, inside the stem's output
         hi = fe._fill_buf.data_ptr() + fe._fill_buf.numel() * 4
-        assert fe._pp4.data_ptr() == fe._pp3.data_ptr() + fe._pp3.numel() * 4 and fe._pp4.data_ptr() + fe._pp4.numel() * 4 <= hi
+        pp3, pp4 = fe.stage("layer3").pp, fe.stage("layer4").pp
+        assert pp4.data_ptr() == pp3.data_ptr() + pp3.numel() * 4 and pp4.data_ptr() + pp4.numel() * 4 <= hi
     args = (fworld["d_hist"].data_ptr(), fworld["d_hcount"].data_ptr(), FB, FH)
     chunks = []
     for c0 in range(0, len(ITEMS), CHUNK):
