@@ -100,7 +100,7 @@ def _case(dims, hint, elem, B, S, order=0, staging=1, **ov):
 
 @pytest.mark.parametrize("S", [1024, 1216, 416])
 def test_plans_of_the_warm_start_suite(plan, S):
-    """The five expectations of plans() in tests/test_gpu_plan_warmstart.py (configs[1]'s dimensions, hint 10: the 4-slot tables;
+    """The five expectations of plans() in tests/plan_cases.py, run by tests/test_gpu_plan_warmstart.py (configs[1]'s dimensions, hint 10: the 4-slot tables;
     nmpc_last_launch_info's family / order_source / staged_outer_iterations / tail_handed_off), for several device sizes."""
     dims, hint, park = (20, 10, 10, 15), 10, max(32, S // 4)
     want = [("latency-evaluation-order", 4, 3 * S // 4, dict(mode=LATENCY, last_order=2, last_staged=0, last_tail=0), None),
