@@ -16,7 +16,8 @@ Host side (Python, mirrors the reference's interface for the solve path only):
 * :mod:`.kfmp_interface`     -- ``KfmpInterface.get_motion_prediction`` (``interfaces/kfmp_interface.py:14-56``): the Kalman-filter
                                 pedestrian predictor, filtered on the device (``nmpc_kf_predict_*``)
 * :mod:`.dwa_interface`      -- ``DwaInterface.run_step`` (``interfaces/dwa_interface.py:20-66``): the dynamic-window baseline tracker,
-                                evaluated on the device (``nmpc_dwa_step_*``)
+                                evaluated on the device (``nmpc_dwa_step_*``; lists of unequal length per offset:
+                                ``nmpc_dwa_step_lists_*``)
 * :mod:`.tcp`                -- OpEn's TCP/JSON wire format in front of the solver + the ``OptimizerTcpManager`` surface
                                 used by ``TrajectoryTracker(use_tcp=True)`` (row f4)
 * :mod:`.snap`               -- ``WorldTransform`` and ``edge_map`` for ``Handle.set_map`` / ``Handle.snap_hypotheses``: the

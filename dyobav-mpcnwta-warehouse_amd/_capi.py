@@ -114,6 +114,13 @@ class NmpcDwaArgs(C.Structure):
         return self
 
 
+class NmpcDwaListsArgs(C.Structure):
+    """Mirror of ``struct nmpc_dwa_lists_args`` (device pointers): the fields of ``NmpcDwaArgs`` with ``R`` (rows per scenario) in the
+    place of ``reserved``, then ``dyn_count`` [n_run, N+1] int32; ``H`` and ``dyn_mode`` are not read."""
+    _fields_ = [(("R" if n == "reserved" else n), t) for n, t in NmpcDwaArgs._fields_] + [("dyn_count", C.c_void_p)]
+    set_config = NmpcDwaArgs.set_config
+
+
 def set_world_transform(args, transform, rescale: float = 1.0):
     """The constants of a :class:`.snap.WorldTransform` and ``rescale`` into ``args`` (any struct with these field names), returned."""
     args.x_reverse, args.y_reverse = int(bool(transform.x_reverse)), int(bool(transform.y_reverse))
@@ -196,9 +203,11 @@ EXPORTED_SYMBOLS = (
     "nmpc_solve_batch_f32", "nmpc_solve_batch_f64", "nmpc_solve_trace_f64", "nmpc_eval_batch_f32", "nmpc_eval_batch_f64",
     "nmpc_assemble_params_f32", "nmpc_assemble_params_f64",
     "nmpc_hypotheses_to_ellipses_f32", "nmpc_hypotheses_to_ellipses_f64",
+    "nmpc_hypotheses_to_ellipses_counts_f32", "nmpc_hypotheses_to_ellipses_counts_f64",
     "nmpc_set_map", "nmpc_snap_hypotheses_f32", "nmpc_snap_hypotheses_f64",
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
+    "nmpc_dwa_step_lists_f32", "nmpc_dwa_step_lists_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
     "nmpc_mmp_block2_f32", "nmpc_mmp_block3_f32", "nmpc_mmp_block4_f32", "nmpc_mmp_head_f32",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
@@ -282,11 +291,14 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
         getattr(lib, "nmpc_assemble_params_" + sfx).argtypes = [vp, C.POINTER(NmpcAssembleArgs), i32, vp]
         getattr(lib, "nmpc_hypotheses_to_ellipses_" + sfx).argtypes = [vp, vp, i32, vp, i32, C.c_double, C.c_double,
                                                                        C.c_double, C.c_double, i32, vp, vp]
+        getattr(lib, "nmpc_hypotheses_to_ellipses_counts_" + sfx).argtypes = [vp, vp, i32, vp, i32, C.c_double, C.c_double,
+                                                                              C.c_double, C.c_double, i32, vp, vp, vp]
         getattr(lib, "nmpc_snap_hypotheses_" + sfx).argtypes = [vp, vp, C.POINTER(NmpcSnapArgs), i32, vp]
         getattr(lib, "nmpc_loop_pre_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
         getattr(lib, "nmpc_loop_post_" + sfx).argtypes = [vp, C.POINTER(NmpcLoopArgs)]
         getattr(lib, "nmpc_kf_predict_" + sfx).argtypes = [vp, C.POINTER(NmpcKfArgs)]
         getattr(lib, "nmpc_dwa_step_" + sfx).argtypes = [vp, C.POINTER(NmpcDwaArgs)]
+        getattr(lib, "nmpc_dwa_step_lists_" + sfx).argtypes = [vp, C.POINTER(NmpcDwaListsArgs)]
         getattr(lib, "nmpc_mmp_input_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpArgs)]
         getattr(lib, "nmpc_mmp_stem_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpStemArgs)]
     lib.nmpc_mmp_stem_shape.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -508,6 +520,13 @@ class Handle:
         fn = getattr(self._lib, "nmpc_dwa_step_" + _suffix(dtype))
         _check(fn(self._h, C.byref(args) if args is not None else None))
 
+    def dwa_step_lists(self, dtype, args: "NmpcDwaListsArgs"):
+        """``nmpc_dwa_step_lists_*``: the dynamic-window tracker over per-offset lists -- ``dyn_c[n_run, R, N+1, 6]`` with
+        ``dyn_count[n_run, N+1]`` (int32), as ``hypotheses_to_ellipses(..., counts=)`` writes them; everything else as ``dwa_step``
+        with ``dyn_mode`` 2. One launch enqueued on the handle's stream."""
+        fn = getattr(self._lib, "nmpc_dwa_step_lists_" + _suffix(dtype))
+        _check(fn(self._h, C.byref(args) if args is not None else None))
+
     def mmp_input(self, dtype, args: "NmpcMmpArgs"):
         """``nmpc_mmp_input_*``: the float32 input stack ``out[n_item, n_off, 7, Hm, Wm]`` of the multi-hypothesis predictor's
         network from the pedestrians' ``hist`` / ``hcount`` rows (``dtype``: the element type of ``hist``), one launch enqueued
@@ -550,14 +569,18 @@ class Handle:
         _check(self._lib.nmpc_mmp_head_f32(self._h, C.byref(args) if args is not None else None))
 
     def hypotheses_to_ellipses(self, dtype, hypos, cur, dyn_out, n_obs_out=None, human_size=0.2, eps=1.0, enlarge=2.0,
-                               extra_margin=0.0):
+                               extra_margin=0.0, counts=None):
         """``nmpc_hypotheses_to_ellipses_*``: device tensors ``hypos[B,N,P,2]``, ``cur[B,H,2]`` ->
-        ``dyn_out[B,Ndynobs,N+1,6]`` (+ ``n_obs_out[B]`` int32)."""
+        ``dyn_out[B,Ndynobs,N+1,6]`` (+ ``n_obs_out[B]`` int32). ``counts``: an int32 device tensor ``[B,N+1]`` for the rows per
+        offset that are clusters (``nmpc_hypotheses_to_ellipses_counts_*``; ``dyn_out`` and ``n_obs_out`` are the same bits)."""
         B, P, H = int(hypos.shape[0]), int(hypos.shape[2]), int(cur.shape[1])
-        fn = getattr(self._lib, "nmpc_hypotheses_to_ellipses_" + _suffix(dtype))
         p = _Arg.ptr
-        _check(fn(self._h, p(hypos), P, p(cur), H, float(human_size), float(eps), float(enlarge), float(extra_margin),
-                  B, p(dyn_out), p(n_obs_out)))
+        args = (self._h, p(hypos), P, p(cur), H, float(human_size), float(eps), float(enlarge), float(extra_margin), B, p(dyn_out),
+                p(n_obs_out))
+        if counts is None:
+            _check(getattr(self._lib, "nmpc_hypotheses_to_ellipses_" + _suffix(dtype))(*args))
+        else:
+            _check(getattr(self._lib, "nmpc_hypotheses_to_ellipses_counts_" + _suffix(dtype))(*args, p(counts)))
 
     def set_map(self, occupied, edge=None):
         """``nmpc_set_map``: host arrays ``occupied[H, W]`` (non-zero = occupied; for the reference: ``255 - label > 0``)

@@ -1378,14 +1378,15 @@ int assemble_params(nmpc_handle_s* h, const nmpc_assemble_args* g, int32_t B, T*
 
 template <typename T>
 int hypotheses_to_ellipses(nmpc_handle_s* h, const T* hypos, int32_t P, const T* cur, int32_t H, double human_size,
-                           double eps, double enlarge, double extra_margin, int32_t B, T* dyn, int32_t* n_obs)
+                           double eps, double enlarge, double extra_margin, int32_t B, T* dyn, int32_t* n_obs, int32_t* counts = nullptr)
 {
     if (!h || !hypos || !cur || !dyn) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
     if (B <= 0) return B == 0 ? 0 : fail(NMPC_ERR_INVALID_ARGUMENT, "B = %d < 0", B);
     if (P < 1 || P > 256) return fail(NMPC_ERR_UNSUPPORTED, "P = %d hypothesis points per time offset outside [1, 256]", P);
     if (h->cfg.N_hor > 64) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_hypotheses_to_ellipses: N_hor = %d > 64", h->cfg.N_hor);
     if (H < 0 || H > h->cfg.Ndynobs) return fail(NMPC_ERR_INVALID_ARGUMENT, "H = %d outside [0, Ndynobs]", H);
-    if (!is_device_ptr(hypos) || !is_device_ptr(cur) || !is_device_ptr(dyn) || (n_obs && !is_device_ptr(n_obs)))
+    if (!is_device_ptr(hypos) || !is_device_ptr(cur) || !is_device_ptr(dyn) || (n_obs && !is_device_ptr(n_obs)) ||
+        (counts && !is_device_ptr(counts)))
         return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_hypotheses_to_ellipses: every array must be a device pointer");
     HIP_TRY(hipSetDevice(h->cfg.device_id));
     nmpc::HypParams<T> a;
@@ -1402,6 +1403,7 @@ int hypotheses_to_ellipses(nmpc_handle_s* h, const T* hypos, int32_t P, const T*
     a.cur = cur;
     a.dyn = dyn;
     a.n_obs = n_obs;
+    a.counts = counts;
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     if (P <= 32)
         hipLaunchKernelGGL((nmpc::hypotheses_kernel<T, unsigned>), dim3(B), dim3(64), 0, h->stream, a);
@@ -1894,42 +1896,67 @@ static long long dwa_axis_bound(double range, double acc, double ts, double res)
     return q < 1e9 ? (long long)q + 1 : 1000000000LL;
 }
 
-template <typename T>
-int dwa_step(nmpc_handle_s* h, const nmpc_dwa_args* g)
+// LISTS: nmpc_dwa_step_lists_* on nmpc_dwa_lists_args (R rows per scenario with dyn_count; H and dyn_mode are not read)
+template <typename T, bool LISTS = false, typename A = nmpc_dwa_args>
+int dwa_step(nmpc_handle_s* h, const A* g)
 {
+    const char* const fn = LISTS ? "nmpc_dwa_step_lists" : "nmpc_dwa_step";
     if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
-    if (g->n_run < 0 || g->B < g->n_run || g->M < 0 || g->Pmax < 2 || g->cap < 1 || g->dyn_mode < 0 || g->dyn_mode > 2 ||
-        (g->dyn_mode > 0 && g->H < 1) || g->H < 0)
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: bad dimensions (B %d, n_run %d, H %d, M %d, Pmax %d, cap %d, dyn_mode %d)",
+    if constexpr (LISTS) {
+        if (g->n_run < 0 || g->B < g->n_run || g->M < 0 || g->Pmax < 2 || g->cap < 1 || g->R < 1)
+            return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: bad dimensions (B %d, n_run %d, R %d, M %d, Pmax %d, cap %d)", fn, g->B, g->n_run,
+                        g->R, g->M, g->Pmax, g->cap);
+    } else if (g->n_run < 0 || g->B < g->n_run || g->M < 0 || g->Pmax < 2 || g->cap < 1 || g->dyn_mode < 0 || g->dyn_mode > 2 ||
+               (g->dyn_mode > 0 && g->H < 1) || g->H < 0)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: bad dimensions (B %d, n_run %d, H %d, M %d, Pmax %d, cap %d, dyn_mode %d)", fn,
                     g->B, g->n_run, g->H, g->M, g->Pmax, g->cap, g->dyn_mode);
-    if (!g->run && g->n_run != g->B) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: run = NULL needs n_run = B");
+    if (!g->run && g->n_run != g->B) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: run = NULL needs n_run = B", fn);
     if (!(g->vel_resolution > 0.0) || !(g->ang_resolution > 0.0) || !(g->lin_vel_max >= g->lin_vel_min) || !(g->ang_vel_max >= 0.0) ||
         !(g->lin_acc_max >= 0.0) || !(g->ang_acc_max >= 0.0))
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: resolutions must be positive, limits ordered, accelerations non-negative");
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: resolutions must be positive, limits ordered, accelerations non-negative", fn);
     if (!g->state_c || !g->last_u_c || !g->goal || !g->path || !g->path_len || !g->U_c || !g->min_cost || !g->choice || !g->counts ||
-        (g->dyn_mode > 0 && !g->dyn_c) || (g->M > 0 && !g->polys))
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: a required array is NULL");
+        ((LISTS || g->dyn_mode > 0) && !g->dyn_c) || (g->M > 0 && !g->polys))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: a required array is NULL", fn);
+    if constexpr (LISTS)
+        if (!g->dyn_count) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: a required array is NULL (dyn_count)", fn);
     const auto aligned = [](const void* q, size_t al) { return q == nullptr || reinterpret_cast<uintptr_t>(q) % al == 0; };
     for (const void* q : {g->state_c, g->last_u_c, g->dyn_c, g->goal, g->path, g->polys, (const void*)g->U_c, (const void*)g->min_cost,
                           (const void*)g->cost_all, (const void*)g->cand_all})
-        if (!aligned(q, sizeof(T))) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: a real array is not aligned to its element type");
+        if (!aligned(q, sizeof(T))) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: a real array is not aligned to its element type", fn);
     if (!aligned(g->run, 8) || !aligned(g->path_len, 8) || !aligned(g->choice, 4) || !aligned(g->counts, 4))
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: an integer array is not aligned to its element type");
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: an integer array is not aligned to its element type", fn);
+    if constexpr (LISTS)
+        if (!aligned(g->dyn_count, 4)) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: an integer array is not aligned to its element type", fn);
     const long long need = dwa_axis_bound(g->lin_vel_max - g->lin_vel_min, g->lin_acc_max, h->cfg.ts, g->vel_resolution) *
                            dwa_axis_bound(2.0 * g->ang_vel_max, g->ang_acc_max, h->cfg.ts, g->ang_resolution);
     if (need > g->cap)
-        return fail(NMPC_ERR_UNSUPPORTED, "nmpc_dwa_step: cap = %d candidates, these limits and resolutions can give %lld", g->cap, need);
-    const size_t lds = (size_t)g->M * 4 * nmpc::kDwaEdgeReals * sizeof(T);
-    if (g->M > 256) return fail(NMPC_ERR_UNSUPPORTED, "nmpc_dwa_step: M = %d rectangles > 256", g->M);
+        return fail(NMPC_ERR_UNSUPPORTED, "%s: cap = %d candidates, these limits and resolutions can give %lld", fn, g->cap, need);
+    size_t lds = (size_t)g->M * 4 * nmpc::kDwaEdgeReals * sizeof(T);
+    if (g->M > 256) return fail(NMPC_ERR_UNSUPPORTED, "%s: M = %d rectangles > 256", fn, g->M);
+    if constexpr (LISTS) {
+        const long long means = (long long)g->R * (h->cfg.N_hor + 1);
+        if (means > nmpc::kDwaListsMaxMeans)
+            return fail(NMPC_ERR_UNSUPPORTED, "%s: R (N_hor + 1) = %lld means per scenario > %d", fn, means, nmpc::kDwaListsMaxMeans);
+        lds = nmpc::dwa_lists_lds<T>(g->M, g->R, h->cfg.N_hor);
+        if (lds > nmpc::kDwaListsMaxLds)
+            return fail(NMPC_ERR_UNSUPPORTED, "%s: %zu B of LDS for M = %d rectangles and R = %d rows > %zu", fn, lds, g->M, g->R,
+                        nmpc::kDwaListsMaxLds);
+    }
     if (g->n_run == 0) return 0;
     HIP_TRY(hipSetDevice(h->cfg.device_id));
     // (a host pointer here would fault inside the kernel: three samples of the argument block are looked up)
     if (h->ptr_mode != NMPC_PTR_DEVICE && (!is_device_ptr(g->state_c) || !is_device_ptr(g->U_c) || !is_device_ptr(g->path)))
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_dwa_step: every array must be a device pointer");
-    nmpc::DwaParams<T> p;
-    std::memset(&p, 0, sizeof p);
-    p.B = g->B, p.n_run = g->n_run, p.N = h->cfg.N_hor, p.H = g->dyn_mode > 0 ? g->H : 0, p.M = g->M, p.Pmax = g->Pmax;
-    p.cap = g->cap, p.dyn_mode = g->dyn_mode;
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: every array must be a device pointer", fn);
+    std::conditional_t<LISTS, nmpc::DwaListsParams<T>, nmpc::DwaParams<T>> p;
+    std::memset(static_cast<void*>(&p), 0, sizeof p);
+    p.B = g->B, p.n_run = g->n_run, p.N = h->cfg.N_hor, p.M = g->M, p.Pmax = g->Pmax, p.cap = g->cap;
+    if constexpr (LISTS) {
+        if (h->ptr_mode != NMPC_PTR_DEVICE && (!is_device_ptr(g->dyn_c) || !is_device_ptr(g->dyn_count)))
+            return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: every array must be a device pointer", fn);
+        p.H = 0, p.dyn_mode = 2, p.R = g->R, p.dyn_count = g->dyn_count;
+    } else {
+        p.H = g->dyn_mode > 0 ? g->H : 0, p.dyn_mode = g->dyn_mode;
+    }
     p.run = reinterpret_cast<const long long*>(g->run);
     p.state_c = static_cast<const T*>(g->state_c), p.last_u_c = static_cast<const T*>(g->last_u_c);
     p.dyn_c = static_cast<const T*>(g->dyn_c), p.goal = static_cast<const T*>(g->goal), p.path = static_cast<const T*>(g->path);
@@ -1942,7 +1969,14 @@ int dwa_step(nmpc_handle_s* h, const nmpc_dwa_args* g)
     p.U_c = static_cast<T*>(g->U_c), p.min_cost = static_cast<T*>(g->min_cost), p.choice = g->choice, p.counts = g->counts;
     p.cost_all = static_cast<T*>(g->cost_all), p.cand_all = static_cast<T*>(g->cand_all);
     const int wpg = nmpc::kDwaThreads / 64;
-    hipLaunchKernelGGL(nmpc::dwa_step_kernel<T>, dim3((g->n_run + wpg - 1) / wpg), dim3(nmpc::kDwaThreads), lds, h->stream, p);
+    if constexpr (LISTS) {
+        if (lds > kLdsOptIn)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(nmpc::dwa_step_lists_kernel<T>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(nmpc::dwa_step_lists_kernel<T>, dim3((g->n_run + wpg - 1) / wpg), dim3(nmpc::kDwaThreads), lds, h->stream, p);
+    } else {
+        hipLaunchKernelGGL(nmpc::dwa_step_kernel<T>, dim3((g->n_run + wpg - 1) / wpg), dim3(nmpc::kDwaThreads), lds, h->stream, p);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2313,6 +2347,20 @@ int nmpc_hypotheses_to_ellipses_f64(nmpc_handle h, const double* hypos, int32_t 
     return hypotheses_to_ellipses<double>(h, hypos, P, cur, H, human_size, eps, enlarge, extra_margin, B, dyn, n_obs);
 }
 
+int nmpc_hypotheses_to_ellipses_counts_f32(nmpc_handle h, const float* hypos, int32_t P, const float* cur, int32_t H,
+                                           double human_size, double eps, double enlarge, double extra_margin, int32_t B,
+                                           float* dyn, int32_t* n_obs, int32_t* counts)
+{
+    return hypotheses_to_ellipses<float>(h, hypos, P, cur, H, human_size, eps, enlarge, extra_margin, B, dyn, n_obs, counts);
+}
+
+int nmpc_hypotheses_to_ellipses_counts_f64(nmpc_handle h, const double* hypos, int32_t P, const double* cur, int32_t H,
+                                           double human_size, double eps, double enlarge, double extra_margin, int32_t B,
+                                           double* dyn, int32_t* n_obs, int32_t* counts)
+{
+    return hypotheses_to_ellipses<double>(h, hypos, P, cur, H, human_size, eps, enlarge, extra_margin, B, dyn, n_obs, counts);
+}
+
 int nmpc_set_map(nmpc_handle h, const uint8_t* occupied, const uint8_t* edge, int32_t height, int32_t width)
 {
     return set_map(h, occupied, edge, height, width);
@@ -2337,6 +2385,8 @@ int nmpc_kf_predict_f32(nmpc_handle h, const nmpc_kf_args* a) { return kf_predic
 int nmpc_kf_predict_f64(nmpc_handle h, const nmpc_kf_args* a) { return kf_predict<double>(h, a); }
 int nmpc_dwa_step_f32(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<float>(h, a); }
 int nmpc_dwa_step_f64(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<double>(h, a); }
+int nmpc_dwa_step_lists_f32(nmpc_handle h, const nmpc_dwa_lists_args* a) { return dwa_step<float, true, nmpc_dwa_lists_args>(h, a); }
+int nmpc_dwa_step_lists_f64(nmpc_handle h, const nmpc_dwa_lists_args* a) { return dwa_step<double, true, nmpc_dwa_lists_args>(h, a); }
 int nmpc_mmp_input_f32(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input<float>(h, a); }
 int nmpc_mmp_input_f64(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input<double>(h, a); }
 int nmpc_mmp_stem_f32(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<float>(h, a); }

@@ -32,6 +32,7 @@ struct HypParams {
     const T* cur;   // [B][H][2]
     T* dyn;         // [B][Ndyn][N+1][6]
     int* n_obs;     // [B] (may be null)
+    int* counts;    // [B][N+1] (may be null): rows per offset = min(clusters, Ndyn); offset 0: min(H, Ndyn)
 };
 
 __device__ __forceinline__ float hsqrt(float x) { return sqrtf(x); }
@@ -67,6 +68,9 @@ __device__ __forceinline__ void hyp_finish(const HypParams<T>& a, const int b, c
     const int n_obs = max_cl;
     const int used = n_obs < a.Ndyn ? n_obs : a.Ndyn;
     if (lane == 0 && a.n_obs) a.n_obs[b] = n_obs;
+    if (a.counts)
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int t = lane; t < NP1; t += 64) a.counts[(size_t)b * NP1 + t] = counts[t] < a.Ndyn ? counts[t] : a.Ndyn;
     // offset 0: current positions; empty slots of used obstacles: [0,0,0,0,0,1]; unused obstacles: zeros
     for (int i = lane; i < a.Ndyn * NP1; i += 64) {
         const int c = i / NP1, t = i - c * NP1;

@@ -10,7 +10,9 @@ reference the previous chosen control belongs to the object and opens the next s
 their costs) are not produced. ``dyn_obstacle_list``: ``None``, a list of positions (ndim 2: the pedestrians' current
 positions) or a list of such lists per time offset 0 .. N_hor (ndim 3: offset 0 = the current positions). With a 3-D list
 the per-step term uses Euclidean distances (the reference's own function raises for three or more pedestrians; see
-include/nmpc_hip.h, ``nmpc_dwa_args``).
+include/nmpc_hip.h, ``nmpc_dwa_args``). A list of lists of UNEQUAL length -- the cluster means of the multi-hypothesis predictor,
+as ``MainBase.run_wta_prediction`` returns them -- goes through ``nmpc_dwa_step_lists_f64`` (``nmpc_dwa_lists_args``: the reference
+itself raises on such a list); a rectangular one stays on dyn_mode 2.
 
 For whole batches of scenarios use ``evaluate.BatchEvaluator(tracker="dwa")``.
 """
@@ -84,8 +86,18 @@ class DwaInterface:
             self._h = _capi.Handle(cfg)
         dev = lambda x, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(x), dtype=dt, device="cuda")
         dyn_mode, H = 0, 0
-        rows = None
-        if dyn_obstacle_list is not None:
+        rows = count = None
+        ragged = _offset_lists(dyn_obstacle_list)
+        if ragged is not None:          # unequal numbers of entries per offset: the lists entry (R = the longest list)
+            if len(ragged) < N + 1:
+                raise ValueError(f"dyn_obstacle_list has {len(ragged)} time offsets, N_hor + 1 = {N + 1} are needed")
+            ragged = ragged[:N + 1]
+            dyn_mode, H = 2, max(len(q) for q in ragged)
+            rows, count = np.zeros((1, H, N + 1, 6)), np.zeros((1, N + 1), dtype=np.int32)
+            for t, q in enumerate(ragged):
+                count[0, t] = len(q)
+                rows[0, :len(q), t, :2] = q[:, :2]
+        elif dyn_obstacle_list is not None:
             d = np.array(dyn_obstacle_list, dtype=np.float64)
             if d.ndim == 2:
                 dyn_mode, H = 1, d.shape[0]
@@ -102,7 +114,7 @@ class DwaInterface:
         polys = self._polygons()
         path = np.array([p[:2] for p in self.ref_path], dtype=np.float64)
         last_u = self.past_actions[-1] if self.past_actions else np.zeros(2)
-        a = _capi.NmpcDwaArgs().set_config(c, SPEED_SCALE[mode])
+        a = (_capi.NmpcDwaArgs() if count is None else _capi.NmpcDwaListsArgs()).set_config(c, SPEED_SCALE[mode])
         cap = 1
         for rng, acc, res in ((c.lin_vel_max - c.lin_vel_min, c.lin_acc_max, c.vel_resolution), (2.0 * c.ang_vel_max, c.ang_acc_max, c.ang_resolution)):
             w = min(rng, 2.0 * acc * float(c.ts))
@@ -116,11 +128,14 @@ class DwaInterface:
             t["dyn_c"] = dev(rows)
         if polys.shape[0]:
             t["polys"] = dev(polys)
+        if count is not None:
+            t["dyn_count"] = dev(count, torch.int32)
+            a.R = H
         a.B, a.n_run, a.H, a.M, a.Pmax, a.cap, a.dyn_mode = 1, 1, H, int(polys.shape[0]), int(path.shape[0]), cap, dyn_mode
         for k, v in t.items():
             setattr(a, k, v.data_ptr())
         self._h.set_stream(torch.cuda.current_stream().cuda_stream)
-        self._h.dwa_step(np.float64, a)
+        (self._h.dwa_step if count is None else self._h.dwa_step_lists)(np.float64, a)
         action = t["U_c"][0, :2].cpu().numpy()
         cost = float(t["min_cost"].cpu()[0])
         choice = int(t["choice"].cpu()[0])
@@ -136,6 +151,26 @@ class DwaInterface:
         if self._h is not None:
             self._h.close()
             self._h = None
+
+
+def _offset_lists(obstacles):
+    """The per-offset arrays [n_t, >= 2] of a list of lists of positions whose lengths differ (what ``run_wta_prediction`` returns:
+    offset 0 = the current positions, then the cluster means of every offset), or ``None`` for anything else -- ``None``, a list of
+    positions, a rectangular list of lists: those keep their path."""
+    if obstacles is None or len(obstacles) == 0:
+        return None
+    out = []
+    for q in obstacles:
+        try:
+            q = np.asarray(q, dtype=np.float64)
+        except (TypeError, ValueError):
+            return None
+        if q.size == 0:
+            q = np.zeros((0, 2))
+        if q.ndim != 2 or q.shape[1] < 2:
+            return None
+        out.append(q)
+    return out if len({len(q) for q in out}) > 1 else None
 
 
 def _rollout(state, u, N, ts):

@@ -2,7 +2,9 @@
 
 Trackers: ``"mpc"`` (below) and ``"dwa"``, the reference's dynamic-window baseline (pkg_dwa_tracker/trajectory_tracker.py:304-355
 as main_base.py:303-321 drives it): ``nmpc_dwa_step_*`` (csrc/nmpc_dwa.h) takes the place of f1 + solve between the same
-``loop_pre`` / ``loop_post`` kernels, with the predictors ``None``, ``cvmp`` and ``kfmp``.
+``loop_pre`` / ``loop_post`` kernels, with the predictors ``None``, ``cvmp`` and ``kfmp``; with ``mmp`` the per-offset lists variant
+``nmpc_dwa_step_lists_*`` on f2's rows and counts (the reference hands the tracker ``mu_list_list`` whatever the predictor,
+main_base.py:303-304).
 
 Semantics of the reference's evaluation loop for the MPC tracker with the constant-velocity predictor (``cvmp``) or the
 Kalman-filter predictor (``kfmp``), the two predictor configurations of ``main_eva.py`` that need no network weights
@@ -36,7 +38,7 @@ scenarios still running:
    ``loop_pre``'s as the input of f1 (``MainBase.run_wta_prediction``, main_base.py:175-208, ``MmpInterface``,
    interfaces/mmp_interface.py:20-70; its independent check is tests/mmp_reference.py);
 3. tracker stage: ``_mpc_step`` = f1, the ``on_params`` hook, ``_solve_step`` (warm start, handle by batch size, dispatch
-   order, status counts, ``_solve``); or ``_dwa_step`` = ``nmpc_dwa_step_*``;
+   order, status counts, ``_solve``); or ``_dwa_step`` = ``nmpc_dwa_step_*`` (behind ``_mmp_predict``: ``nmpc_dwa_step_lists_*``);
 4. ``nmpc_loop_post_*``: first action, agent motion, metrics, flags.
 
 A run starts in ``_start_run`` (flags and metrics, one namespace with the ``_loop_args`` / ``_kf_args`` / ``_mmp_args`` / ``_dwa_args`` buffers)
@@ -134,7 +136,10 @@ class BatchEvaluator:
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
         configuration's). It runs with ``predictor`` ``None`` (the pedestrians' current positions, as the reference without a
-        predictor), ``"cvmp"`` or ``"kfmp"`` (their mean positions per offset), on the fused path with ``n_hyp == 1``, and
+        predictor), ``"cvmp"`` or ``"kfmp"`` (their mean positions per offset) or ``"mmp"`` (the cluster means of f2, whose number
+        differs from offset to offset: ``nmpc_dwa_step_lists_*`` with ``R = Ndynobs`` rows and f2's per-offset counts; every ``mmp_*``
+        option below applies; ``record=`` entries carry ``dyn``, ``dyn_count``, ``n_obs``, ``n_outside`` and the tracker's outputs), on
+        the fused path with ``n_hyp == 1``, and
         creates no parameter vectors, multipliers or solver handles. Metrics, goal and collision rules are the shared ones.
 
         ``predictor``: ``"cvmp"`` = the constant-velocity predictor; ``"kfmp"`` = the Kalman-filter predictor
@@ -151,7 +156,7 @@ class BatchEvaluator:
         hypotheses are snapped on (``255 - ref_image`` is the occupancy, ``Handle.set_map`` once, here). ``transform``: the
         :class:`.snap.WorldTransform` between map pixels and the world, ``rescale``: ``scale2nn``. ``mmp_chunk``: pedestrians
         per network call (default: as many as keep the input tensor at or below 1 GiB -- 19 for the warehouse map at
-        N_hor = 20). It needs ``tracker="mpc"``, ``fused=True``, ``n_hyp == 1`` and ``H * mmp_hyp <= 256``. ``mmp_stem``: a
+        N_hor = 20). It needs ``fused=True``, ``n_hyp == 1`` and ``H * mmp_hyp <= 256``. ``mmp_stem``: a
         :class:`.mmp_stem.StemSpec` (``mmp_stem.split_network`` / ``fold_stem``) = the network's first layer, computed by the
         device stage itself (``nmpc_mmp_stem_*``, csrc/nmpc_mmp_stem.h) without the input stack ever being written; ``network``
         is then the trunk behind it, called on ``[M, C, Hp, Wp]``, and the chunk is sized from that tensor (34 pedestrians for
@@ -201,8 +206,8 @@ class BatchEvaluator:
             raise ValueError(f"tracker = {tracker!r} (mpc or dwa)")
         if tracker == "mpc" and predictor is None:
             raise ValueError("tracker = 'mpc' needs a predictor (cvmp, kfmp or mmp)")
-        if predictor not in ("cvmp", "kfmp") and not (tracker == "dwa" and predictor is None) and not (tracker == "mpc" and predictor == "mmp"):
-            raise ValueError(f"predictor = {predictor!r} (cvmp or kfmp; mmp with tracker = 'mpc'; None with tracker = 'dwa')")
+        if predictor not in ("cvmp", "kfmp", "mmp") and not (tracker == "dwa" and predictor is None):
+            raise ValueError(f"predictor = {predictor!r} (cvmp, kfmp or mmp; None with tracker = 'dwa')")
         if mmp_stem is not None and predictor != "mmp":
             raise ValueError("mmp_stem needs predictor = 'mmp'")
         mmp_specs = MmpFrontEnd.check_specs(mmp_stem, mmp_blocks, prefix="mmp_", blocks2=mmp_blocks2, blocks3=mmp_blocks3, blocks4=mmp_blocks4,
@@ -224,6 +229,8 @@ class BatchEvaluator:
                 raise ValueError(f"mmp_hyp = {mmp_hyp}, mmp_chunk = {mmp_chunk}, rescale = {rescale}")
         if tracker == "dwa" and (self.n_hyp != 1 or not fused):
             raise ValueError("tracker = 'dwa' needs n_hyp = 1 and fused = True")
+        if config is None:
+            raise ValueError("config is None: an NmpcConfigStruct is needed (default_config_struct())")
         self.tracker, self.predictor = tracker, predictor
         self.dwa_config = None
         if tracker == "dwa":
@@ -602,6 +609,7 @@ class BatchEvaluator:
         r.mmp_raw_p, r.mmp_hyp = z(B * H, N, K, 2), z(B, N, H * K, 2)
         r.mmp_dyn = z(B, self.cfg.Ndynobs, N + 1, 6)
         r.mmp_n_obs, r.mmp_n_out = z(B, dtype=torch.int32, fill=0), z(B, dtype=torch.int32, fill=0)
+        r.mmp_counts = z(B, N + 1, dtype=torch.int32, fill=0)      # rows of mmp_dyn per offset that are clusters (the lists DWA step reads them)
         r.mmp_obs_steps = z(max(max_steps, 1), B, dtype=torch.int32, fill=-1)
         r.mmp_out_steps = z(max(max_steps, 1), B, dtype=torch.int32, fill=-1)
         r.mmp_all = torch.arange(B * H, dtype=torch.long, device=self.dev)
@@ -613,7 +621,7 @@ class BatchEvaluator:
         """The multi-hypothesis predictor for the ``nA`` running scenarios (``idx``, None = all), MainBase.run_wta_prediction
         (main_base.py:175-208): per chunk of pedestrians the device front end (``MmpFrontEnd.run``: input stack, or the fused first
         layer's output, then the fused blocks of layer1 to layer4) -> network (with ``mmp_head`` the front end's last launch instead); then, per scenario with its pedestrians' segments concatenated
-        in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]``."""
+        in order (:192-195), snap -> f2 with ``cur`` = the current positions. Writes ``r.mmp_dyn[:nA]`` and ``r.mmp_counts[:nA]``."""
         torch, N, H, K = self.torch, self.N, self.H, self.mmp_hyp
 
         def part(name, call):
@@ -644,7 +652,7 @@ class BatchEvaluator:
         part("snap", lambda: self.h.snap_hypotheses(self.dt, raw, hyp, H, K, self.mmp_tf, self.mmp_rescale, n_outside=r.mmp_n_out[:nA]))
         cur = self.humans if idx is None else self.humans.index_select(0, idx)
         part("f2", lambda: self.h.hypotheses_to_ellipses(self.dt, hyp, cur, r.mmp_dyn[:nA], r.mmp_n_obs[:nA], human_size=HUMAN_SIZE,
-                                                         eps=1.0, enlarge=2.0, extra_margin=0.0))
+                                                         eps=1.0, enlarge=2.0, extra_margin=0.0, counts=r.mmp_counts[:nA]))
         for steps, now in ((r.mmp_obs_steps, r.mmp_n_obs), (r.mmp_out_steps, r.mmp_n_out)):
             if idx is None:
                 steps[kt].copy_(now)
@@ -652,13 +660,17 @@ class BatchEvaluator:
                 steps[kt].index_copy_(0, idx, now[:nA])
 
     def _dwa_args(self, r):
-        """``NmpcDwaArgs`` of a run: the compact buffers ``loop_pre`` fills in, the node paths, the outputs per scenario."""
+        """``NmpcDwaArgs`` of a run: the compact buffers ``loop_pre`` fills in, the node paths, the outputs per scenario. With the
+        predictor ``mmp`` (after ``_mmp_args``): ``NmpcDwaListsArgs`` on the stage's ``mmp_dyn`` / ``mmp_counts``."""
         B, z, i32 = self.B, self._full, self.torch.int32
         r.dwa_cost, r.dwa_choice, r.dwa_counts = z(B), z(B, dtype=i32, fill=0), z(B, 2, dtype=i32, fill=0)
-        dw = _capi.NmpcDwaArgs().set_config(self.dwa_config, self.speed_scale)
+        lists = self.predictor == "mmp"        # f2's rows with their per-offset counts: nmpc_dwa_step_lists_*, R = Ndynobs
+        dw = (_capi.NmpcDwaListsArgs() if lists else _capi.NmpcDwaArgs()).set_config(self.dwa_config, self.speed_scale)
         dw.B, dw.H, dw.M, dw.Pmax, dw.cap = B, self.H, int(self.polys.shape[0]), int(self.node_path.shape[1]), self.dwa_cap
         dw.dyn_mode = 1 if self.predictor is None else 2
         dw.state_c, dw.last_u_c, dw.dyn_c = r.state_c.data_ptr(), r.last_u_c.data_ptr(), r.dyn_c.data_ptr()
+        if lists:
+            dw.R, dw.dyn_c, dw.dyn_count = int(self.cfg.Ndynobs), r.mmp_dyn.data_ptr(), r.mmp_counts.data_ptr()
         dw.goal, dw.path, dw.path_len = self.goal.data_ptr(), self.node_path.data_ptr(), self.node_len.data_ptr()
         dw.polys = self.polys.data_ptr() if self.polys.numel() else None
         dw.min_cost, dw.choice, dw.counts = r.dwa_cost.data_ptr(), r.dwa_choice.data_ptr(), r.dwa_counts.data_ptr()
@@ -735,7 +747,8 @@ class BatchEvaluator:
         solve, so no handle is returned."""
         dwa_step(self.dt, dw)
         if rec is not None:
-            rec.update(run=None if idx is None else idx.cpu().numpy(), U_c=Ua.cpu().numpy(), min_cost=r.dwa_cost[:nA].cpu().numpy(),
+            rec.update(run=None if idx is None else idx.cpu().numpy(), state_c=r.state_c[:nA].cpu().numpy(), last_u_c=r.last_u_c[:nA].cpu().numpy(),
+                       U_c=Ua.cpu().numpy(), min_cost=r.dwa_cost[:nA].cpu().numpy(),
                        choice=r.dwa_choice[:nA].cpu().numpy(), counts=r.dwa_counts[:nA].cpu().numpy())
 
     # ---- the time step --------------------------------------------------------------------------------------------
@@ -749,7 +762,7 @@ class BatchEvaluator:
         dw = self._dwa_args(r) if self.tracker == "dwa" else None
         kf_predict, kf_events = self._timed(self.h.kf_predict, self.time_predictor)
         mmp_predict, mmp_events = self._timed(self._mmp_predict, self.time_predictor)
-        dwa_step, dwa_events = self._timed(self.h.dwa_step, self.time_tracker)
+        dwa_step, dwa_events = self._timed(self.h.dwa_step_lists if self.tracker == "dwa" and mm is not None else self.h.dwa_step, self.time_tracker)
         solve_ms, n_steps_run = [], 0
         for kt in range(max_steps):
             if not bool(r.alive.any()):
@@ -774,6 +787,7 @@ class BatchEvaluator:
             rec = None if record is None else self._record_entry(r.alive)
             if rec is not None and mm is not None:
                 rec.update(dyn=(r.mmp_dyn if full else torch.zeros_like(r.mmp_dyn).index_copy_(0, idx, r.mmp_dyn[:nA])).cpu().numpy(),
+                           dyn_count=(r.mmp_counts if full else torch.zeros_like(r.mmp_counts).index_copy_(0, idx, r.mmp_counts[:nA])).cpu().numpy(),
                            n_obs=r.mmp_obs_steps[kt].cpu().numpy(), n_outside=r.mmp_out_steps[kt].cpu().numpy())
             if dw is not None:
                 dw.n_run, dw.run, dw.U_c = nA, a.run, Ua.data_ptr()

@@ -2,10 +2,12 @@
 """Measurement of the f3 path (batched closed-loop evaluator): B warehouse scenarios advanced in lock-step; one JSON
 line with scenario-steps/s, the share of the wall time spent inside the solve kernel, and the outcome statistics.
 The comparison figure is the reference's own way of doing this: one scenario after another, one solve per step.
-   usage: bench_evaluate.py [--tracker {mpc,dwa}] [--predictor {cvmp,kfmp,none}] [B] [max_steps] [f32|f64] [n_ped] [n_hyp]
+   usage: bench_evaluate.py [--tracker {mpc,dwa}] [--predictor {cvmp,kfmp,mmp,none}] [B] [max_steps] [f32|f64] [n_ped] [n_hyp]
    --tracker dwa: the reference's dynamic-window baseline (nmpc_dwa_step_*, dwa_test.yaml's values) in place of f1 + solve;
    --predictor none is its run without a predictor. HIP events around every call of the stage give "tracker_stage" (ms per
    lock-step, scenario-steps/s inside the kernel); the solve fields are empty then.
+   --predictor mmp (either tracker; with dwa the per-offset lists step nmpc_dwa_step_lists_*): the multi-hypothesis predictor with
+   the network of tools/mmp_evaluate_profile.py (random weights), 20 hypotheses per pedestrian, n_hyp = 1.
    --predictor kfmp: the Kalman-filter predictor (nmpc_kf_predict_*, n_hyp = 1) instead of the constant-velocity one; HIP
    events around every call of the stage give "predictor_stage" (ms at the first / last lock-step, share of the run).
    n_ped x n_hyp = 2 x 1 (default): the shipped yaml's dimensions with the constant-velocity predictor (Ndynobs = 15);
@@ -35,8 +37,8 @@ if tracker not in ("mpc", "dwa"):
     sys.exit(f"--tracker {tracker}: mpc or dwa")
 if predictor == "none" and tracker == "dwa":
     predictor = None
-if predictor not in ("cvmp", "kfmp", None):
-    sys.exit(f"--predictor {predictor}: cvmp or kfmp (none with --tracker dwa)")
+if predictor not in ("cvmp", "kfmp", "mmp", None):
+    sys.exit(f"--predictor {predictor}: cvmp, kfmp or mmp (none with --tracker dwa)")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 max_steps = int(sys.argv[2]) if len(sys.argv) > 2 else 60
 dtype = {"f32": np.float32, "f64": np.float64}[sys.argv[3] if len(sys.argv) > 3 else "f32"]
@@ -55,10 +57,17 @@ budget = os.environ.get("BUDGET", "0")
 cfg.max_evaluations = (evaluation_budget(100_000, cfg.N_hor, cfg.Nother, cfg.Nstcobs, cfg.Ndynobs) if budget == "yaml"
                        else int(budget))
 cfg.tail_latency = int(os.environ.get("TAIL", "0"))
-warm = make(64, seed=14, n_ped=n_ped)
+mmp = {}
+if predictor == "mmp":      # the network of tools/mmp_evaluate_profile.py (the reference's architecture, random weights) on the warehouse label image
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import mmp_evaluate_profile as mp
+    torch.manual_seed(0)
+    _, _, ref_image, transform, _ = mp._world(1, n_ped)
+    mmp = dict(network=mp.make_network(20).cuda().eval(), mmp_hyp=20, ref_image=ref_image, transform=transform)
+warm = make(64 if predictor != "mmp" else min(B, 8), seed=14, n_ped=n_ped)
 warm.pop("scenario_index", None)
-BatchEvaluator(cfg, dtype=dtype, n_hyp=n_hyp, predictor=predictor, tracker=tracker, **warm).run(max_steps=3)  # warm-up
-ev = BatchEvaluator(cfg, dtype=dtype, human_stagger=stagger, seed=5, n_hyp=n_hyp, predictor=predictor, tracker=tracker, **sc)
+BatchEvaluator(cfg, dtype=dtype, n_hyp=n_hyp, predictor=predictor, tracker=tracker, **mmp, **warm).run(max_steps=3)  # warm-up
+ev = BatchEvaluator(cfg, dtype=dtype, human_stagger=stagger, seed=5, n_hyp=n_hyp, predictor=predictor, tracker=tracker, **mmp, **sc)
 ev.count_status = tracker == "mpc"
 ev.time_tracker = tracker == "dwa"
 ev.time_predictor = predictor == "kfmp"
@@ -96,7 +105,7 @@ tracker_stage = None
 if ev.tracker_ms:
     tms = [float(x) for x in ev.tracker_ms]
     running = [int((res.steps > kt).sum()) for kt in range(len(tms))]
-    tracker_stage = {"kernel": "nmpc_dwa_step (HIP events around the call)", "ms_first_step": tms[0], "ms_last_step": tms[-1], "ms_max": max(tms),
+    tracker_stage = {"kernel": ("nmpc_dwa_step_lists" if predictor == "mmp" else "nmpc_dwa_step") + " (HIP events around the call)", "ms_first_step": tms[0], "ms_last_step": tms[-1], "ms_max": max(tms),
                      "ms_total": sum(tms), "share_of_wall_time": sum(tms) * 1e-3 / el, "candidates_per_scenario_max": int(ev.dwa_cap),
                      "scenario_steps_per_s_in_the_kernel": sum(running) / (sum(tms) * 1e-3),
                      "per_step": [{"step": kt, "running": n, "dwa_ms": round(m, 3)} for kt, (n, m) in enumerate(zip(running, tms))]}
@@ -110,7 +119,7 @@ print(json.dumps({
     "n_gpus": 1, "dtype": "f32" if dtype == np.float32 else "f64", "wall_s": el, "tracker": tracker, "predictor": predictor, "predictor_stage": stage, "tracker_stage": tracker_stage,
     "family": family, "max_evaluations": int(cfg.max_evaluations), "tail_latency": int(cfg.tail_latency), "human_stagger": stagger,
     "config": {"workload": f"B={B} scenarios x <= {max_steps} steps, " + ("mpc_fast.yaml, " if tracker == "mpc" else "dynamic-window tracker (dwa_test.yaml's values), ") + ("scenario_0..2 on the 55-polygon warehouse map" if family == "reference" else "14 map boxes") + f", {n_ped} pedestrians x {n_hyp} "
-                           f"hypotheses (Ndynobs = {cfg.Ndynobs}; " + ("Kalman-filter rows" if predictor == "kfmp" else "current positions only" if predictor is None else "constant-velocity rows" if n_hyp == 1 else "fan around the constant-velocity prediction") + ")"},
+                           f"hypotheses (Ndynobs = {cfg.Ndynobs}; " + ("Kalman-filter rows" if predictor == "kfmp" else "cluster means of the multi-hypothesis predictor" if predictor == "mmp" else "current positions only" if predictor is None else "constant-velocity rows" if n_hyp == 1 else "fan around the constant-velocity prediction") + ")"},
     "lockstep_steps": len(res.solve_ms) if tracker == "mpc" else len(ev.tracker_ms), "scenario_steps": scen_steps,
     "solve_kernel_ms_total": float(np.sum(res.solve_ms)), "solve_kernel_share": float(np.sum(res.solve_ms)) * 1e-3 / el,
     "solve_kernel_ms_per_step": [round(float(x), 2) for x in res.solve_ms[:6]] + ["..."] + [round(float(x), 2) for x in res.solve_ms[-3:]],
