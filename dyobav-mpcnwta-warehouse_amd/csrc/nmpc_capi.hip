@@ -31,6 +31,7 @@
 #include "nmpc_mmp_block.h"
 #include "nmpc_mmp_block2.h"
 #include "nmpc_mmp_block3.h"
+#include "nmpc_mmp_block3_f16.h"
 #include "nmpc_mmp_block4.h"
 #include "nmpc_mmp_head.h"
 
@@ -1751,7 +1752,8 @@ int mmp_block(nmpc_handle_s* h, const nmpc_mmp_block_args* g)
 
 // The three strided stages (layer2 .. layer4) behind one entry, mmp_strided<Stage>. A Stage says what differs: the name in the
 // messages, the structs, the output channels C, the threads of a workgroup, how the plane of outputs H2 x W2 is cut into ty x tx
-// tiles, and the kernels <stride 2, projection>, <stride 1, projection>, <stride 1, identity>. Two numbers of the entry follow from
+// tiles, the alignment of packed weights (0: plain float arrays), and the kernels <stride 2, projection>, <stride 1, projection>,
+// <stride 1, identity>. Two numbers of the entry follow from
 // a stage's tile: the kernels' pixel coordinates are ints and reach 2 (tile origin + reach) + 1, which must not wrap -- hence no
 // plane over 2^30 --, and once the workgroup count has passed H2 W2 M <= (outputs of a tile) x 2^31, with H W <= 4 H2 W2: the byte
 // counts of the overlap test do not overflow.
@@ -1759,7 +1761,7 @@ struct MmpLayer2 {
     using Args = nmpc_mmp_block2_args;
     using Params = nmpc::MmpBlock2Params;
     static constexpr const char* name = "nmpc_mmp_block2";
-    static constexpr int C = nmpc::kB2C, threads = nmpc::kB2Threads;
+    static constexpr int C = nmpc::kB2C, threads = nmpc::kB2Threads, packed_align = 0;
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk2_kernel<2, true>, nmpc::mmp_blk2_kernel<1, true>, nmpc::mmp_blk2_kernel<1, false>};
     // tiles of 8 x 44 = 352 outputs; reach 11
     static void tile(Params& p, long long& ty, long long& tx)
@@ -1772,20 +1774,31 @@ struct MmpLayer3 {
     using Args = nmpc_mmp_block3_args;
     using Params = nmpc::MmpBlock3Params;
     static constexpr const char* name = "nmpc_mmp_block3";
-    static constexpr int C = nmpc::kB3C, threads = nmpc::kB3Threads;
+    static constexpr int C = nmpc::kB3C, threads = nmpc::kB3Threads, packed_align = 0;
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk3_kernel<2, true>, nmpc::mmp_blk3_kernel<1, true>, nmpc::mmp_blk3_kernel<1, false>};
     // tiles of 7 x 21 = 147 outputs; reach 10
-    static void tile(Params& p, long long& ty, long long& tx)
+    template <typename P>
+    static void tile(P& p, long long& ty, long long& tx)
     {
         ty = ((long long)p.H2 + nmpc::kB3TH - 1) / nmpc::kB3TH, tx = ((long long)p.W2 + nmpc::kB3TW - 1) / nmpc::kB3TW;
     }
+};
+
+// layer3 with binary16 MFMA operands (csrc/nmpc_mmp_block3_f16.h): layer3's channels, threads and tiles; w1, w2 and wd are the
+// packed fragments, 16 bytes per lane, which is what packed_align adds to the checks
+struct MmpLayer3F16 : MmpLayer3 {
+    using Args = nmpc_mmp_block3_f16_args;
+    using Params = nmpc::MmpBlock3HParams;
+    static constexpr const char* name = "nmpc_mmp_block3_f16";
+    static constexpr int packed_align = 16;
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk3h_kernel<2, true>, nmpc::mmp_blk3h_kernel<1, true>, nmpc::mmp_blk3h_kernel<1, false>};
 };
 
 struct MmpLayer4 {
     using Args = nmpc_mmp_block4_args;
     using Params = nmpc::MmpBlock4Params;
     static constexpr const char* name = "nmpc_mmp_block4";
-    static constexpr int C = nmpc::kB4C, threads = nmpc::kB4Threads;
+    static constexpr int C = nmpc::kB4C, threads = nmpc::kB4Threads, packed_align = 0;
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk4_kernel<2, true>, nmpc::mmp_blk4_kernel<1, true>, nmpc::mmp_blk4_kernel<1, false>};
     // tiles of at most 10 x 11 = 110 outputs; reach 11. A side that fits the tile's plane of m is one tile without a halo; a longer
     // one is cut with a halo of one
@@ -1815,6 +1828,12 @@ int mmp_strided(nmpc_handle_s* h, const typename Stage::Args* g)
         return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: a required array is NULL", fn);
     if (reinterpret_cast<uintptr_t>(g->out) % 4 || reinterpret_cast<uintptr_t>(g->x) % 4)
         return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: x or out is not aligned to float", fn);
+    if constexpr (Stage::packed_align != 0) { // (the stages with packed weights: each lane loads a whole fragment)
+        const void* packed[] = {g->w1, g->w2, g->wd};
+        for (const void* q : packed)
+            if (reinterpret_cast<uintptr_t>(q) % Stage::packed_align)
+                return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: w1, w2 or wd is not aligned to %d bytes", fn, Stage::packed_align);
+    }
     if (g->M == 0) return 0;
     if (g->H > (1 << 30) || g->W > (1 << 30)) return fail(NMPC_ERR_UNSUPPORTED, "%s: plane %d x %d over 2^30", fn, g->H, g->W);
     typename Stage::Params p;
@@ -2394,6 +2413,7 @@ int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_s
 int nmpc_mmp_block_f32(nmpc_handle h, const nmpc_mmp_block_args* a) { return mmp_block(h, a); }
 int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return mmp_strided<MmpLayer2>(h, a); }
 int nmpc_mmp_block3_f32(nmpc_handle h, const nmpc_mmp_block3_args* a) { return mmp_strided<MmpLayer3>(h, a); }
+int nmpc_mmp_block3_f16(nmpc_handle h, const nmpc_mmp_block3_f16_args* a) { return mmp_strided<MmpLayer3F16>(h, a); }
 int nmpc_mmp_block4_f32(nmpc_handle h, const nmpc_mmp_block4_args* a) { return mmp_strided<MmpLayer4>(h, a); }
 int nmpc_mmp_head_f32(nmpc_handle h, const nmpc_mmp_head_args* a) { return mmp_head(h, a); }
 int nmpc_mmp_stem_shape(int32_t Hm, int32_t Wm, int32_t* Hp, int32_t* Wp)

@@ -131,7 +131,7 @@ class BatchEvaluator:
                  hyp_radius_growth: float = 0.05, predictor: Optional[str] = "cvmp", kf_Q=None, kf_R=None, kf_P0=None,
                  tracker: str = "mpc", dwa_config=None, network=None, mmp_hyp: int = 20, mmp_chunk: Optional[int] = None,
                  ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None, mmp_blocks=None, mmp_blocks2=None, mmp_blocks3=None,
-                 mmp_blocks4=None, mmp_head=None):
+                 mmp_blocks4=None, mmp_head=None, mmp_half=()):
         """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
@@ -192,6 +192,12 @@ class BatchEvaluator:
         ``mmp_hyp`` must be half the head's outputs. Measured in the same setting (``profiles/mmp_layer4_evaluate.json``, DESIGN.md
         section 7): the stage takes 389 ms per lock-step against 420 ms without; the three launches 58 ms where torch's own layer4
         took 95, the head 4.4 ms where torch's pool and linear layers took 3.0.
+        ``mmp_half``: the stages to run on binary16 MFMA operands with float32 accumulation: ``("layer3",)`` (needs ``mmp_blocks3``;
+        ``nmpc_mmp_block3_f16``, csrc/nmpc_mmp_block3_f16.h) or ``()``, the default, which changes nothing. The rule: whatever an
+        MFMA reads -- the weights, rounded once on the host; ``x`` as it is staged; the first convolution's activated output as it
+        goes to LDS -- is binary16, rounded to nearest even and saturated at +-65504; nothing else is: the activations in memory, the
+        accumulation, the affines, the LeakyReLUs and the identity stay float32. What that costs and gains, measured: DESIGN.md
+        section 7, ``profiles/mmp_layer3_f16_evaluate.json``. Any other stage name is a ``ValueError``: only layer3 has an f16 kernel.
 
         ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the
@@ -213,6 +219,9 @@ class BatchEvaluator:
         mmp_specs = MmpFrontEnd.check_specs(mmp_stem, mmp_blocks, prefix="mmp_", blocks2=mmp_blocks2, blocks3=mmp_blocks3, blocks4=mmp_blocks4,
                                             head=mmp_head)
         mmp_head = mmp_specs[-1]
+        if mmp_half and predictor != "mmp":
+            raise ValueError("mmp_half needs predictor = 'mmp'")
+        mmp_half = MmpFrontEnd.check_half(mmp_half, mmp_specs, prefix="mmp_")
         if predictor == "mmp":
             if self.n_hyp != 1 or not fused:
                 raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
@@ -320,7 +329,7 @@ class BatchEvaluator:
         else:
             self._init_dwa(robot_paths)
         if predictor == "mmp":
-            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_specs)
+            self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_specs, mmp_half)
 
     def _tensor(self, x):
         return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
@@ -381,7 +390,7 @@ class BatchEvaluator:
         self._info, self._evals = self._full(B, 8), self._full(B)
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
 
-    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, specs):
+    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, specs, half=()):
         """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the device front
         end (``mmp_front``: its kernels, weights and buffers) and from it the shape of one row of the network's input -- the stack's
         [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind the last fused stage its [channels, H, W], or with a
@@ -398,7 +407,7 @@ class BatchEvaluator:
         # mmp_interface.py:60 snaps on 255 - ref_image; its grey levels decide the edges (Handle.set_map)
         self.h.set_map(255.0 - img.astype(np.float64))
         fe = self.mmp_front = MmpFrontEnd(self.h, self.dt, self.dev, self.mmp_Hm, self.mmp_Wm, self.N, transform, self.mmp_rescale, MMP_SIGMA,
-                                          self.mmp_ref, *specs)
+                                          self.mmp_ref, *specs, half=half)
         self.mmp_row = fe.row
         for name in SPEC_NAMES:
             setattr(self, "mmp_" + name, getattr(fe, name))

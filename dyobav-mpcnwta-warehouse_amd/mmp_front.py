@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
-from .mmp_stem import STAGES, block2_plane, check_head, check_spec, check_stage, head_features
+from .mmp_stem import STAGES, block2_plane, check_head, check_spec, check_stage, head_features, pack_block3_f16
 
 _BLOCK_ARRAYS = ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
 _HEAD_ARRAYS = ("w1", "c1", "w2", "c2")
@@ -21,6 +21,8 @@ SPEC_NAMES = ("stem",) + tuple(st.arg for st in STAGES) + ("head",)     # the sp
 # beside each row of STAGES: the struct of its kernel and the Handle method that launches it
 _DEVICE = ((_capi.NmpcMmpBlockArgs, "mmp_block"), (_capi.NmpcMmpBlock2Args, "mmp_block2"), (_capi.NmpcMmpBlock3Args, "mmp_block3"),
            (_capi.NmpcMmpBlock4Args, "mmp_block4"))
+# ``half=``: the stages that have a kernel with binary16 MFMA operands -- how their checked specs are packed, the struct, the method
+_HALF = {"layer3": (pack_block3_f16, _capi.NmpcMmpBlock3F16Args, "mmp_block3_f16")}
 # what each keyword behind ``stem`` needs in front of it, as ``check_specs`` says it
 _NEEDS = (("the blocks run on the fused first layer's output",)
           + tuple(f"the blocks of {st.layer} run on the fused {prev.layer}'s output" for prev, st in zip(STAGES, STAGES[1:]))
@@ -30,9 +32,9 @@ _NEEDS = (("the blocks run on the fused first layer's output",)
 class Stage:
     """One residual stage of a front end (``MmpFrontEnd.stages``)."""
 
-    def __init__(self, name, channels, specs, Args, launch, planes, reads_fill):
+    def __init__(self, name, channels, specs, cins, Args, launch, planes, reads_fill):
         self.name, self.channels = name, channels           # "layer1" ..; the output channels of its blocks
-        self.specs = specs                                  # its specs with their arrays on the device
+        self.specs, self.cins = specs, cins                 # its specs with their arrays on the device (packed ones with ``half``); each block's Cin
         self.Args, self.launch = Args, launch               # the struct of its kernel, the Handle method that launches it
         self.planes = planes                                # the input plane of every block, then the last one's output
         self.buf_row = (channels,) + planes[1]              # a row of its two buffers (planes only shrink: the first output is the largest)
@@ -43,13 +45,17 @@ class Stage:
 
 class MmpFrontEnd:
     def __init__(self, handle: _capi.Handle, dtype, device, Hm: int, Wm: int, n_off: int, transform, rescale: float, sigma: float,
-                 ref_image, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None):
+                 ref_image, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=()):
         """``dtype``: the element type of ``hist``; ``ref_image``: the float32 label image ``[Hm, Wm]`` on ``device``; ``transform``: the
         :class:`.snap.WorldTransform` between map pixels and the world of ``hist``; ``stem``: a :class:`.mmp_stem.StemSpec`; ``blocks``
         .. ``blocks4``: the specs of ``layer1`` .. ``layer4`` (``mmp_stem.STAGES``), each needing the one before it; ``head`` (needs
         ``blocks4``): the ``HeadSpec`` of the network's end, whose ``F`` must be ``128 * (H4 // 2) * (W4 // 2)`` for the plane that
         arrives. ``fill_row``: a row of what the fill writes; ``row``: a row of what the network sees (with a head ``(O,)``: its
         output); ``bytes_per_item``: the buffers one pedestrian takes. ``stages``: one :class:`Stage` per stage given.
+        ``half``: the names of the stages to run on binary16 MFMA operands with float32 accumulation -- ``("layer3",)`` (needs
+        ``blocks3``; ``nmpc_mmp_block3_f16``, csrc/nmpc_mmp_block3_f16.h, whose header states the rounding rule) or ``()``; the stage's
+        record then carries the packed specs, that kernel's struct and its launch method, and nothing else differs: the buffers
+        stay float32 where they were.
 
         Where a stage's two buffers lie is one rule: the fill's output (the stem's, ``[C, Hp, Wp]`` per row) is idle once layer1's
         first block has read it, so the buffers of the stages behind layer1 are laid INSIDE it one behind the other, at a running
@@ -60,8 +66,10 @@ class MmpFrontEnd:
         import torch
         specs = self.check_specs(stem, blocks, blocks2=blocks2, blocks3=blocks3, blocks4=blocks4, head=head)
         stem, head = specs[0], specs[-1]
+        self.half = self.check_half(half, specs)
         self.h, self.dt, self.dev, self.n_off = handle, np.dtype(dtype), device, int(n_off)
-        dev = lambda spec, names: spec._replace(**{n: torch.as_tensor(getattr(spec, n), device=device) for n in names if getattr(spec, n) is not None})
+        bits = lambda a: a.view(np.int16) if a.dtype == np.uint16 else a          # (packed binary16 bit patterns travel as int16)
+        dev = lambda spec, names: spec._replace(**{n: torch.as_tensor(bits(getattr(spec, n)), device=device) for n in names if getattr(spec, n) is not None})
         self.stem = None if stem is None else dev(stem, ("weight", "scale", "shift"))
         self.ref = ref_image
         if stem is None:
@@ -78,13 +86,18 @@ class MmpFrontEnd:
         self.row, self.bytes_per_item = self.fill_row, self.n_off * fill_size * 4
         self.stages, offset, inside = [], 0, True           # offset: floats of a fill row given away so far; inside: nothing overflowed yet
         for table, (Args, launch), given in zip(STAGES, _DEVICE, specs[1:-1]):
+            if given is not None and table.layer in self.half:
+                pack, Args, launch = _HALF[table.layer]
+                cins, given = tuple(int(b.w1.shape[1]) for b in given), tuple(pack(b) for b in given)
+            elif given is not None:
+                cins = tuple(int(b.w1.shape[1]) for b in given)
             setattr(self, table.arg, None if given is None else tuple(dev(b, _BLOCK_ARRAYS) for b in given))
             if given is None:
                 continue
             planes = [self.row[1:]]
             for b in given:
                 planes.append(block2_plane(*planes[-1], getattr(b, "stride", 1)))       # (layer1's blocks have no stride: 1)
-            st = Stage(table.layer, table.channels, getattr(self, table.arg), Args, getattr(handle, launch), planes, reads_fill=not self.stages)
+            st = Stage(table.layer, table.channels, getattr(self, table.arg), cins, Args, getattr(handle, launch), planes, reads_fill=not self.stages)
             size = 2 * int(np.prod(st.buf_row))
             st.in_fill = inside and not st.reads_fill and offset + size <= fill_size
             if st.in_fill:
@@ -123,6 +136,18 @@ class MmpFrontEnd:
             out.append(v)
         return tuple(out)
 
+    @staticmethod
+    def check_half(half, specs, prefix: str = "") -> tuple:
+        """``half`` as a tuple of stage names, checked against the checked ``specs`` of ``check_specs`` (all six)."""
+        half = (half,) if isinstance(half, str) else tuple(half)
+        for name in half:
+            if name not in _HALF:
+                raise ValueError(f"{prefix}half: {name!r}: only layer3 has an f16 kernel")
+            k = next(i for i, st in enumerate(STAGES) if st.layer == name)
+            if specs[1 + k] is None:
+                raise ValueError(f"{prefix}half: {name!r} needs {prefix}{STAGES[k].arg}")
+        return tuple(dict.fromkeys(half))
+
     def stage(self, name: str):
         """The :class:`Stage` called ``name`` (``"layer1"`` ..), or ``None`` if its specs were not given."""
         return next((st for st in self.stages if st.name == name), None)
@@ -141,7 +166,7 @@ class MmpFrontEnd:
             st.pp = self._fill_buf.view(-1)[rows * st.offset:rows * (st.offset + 2 * n)].view(2, rows * n) if st.in_fill else new(2, rows * n)
             for i, b in enumerate(st.specs):
                 a = st.Args()
-                a.Cin, (a.H, a.W) = int(b.w1.shape[1]), st.planes[i]
+                a.Cin, (a.H, a.W) = st.cins[i], st.planes[i]
                 for name, v in zip(b._fields, b):           # the weights' pointers, the slopes and, where the stage has one, the stride
                     setattr(a, name, v.data_ptr() if torch.is_tensor(v) else v)
                 a.x, a.out = x.data_ptr(), st.pp[i % 2].data_ptr()

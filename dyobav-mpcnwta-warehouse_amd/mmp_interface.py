@@ -37,7 +37,7 @@ OBSV_LEN = 5        # config.obsv_len of the reference's network configurations
 
 
 class MmpInterface:
-    def __init__(self, network: Optional[Callable] = None, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None):
+    def __init__(self, network: Optional[Callable] = None, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=()):
         """``stem``: a :class:`.mmp_stem.StemSpec` = the network's first layer, computed on the device without the input stack
         (``nmpc_mmp_stem_f64``); ``network`` is then the trunk behind it, a callable on ``[M, C, Hp, Wp]``. ``blocks`` (needs
         ``stem``): the :class:`.mmp_stem.BlockSpec` s of the residual stage behind the stem (``mmp_stem.split_network_layer1``),
@@ -50,7 +50,9 @@ class MmpInterface:
         (``mmp_stem.split_network_layer4``, ``nmpc_mmp_block4_f32``); ``network`` is then the trunk from ``apool`` on, called on
         ``[M, 128, H4, W4]``. ``head`` (needs ``blocks4``): the :class:`.mmp_stem.HeadSpec` of the network's end
         (``mmp_stem.split_network_whole``, ``nmpc_mmp_head_f32``); ``network`` must then be ``None``, and ``batch_size`` no longer
-        splits anything."""
+        splits anything. ``half``: ``("layer3",)`` (needs ``blocks3``) runs that stage's blocks on binary16 MFMA operands with float32
+        accumulation (``nmpc_mmp_block3_f16``; the rounding rule: csrc/nmpc_mmp_block3_f16.h); ``()`` changes nothing; any other
+        stage name is a ``ValueError``: only layer3 has an f16 kernel."""
         if head is not None and network is not None:
             raise TypeError("head is the network's end: network must be None with it")
         if head is None and not callable(network):
@@ -58,6 +60,7 @@ class MmpInterface:
         self._prt_name = "MMPInterface"
         self.network = network
         self._specs = MmpFrontEnd.check_specs(stem, blocks, blocks2=blocks2, blocks3=blocks3, blocks4=blocks4, head=head)
+        self._half = MmpFrontEnd.check_half(half, self._specs)
         for name, spec in zip(SPEC_NAMES, self._specs):
             setattr(self, name, spec)
         self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)
@@ -106,7 +109,7 @@ class MmpInterface:
         key = (N, Hm, Wm, float(rescale))
         if key not in self._fronts:
             d_ref = torch.empty(Hm, Wm, dtype=torch.float32, device=d_hist.device)
-            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, *self._specs)
+            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, *self._specs, half=self._half)
             self._fronts[key].allocate(1)
         fe = self._fronts[key]
         fe.ref.copy_(torch.from_numpy(img))

@@ -31,7 +31,9 @@ blocks2=blocks2, ...)``. The network's end -- ``AvgPool2d(2, 2)``, flatten,
 ``fc1 = Linear(F, 128)``, ``leaky``, ``swarm.layer_hypos = Linear(128, 2 K)`` -- is one launch (``nmpc_mmp_head_f32``,
 csrc/nmpc_mmp_head.h): ``HeadSpec(w1, c1, slope, w2, c2)`` from ``fold_head``, and ``split_network_whole(net)`` returns the stem,
 the four tuples of blocks and the head with NO trunk left, for ``BatchEvaluator(..., mmp_blocks4=blocks4, mmp_head=head)`` and
-``MmpInterface(None, ..., blocks4=blocks4, head=head)``."""
+``MmpInterface(None, ..., blocks4=blocks4, head=head)``. Layer3 also has a kernel on binary16 MFMA operands (``nmpc_mmp_block3_f16``,
+csrc/nmpc_mmp_block3_f16.h; ``half=("layer3",)`` in the callers): ``pack_block3_f16`` rounds a ``Block3Spec``'s weights once and packs
+them in the order the kernel's lanes load them, ``unpack_block3_f16`` inverts it, ``round_f16`` is the rounding."""
 from __future__ import annotations
 
 from typing import Callable, NamedTuple, Optional, Tuple
@@ -389,6 +391,56 @@ def check_block3(spec) -> Block3Spec:
 def check_block4(spec) -> Block4Spec:
     """As ``check_block2``, at 128 output channels."""
     return _check_strided(spec, BLOCK4_CHANNELS, Block4Spec)
+
+
+# Layer3 with binary16 MFMA operands (``nmpc_mmp_block3_f16``, csrc/nmpc_mmp_block3_f16.h): Block3Spec's fields with ``w1``, ``w2`` and
+# ``wd`` rounded to binary16 and packed in the order the kernel's lanes load them, as uint16 bit patterns:
+#   w1 [9, KB, 4, 64, 8]: [tap 3 ky + kx][K block kb][group g][lane l][j] = f16(w1[16 g + (l & 15), 32 kb + 8 (l >> 4) + j, ky, kx]),
+#   KB = ceil(Cin / 32), zero where the input channel is >= Cin; w2 the same with Cin = 64; wd [KB, 4, 64, 8] without the tap.
+# The scales, the shifts, the slopes and the stride are Block3Spec's, unchanged, in float32.
+Block3F16Spec = NamedTuple("Block3F16Spec", _STRIDED_FIELDS)
+F16_MAX = 65504.0
+
+
+def round_f16(a) -> np.ndarray:
+    """The rounding of the f16 kernels as numpy states it: clipped to +-65504 (the infinities with the finite values, NaN stays
+    NaN), then rounded to nearest even with subnormals kept -> ``np.float16``."""
+    return np.clip(np.asarray(a), -F16_MAX, F16_MAX).astype(np.float16)
+
+
+def _pack_f16(w) -> np.ndarray:
+    """``[64, Cin, T]`` -> ``[T, KB, 4, 64, 8]`` uint16 in fragment order."""
+    C, Cin, T = w.shape
+    KB = (Cin + 31) // 32
+    wp = np.zeros((C, 32 * KB, T), dtype=np.float16)
+    wp[:, :Cin] = round_f16(w)
+    # [g, row, kb, quad, j, t] -> [t, kb, g, quad, row, j]: lane = 16 quad + row
+    return np.ascontiguousarray(wp.reshape(C // 16, 16, KB, 4, 8, T).transpose(5, 2, 0, 3, 1, 4)).reshape(T, KB, C // 16, 64, 8).view(np.uint16)
+
+
+def _unpack_f16(p, Cin: int) -> np.ndarray:
+    """``[T, KB, 4, 64, 8]`` uint16 -> ``[64, Cin, T]`` float16: the inverse of ``_pack_f16`` (the padding channels dropped)."""
+    T, KB, G = p.shape[:3]
+    w = np.ascontiguousarray(p).view(np.float16).reshape(T, KB, G, 4, 16, 8).transpose(2, 4, 1, 3, 5, 0)
+    return np.ascontiguousarray(w.reshape(16 * G, 32 * KB, T)[:, :Cin])
+
+
+def pack_block3_f16(spec) -> Block3F16Spec:
+    """A :class:`Block3Spec` -> :class:`Block3F16Spec`: the three weight arrays rounded once (``round_f16``) and packed; everything
+    else passed through. ``ValueError`` for what ``check_block3`` refuses."""
+    spec = check_block3(spec)
+    C, Cin = spec.w1.shape[:2]
+    wd = None if spec.wd is None else _pack_f16(spec.wd.reshape(C, Cin, 1))[0]
+    return Block3F16Spec(*spec._replace(w1=_pack_f16(spec.w1.reshape(C, Cin, 9)), w2=_pack_f16(spec.w2.reshape(C, C, 9)), wd=wd))
+
+
+def unpack_block3_f16(packed, Cin: int) -> Block3Spec:
+    """The inverse of ``pack_block3_f16`` for a block of ``Cin`` input channels: a :class:`Block3Spec` whose ``w1`` [64, Cin, 3, 3],
+    ``w2`` and ``wd`` [64, Cin] are the ROUNDED weights as ``np.float16``."""
+    C = BLOCK3_CHANNELS
+    wd = None if packed.wd is None else _unpack_f16(np.asarray(packed.wd)[None], Cin).reshape(C, Cin)
+    return Block3Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
+                                       w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
 
 
 def _linear(fn, name, layer, n_in, n_out):

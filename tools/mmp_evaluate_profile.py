@@ -45,7 +45,7 @@ above, with HIP events around ``input``, ``layer1`` .. ``layer4``, ``head`` / ``
 torch's own layer4 and its pool and linear layers, eager, each alone on one chunk of the parent path's layer3 output; then the
 three block launches and the head launch alone on that chunk, next to the model of csrc/nmpc_mmp_block4.h.
    usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]
-          [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS] | --fused-layer4 [REPS]]
+          [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS] | --fused-layer4 [REPS] | --half-layer3 [REPS]]
           (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
@@ -321,7 +321,7 @@ def torch_layer2_alone(ev, layer2, n_item, reps=5):
     return dict(items=n_item, samples=rows, **t)
 
 
-def _strided_kernel_rate(fe, rows, reps, blocks, C, first, plane, run_all):
+def _strided_kernel_rate(fe, rows, reps, blocks, C, first, plane, run_all, cins=None):
     """The launches of one strided stage (``blocks`` at ``C`` output channels, ``run_block(first ..)``, input plane ``plane``) alone
     on ``rows`` rows of what the stage in front left: ms each and together, useful fma per second (C (9 Cin + 9 C (+ Cin)) per
     output pixel) and bytes per second (x read once, out written once)."""
@@ -329,7 +329,7 @@ def _strided_kernel_rate(fe, rows, reps, blocks, C, first, plane, run_all):
     rec = {"rows": rows, "blocks": []}
     fma_all = bytes_all = 0
     for i, b in enumerate(blocks):
-        Cin, proj, s = int(b.w1.shape[1]), b.wd is not None, int(b.stride)
+        Cin, proj, s = (cins[i] if cins else int(b.w1.shape[1])), b.wd is not None, int(b.stride)      # (cins: packed weights do not show Cin)
         H2, W2 = (H - 1) // s + 1, (W - 1) // s + 1
         fma = rows * H2 * W2 * C * (9 * Cin + 9 * C + (Cin if proj else 0))
         nbytes = rows * 4 * (Cin * H * W + C * H2 * W2)
@@ -369,7 +369,8 @@ def block3_kernel_rate(ev, n_item, reps=10):
     rows = _fill(ev, n_item)().shape[0]
     fe.run_blocks(rows)
     plane = tuple(fe.run_blocks2(rows).shape[2:])
-    return {"items": n_item, **_strided_kernel_rate(fe, rows, reps, fe.blocks3, 64, len(fe.blocks) + len(fe.blocks2), plane, fe.run_blocks3)}
+    return {"items": n_item, **_strided_kernel_rate(fe, rows, reps, fe.blocks3, 64, len(fe.blocks) + len(fe.blocks2), plane, fe.run_blocks3,
+                                                    cins=fe.stage("layer3").cins)}
 
 
 def fused_layer2_main(out_path, B, steps, dt, n_ped, K, reps):
@@ -656,8 +657,86 @@ def fused_layer4_main(out_path, B, steps, dt, n_ped, K, reps):
     print(json.dumps({"block4": [(b["Cin"], b["stride"], b["ms_median"], b["TFMAps_median"]) for b in bk["blocks"]], "all": (bk["ms_median"], bk["TFMAps_median"])}))
 
 
+def half_layer3_main(out_path, B, steps, dt, n_ped, K, reps):
+    """``--half-layer3``: the whole network on the device (the new path of ``--fused-layer4``) with layer3 on float32 operands and with
+    ``mmp_half=("layer3",)`` (nmpc_mmp_block3_f16), alternated in one process: the six launches alone on one chunk, then the closed
+    loop with events around every part."""
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import split_network_whole
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    as_block = lambda b: SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)
+    L = list(net)
+    shaped = SimpleNamespace(resnet34=SimpleNamespace(stem=SimpleNamespace(conv1=L[0], pooling=L[1]), layer1=[as_block(b) for b in L[2:5]],
+                                                      layer2=[as_block(b) for b in L[5:9]], layer3=[as_block(b) for b in L[9:15]],
+                                                      layer4=[as_block(b) for b in L[15:18]], apool=L[18]), fc1=L[20], leaky=L[21], swarm=L[22])
+    spec, blocks, blocks2, blocks3, blocks4, head = split_network_whole(shaped)
+    head = head._replace(c2=head.c2 + np.float32(150.0))   # (the "+ 150" that puts the random network's hypotheses on the map)
+    whole = dict(network=None, mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, mmp_blocks3=blocks3, mmp_blocks4=blocks4, mmp_head=head)
+    paths = {"fp32": dict(whole), "f16": dict(whole, mmp_half=("layer3",))}
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rows_step = B * n_ped * nm.default_config_struct().N_hor
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage, the whole network on the device: layer3 "
+                   "on float32 MFMA operands (nmpc_mmp_block3_f32) and on binary16 operands with float32 accumulation (nmpc_mmp_block3_f16, "
+                   "mmp_half = ('layer3',)), alternated in one process; random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS, "fp32_peak_TFMAps": PEAK_TFMAS},
+           "model_of_the_f16_header_per_lock_step_ms": {"mfma_pipe_never_waits": 4.3, "memory_at_copy_rate": 4.3},
+           "fp32_mfma_never_waits_floor_over_fp32_measured": 0.57, "chunk_pedestrians": {}, "block3_kernels": {p: [] for p in paths},
+           "runs": {p: [] for p in paths}}
+    for _ in range(reps):                                   # the six launches alone, three runs per arm, alternated (the first also warms up)
+        for path in paths:
+            ev = evaluator(path)
+            rec["chunk_pedestrians"][path] = ev.mmp_chunk
+            try:
+                rec["block3_kernels"][path].append(block3_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped)))
+                ev.run(max_steps=1)
+            finally:
+                ev.close()
+            r = rec["block3_kernels"][path][-1]
+            print(path, json.dumps({"rows": r["rows"], "six_launches_ms": r["ms_median"], "each": [b["ms_median"] for b in r["blocks"]]}), flush=True)
+            with open(out_path, "w") as f:
+                json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = ("input", "layer1", "layer2", "layer3", "layer4", "head")
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names}, stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    rec["stage_median_of_each_run_ms"] = {p: [float(np.median([s["stage_ms"] for s in run])) for run in rec["runs"][p]] for p in paths}
+    rec["layer3_median_of_each_run_ms"] = {p: [float(np.median([s["layer3"] for s in run])) for run in rec["runs"][p]] for p in paths}
+    rec["six_launches_of_each_run_ms"] = {p: [r["ms_median"] for r in rec["block3_kernels"][p]] for p in paths}
+    rec["six_launches_per_lock_step_ms"] = {p: float(np.median([r["ms_median"] * rows_step / r["rows"] for r in rec["block3_kernels"][p]])) for p in paths}
+    six, m = rec["six_launches_of_each_run_ms"], rec["median_per_lock_step_ms"]
+    rec["f16_over_fp32_six_launches"] = float(np.median(six["f16"]) / np.median(six["fp32"]))
+    rec["f16_over_fp32_stage"] = m["f16"]["stage"] / m["fp32"]["stage"]
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "stage_median_of_each_run_ms", "layer3_median_of_each_run_ms", "six_launches_of_each_run_ms",
+                                          "six_launches_per_lock_step_ms", "f16_over_fp32_six_launches", "f16_over_fp32_stage", "chunk_pedestrians")}))
+    for p in paths:
+        r = rec["block3_kernels"][p][-1]
+        print(p, json.dumps([(b["Cin"], b["stride"], b["ms_median"], b["TFMAps_median"], b["GBps_median"]) for b in r["blocks"]]))
+
+
 def main():
-    for flag, run in (("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+    for flag, run in (("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
         if flag in sys.argv:
             i = sys.argv.index(flag)
             reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
