@@ -193,6 +193,12 @@ class NmpcMmpBlock4Args(C.Structure):
     _fields_ = NmpcMmpBlock3Args._fields_
 
 
+class NmpcMmpBlock4F16Args(C.Structure):
+    """Mirror of ``struct nmpc_mmp_block4_f16_args`` (device pointers): the fields of ``NmpcMmpBlock4Args``, with ``w1``, ``w2`` and
+    ``wd`` the packed binary16 fragments of ``mmp_stem.pack_block4_f16`` (aligned to 16 bytes)."""
+    _fields_ = NmpcMmpBlock4Args._fields_
+
+
 class NmpcMmpHeadArgs(C.Structure):
     """Mirror of ``struct nmpc_mmp_head_args`` (device pointers): the network's end, ``x`` [M, C, H, W] -> ``out`` [M, O] through the
     2 x 2 average pool, ``w1`` [128, F], ``c1`` [128], the slope, ``w2`` [O, 128] and ``c2`` [O]."""
@@ -215,7 +221,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
     "nmpc_dwa_step_lists_f32", "nmpc_dwa_step_lists_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
-    "nmpc_mmp_block2_f32", "nmpc_mmp_block3_f32", "nmpc_mmp_block3_f16", "nmpc_mmp_block4_f32", "nmpc_mmp_head_f32",
+    "nmpc_mmp_block2_f32", "nmpc_mmp_block3_f32", "nmpc_mmp_block3_f16", "nmpc_mmp_block4_f32", "nmpc_mmp_block4_f16", "nmpc_mmp_head_f32",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
     "nmpc_last_error",
 )
@@ -313,6 +319,7 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     lib.nmpc_mmp_block3_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock3Args)]
     lib.nmpc_mmp_block3_f16.argtypes = [vp, C.POINTER(NmpcMmpBlock3F16Args)]
     lib.nmpc_mmp_block4_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock4Args)]
+    lib.nmpc_mmp_block4_f16.argtypes = [vp, C.POINTER(NmpcMmpBlock4F16Args)]
     lib.nmpc_mmp_head_f32.argtypes = [vp, C.POINTER(NmpcMmpHeadArgs)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     lib.nmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -569,6 +576,11 @@ class Handle:
         """``nmpc_mmp_block3_f16``: the block of ``mmp_block3`` with binary16 MFMA operands and float32 accumulation (the rounding
         rule: include/nmpc_hip.h), on the packed weights of ``mmp_stem.pack_block3_f16``; ``x`` and ``out`` stay float32."""
         _check(self._lib.nmpc_mmp_block3_f16(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_block4_f16(self, args: "NmpcMmpBlock4F16Args"):
+        """``nmpc_mmp_block4_f16``: the block of ``mmp_block4`` with binary16 MFMA operands and float32 accumulation (the rounding
+        rule: include/nmpc_hip.h), on the packed weights of ``mmp_stem.pack_block4_f16``; ``x`` and ``out`` stay float32."""
+        _check(self._lib.nmpc_mmp_block4_f16(self._h, C.byref(args) if args is not None else None))
 
     def mmp_block4(self, args: "NmpcMmpBlock4Args"):
         """``nmpc_mmp_block4_f32``: one fused residual block of the network's layer4 (as ``mmp_block3``, at 128 output channels),

@@ -33,6 +33,7 @@
 #include "nmpc_mmp_block3.h"
 #include "nmpc_mmp_block3_f16.h"
 #include "nmpc_mmp_block4.h"
+#include "nmpc_mmp_block4_f16.h"
 #include "nmpc_mmp_head.h"
 
 using namespace nmpc_plan;
@@ -1802,11 +1803,22 @@ struct MmpLayer4 {
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk4_kernel<2, true>, nmpc::mmp_blk4_kernel<1, true>, nmpc::mmp_blk4_kernel<1, false>};
     // tiles of at most 10 x 11 = 110 outputs; reach 11. A side that fits the tile's plane of m is one tile without a halo; a longer
     // one is cut with a halo of one
-    static void tile(Params& p, long long& ty, long long& tx)
+    template <typename P>
+    static void tile(P& p, long long& ty, long long& tx)
     {
         ty = nmpc::mmp_b4_tiles(p.H2, nmpc::kB4MH), tx = nmpc::mmp_b4_tiles(p.W2, nmpc::kB4MW);
         p.oy = p.H2 <= nmpc::kB4MH ? 1 : 2, p.ox = p.W2 <= nmpc::kB4MW ? 1 : 2;
     }
+};
+
+// layer4 with binary16 MFMA operands (csrc/nmpc_mmp_block4_f16.h): layer4's channels and tiles on workgroups of 256 threads; w1,
+// w2 and wd are the packed fragments, 16 bytes per lane, which is what packed_align adds to the checks
+struct MmpLayer4F16 : MmpLayer4 {
+    using Args = nmpc_mmp_block4_f16_args;
+    using Params = nmpc::MmpBlock4HParams;
+    static constexpr const char* name = "nmpc_mmp_block4_f16";
+    static constexpr int threads = nmpc::kB4HThreads, packed_align = 16;
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk4h_kernel<2, true>, nmpc::mmp_blk4h_kernel<1, true>, nmpc::mmp_blk4h_kernel<1, false>};
 };
 
 template <typename Stage>
@@ -2415,6 +2427,7 @@ int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return m
 int nmpc_mmp_block3_f32(nmpc_handle h, const nmpc_mmp_block3_args* a) { return mmp_strided<MmpLayer3>(h, a); }
 int nmpc_mmp_block3_f16(nmpc_handle h, const nmpc_mmp_block3_f16_args* a) { return mmp_strided<MmpLayer3F16>(h, a); }
 int nmpc_mmp_block4_f32(nmpc_handle h, const nmpc_mmp_block4_args* a) { return mmp_strided<MmpLayer4>(h, a); }
+int nmpc_mmp_block4_f16(nmpc_handle h, const nmpc_mmp_block4_f16_args* a) { return mmp_strided<MmpLayer4F16>(h, a); }
 int nmpc_mmp_head_f32(nmpc_handle h, const nmpc_mmp_head_args* a) { return mmp_head(h, a); }
 int nmpc_mmp_stem_shape(int32_t Hm, int32_t Wm, int32_t* Hp, int32_t* Wp)
 {

@@ -192,12 +192,14 @@ class BatchEvaluator:
         ``mmp_hyp`` must be half the head's outputs. Measured in the same setting (``profiles/mmp_layer4_evaluate.json``, DESIGN.md
         section 7): the stage takes 389 ms per lock-step against 420 ms without; the three launches 58 ms where torch's own layer4
         took 95, the head 4.4 ms where torch's pool and linear layers took 3.0.
-        ``mmp_half``: the stages to run on binary16 MFMA operands with float32 accumulation: ``("layer3",)`` (needs ``mmp_blocks3``;
-        ``nmpc_mmp_block3_f16``, csrc/nmpc_mmp_block3_f16.h) or ``()``, the default, which changes nothing. The rule: whatever an
+        ``mmp_half``: the stages to run on binary16 MFMA operands with float32 accumulation: ``"layer3"`` (needs ``mmp_blocks3``;
+        ``nmpc_mmp_block3_f16``, csrc/nmpc_mmp_block3_f16.h), ``"layer4"`` (with ``mmp_blocks4``; ``nmpc_mmp_block4_f16``,
+        csrc/nmpc_mmp_block4_f16.h), both, or ``()``, the default, which changes nothing. The rule: whatever an
         MFMA reads -- the weights, rounded once on the host; ``x`` as it is staged; the first convolution's activated output as it
         goes to LDS -- is binary16, rounded to nearest even and saturated at +-65504; nothing else is: the activations in memory, the
         accumulation, the affines, the LeakyReLUs and the identity stay float32. What that costs and gains, measured: DESIGN.md
-        section 7, ``profiles/mmp_layer3_f16_evaluate.json``. Any other stage name is a ``ValueError``: only layer3 has an f16 kernel.
+        section 7, ``profiles/mmp_layer3_f16_evaluate.json`` and ``profiles/mmp_layer4_f16_evaluate.json``. Any other stage name is a
+        ``ValueError``: only layer3 has an f16 kernel, and layer4 where ``mmp_blocks4`` is given.
 
         ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the

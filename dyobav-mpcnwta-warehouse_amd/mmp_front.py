@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
-from .mmp_stem import STAGES, block2_plane, check_head, check_spec, check_stage, head_features, pack_block3_f16
+from .mmp_stem import STAGES, block2_plane, check_head, check_spec, check_stage, head_features, pack_block3_f16, pack_block4_f16
 
 _BLOCK_ARRAYS = ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
 _HEAD_ARRAYS = ("w1", "c1", "w2", "c2")
@@ -22,7 +22,8 @@ SPEC_NAMES = ("stem",) + tuple(st.arg for st in STAGES) + ("head",)     # the sp
 _DEVICE = ((_capi.NmpcMmpBlockArgs, "mmp_block"), (_capi.NmpcMmpBlock2Args, "mmp_block2"), (_capi.NmpcMmpBlock3Args, "mmp_block3"),
            (_capi.NmpcMmpBlock4Args, "mmp_block4"))
 # ``half=``: the stages that have a kernel with binary16 MFMA operands -- how their checked specs are packed, the struct, the method
-_HALF = {"layer3": (pack_block3_f16, _capi.NmpcMmpBlock3F16Args, "mmp_block3_f16")}
+_HALF = {"layer3": (pack_block3_f16, _capi.NmpcMmpBlock3F16Args, "mmp_block3_f16"),
+         "layer4": (pack_block4_f16, _capi.NmpcMmpBlock4F16Args, "mmp_block4_f16")}
 # what each keyword behind ``stem`` needs in front of it, as ``check_specs`` says it
 _NEEDS = (("the blocks run on the fused first layer's output",)
           + tuple(f"the blocks of {st.layer} run on the fused {prev.layer}'s output" for prev, st in zip(STAGES, STAGES[1:]))
@@ -52,8 +53,9 @@ class MmpFrontEnd:
         ``blocks4``): the ``HeadSpec`` of the network's end, whose ``F`` must be ``128 * (H4 // 2) * (W4 // 2)`` for the plane that
         arrives. ``fill_row``: a row of what the fill writes; ``row``: a row of what the network sees (with a head ``(O,)``: its
         output); ``bytes_per_item``: the buffers one pedestrian takes. ``stages``: one :class:`Stage` per stage given.
-        ``half``: the names of the stages to run on binary16 MFMA operands with float32 accumulation -- ``("layer3",)`` (needs
-        ``blocks3``; ``nmpc_mmp_block3_f16``, csrc/nmpc_mmp_block3_f16.h, whose header states the rounding rule) or ``()``; the stage's
+        ``half``: the names of the stages to run on binary16 MFMA operands with float32 accumulation -- ``"layer3"`` (needs
+        ``blocks3``; ``nmpc_mmp_block3_f16``, csrc/nmpc_mmp_block3_f16.h, whose header states the rounding rule), ``"layer4"`` (with
+        ``blocks4``; ``nmpc_mmp_block4_f16``, csrc/nmpc_mmp_block4_f16.h, the same rule), both, or ``()``; such a stage's
         record then carries the packed specs, that kernel's struct and its launch method, and nothing else differs: the buffers
         stay float32 where they were.
 
@@ -141,9 +143,9 @@ class MmpFrontEnd:
         """``half`` as a tuple of stage names, checked against the checked ``specs`` of ``check_specs`` (all six)."""
         half = (half,) if isinstance(half, str) else tuple(half)
         for name in half:
-            if name not in _HALF:
-                raise ValueError(f"{prefix}half: {name!r}: only layer3 has an f16 kernel")
-            k = next(i for i, st in enumerate(STAGES) if st.layer == name)
+            k = next((i for i, st in enumerate(STAGES) if st.layer == name), None)
+            if name not in _HALF or (name == "layer4" and specs[1 + k] is None):
+                raise ValueError(f"{prefix}half: {name!r}: only layer3 has an f16 kernel, and layer4 where {prefix}blocks4 is given")
             if specs[1 + k] is None:
                 raise ValueError(f"{prefix}half: {name!r} needs {prefix}{STAGES[k].arg}")
         return tuple(dict.fromkeys(half))

@@ -50,9 +50,10 @@ class MmpInterface:
         (``mmp_stem.split_network_layer4``, ``nmpc_mmp_block4_f32``); ``network`` is then the trunk from ``apool`` on, called on
         ``[M, 128, H4, W4]``. ``head`` (needs ``blocks4``): the :class:`.mmp_stem.HeadSpec` of the network's end
         (``mmp_stem.split_network_whole``, ``nmpc_mmp_head_f32``); ``network`` must then be ``None``, and ``batch_size`` no longer
-        splits anything. ``half``: ``("layer3",)`` (needs ``blocks3``) runs that stage's blocks on binary16 MFMA operands with float32
-        accumulation (``nmpc_mmp_block3_f16``; the rounding rule: csrc/nmpc_mmp_block3_f16.h); ``()`` changes nothing; any other
-        stage name is a ``ValueError``: only layer3 has an f16 kernel."""
+        splits anything. ``half``: ``"layer3"`` (needs ``blocks3``) and ``"layer4"`` (with ``blocks4``), alone or together, run
+        that stage's blocks on binary16 MFMA operands with float32 accumulation (``nmpc_mmp_block3_f16``, ``nmpc_mmp_block4_f16``;
+        the rounding rule: csrc/nmpc_mmp_block3_f16.h); ``()`` changes nothing; any other stage name is a ``ValueError``: only
+        layer3 has an f16 kernel, and layer4 where ``blocks4`` is given."""
         if head is not None and network is not None:
             raise TypeError("head is the network's end: network must be None with it")
         if head is None and not callable(network):

@@ -33,7 +33,9 @@ csrc/nmpc_mmp_head.h): ``HeadSpec(w1, c1, slope, w2, c2)`` from ``fold_head``, a
 the four tuples of blocks and the head with NO trunk left, for ``BatchEvaluator(..., mmp_blocks4=blocks4, mmp_head=head)`` and
 ``MmpInterface(None, ..., blocks4=blocks4, head=head)``. Layer3 also has a kernel on binary16 MFMA operands (``nmpc_mmp_block3_f16``,
 csrc/nmpc_mmp_block3_f16.h; ``half=("layer3",)`` in the callers): ``pack_block3_f16`` rounds a ``Block3Spec``'s weights once and packs
-them in the order the kernel's lanes load them, ``unpack_block3_f16`` inverts it, ``round_f16`` is the rounding."""
+them in the order the kernel's lanes load them, ``unpack_block3_f16`` inverts it, ``round_f16`` is the rounding. Layer4 has the
+same under the same rule (``nmpc_mmp_block4_f16``, csrc/nmpc_mmp_block4_f16.h; ``half=("layer4",)`` or ``("layer3", "layer4")``):
+``pack_block4_f16`` and ``unpack_block4_f16`` on a ``Block4Spec``, eight groups of sixteen output channels where layer3 has four."""
 from __future__ import annotations
 
 from typing import Callable, NamedTuple, Optional, Tuple
@@ -409,7 +411,7 @@ def round_f16(a) -> np.ndarray:
 
 
 def _pack_f16(w) -> np.ndarray:
-    """``[64, Cin, T]`` -> ``[T, KB, 4, 64, 8]`` uint16 in fragment order."""
+    """``[C, Cin, T]`` -> ``[T, KB, C // 16, 64, 8]`` uint16 in fragment order (``C`` = 64 or 128 output channels: 4 or 8 groups)."""
     C, Cin, T = w.shape
     KB = (Cin + 31) // 32
     wp = np.zeros((C, 32 * KB, T), dtype=np.float16)
@@ -419,7 +421,7 @@ def _pack_f16(w) -> np.ndarray:
 
 
 def _unpack_f16(p, Cin: int) -> np.ndarray:
-    """``[T, KB, 4, 64, 8]`` uint16 -> ``[64, Cin, T]`` float16: the inverse of ``_pack_f16`` (the padding channels dropped)."""
+    """``[T, KB, G, 64, 8]`` uint16 -> ``[16 G, Cin, T]`` float16: the inverse of ``_pack_f16`` (the padding channels dropped)."""
     T, KB, G = p.shape[:3]
     w = np.ascontiguousarray(p).view(np.float16).reshape(T, KB, G, 4, 16, 8).transpose(2, 4, 1, 3, 5, 0)
     return np.ascontiguousarray(w.reshape(16 * G, 32 * KB, T)[:, :Cin])
@@ -440,6 +442,29 @@ def unpack_block3_f16(packed, Cin: int) -> Block3Spec:
     C = BLOCK3_CHANNELS
     wd = None if packed.wd is None else _unpack_f16(np.asarray(packed.wd)[None], Cin).reshape(C, Cin)
     return Block3Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
+                                       w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
+
+
+# Layer4 with binary16 MFMA operands (``nmpc_mmp_block4_f16``, csrc/nmpc_mmp_block4_f16.h): the same rule and the same order with
+# eight groups of output channels: w1 [9, KB, 8, 64, 8], w2 [9, 4, 8, 64, 8] (Cin = 128), wd [KB, 8, 64, 8]; the rest is Block4Spec's.
+Block4F16Spec = NamedTuple("Block4F16Spec", _STRIDED_FIELDS)
+
+
+def pack_block4_f16(spec) -> Block4F16Spec:
+    """A :class:`Block4Spec` -> :class:`Block4F16Spec`: the three weight arrays rounded once (``round_f16``) and packed; everything
+    else passed through. ``ValueError`` for what ``check_block4`` refuses."""
+    spec = check_block4(spec)
+    C, Cin = spec.w1.shape[:2]
+    wd = None if spec.wd is None else _pack_f16(spec.wd.reshape(C, Cin, 1))[0]
+    return Block4F16Spec(*spec._replace(w1=_pack_f16(spec.w1.reshape(C, Cin, 9)), w2=_pack_f16(spec.w2.reshape(C, C, 9)), wd=wd))
+
+
+def unpack_block4_f16(packed, Cin: int) -> Block4Spec:
+    """The inverse of ``pack_block4_f16`` for a block of ``Cin`` input channels: a :class:`Block4Spec` whose ``w1`` [128, Cin, 3, 3],
+    ``w2`` and ``wd`` [128, Cin] are the ROUNDED weights as ``np.float16``."""
+    C = BLOCK4_CHANNELS
+    wd = None if packed.wd is None else _unpack_f16(np.asarray(packed.wd)[None], Cin).reshape(C, Cin)
+    return Block4Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
                                        w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
 
 
