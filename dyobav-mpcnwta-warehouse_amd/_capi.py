@@ -173,6 +173,12 @@ class NmpcMmpBlock2Args(C.Structure):
     _fields_ = NmpcMmpBlockArgs._fields_ + [("stride", C.c_int32)]
 
 
+class NmpcMmpBlock2F16Args(C.Structure):
+    """Mirror of ``struct nmpc_mmp_block2_f16_args`` (device pointers): the fields of ``NmpcMmpBlock2Args``, with ``w1``, ``w2`` and
+    ``wd`` the packed binary16 fragments of ``mmp_stem.pack_block2_f16`` (aligned to 16 bytes)."""
+    _fields_ = NmpcMmpBlock2Args._fields_
+
+
 class NmpcMmpBlock3Args(C.Structure):
     """Mirror of ``struct nmpc_mmp_block3_args`` (device pointers): one residual block of the network's layer3, ``x`` [M, Cin, H, W]
     -> ``out`` [M, 64, H2, W2]; the fields of ``NmpcMmpBlock2Args``; ``wd = None`` for the block without a projection (``Cin == 64``,
@@ -221,7 +227,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
     "nmpc_dwa_step_lists_f32", "nmpc_dwa_step_lists_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
-    "nmpc_mmp_block2_f32", "nmpc_mmp_block3_f32", "nmpc_mmp_block3_f16", "nmpc_mmp_block4_f32", "nmpc_mmp_block4_f16", "nmpc_mmp_head_f32",
+    "nmpc_mmp_block2_f32", "nmpc_mmp_block2_f16", "nmpc_mmp_block3_f32", "nmpc_mmp_block3_f16", "nmpc_mmp_block4_f32", "nmpc_mmp_block4_f16", "nmpc_mmp_head_f32",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
     "nmpc_last_error",
 )
@@ -316,6 +322,7 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     lib.nmpc_mmp_stem_shape.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.nmpc_mmp_block_f32.argtypes = [vp, C.POINTER(NmpcMmpBlockArgs)]
     lib.nmpc_mmp_block2_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock2Args)]
+    lib.nmpc_mmp_block2_f16.argtypes = [vp, C.POINTER(NmpcMmpBlock2F16Args)]
     lib.nmpc_mmp_block3_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock3Args)]
     lib.nmpc_mmp_block3_f16.argtypes = [vp, C.POINTER(NmpcMmpBlock3F16Args)]
     lib.nmpc_mmp_block4_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock4Args)]
@@ -571,6 +578,11 @@ class Handle:
         """``nmpc_mmp_block3_f32``: one fused residual block of the network's layer3 (as ``mmp_block2``, at 64 output channels),
         ``out[M, 64, H2, W2]`` from ``x[M, Cin, H, W]``, float32 under both dtypes, one launch enqueued on the handle's stream."""
         _check(self._lib.nmpc_mmp_block3_f32(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_block2_f16(self, args: "NmpcMmpBlock2F16Args"):
+        """``nmpc_mmp_block2_f16``: the block of ``mmp_block2`` with binary16 MFMA operands and float32 accumulation (the rounding
+        rule: include/nmpc_hip.h), on the packed weights of ``mmp_stem.pack_block2_f16``; ``x`` and ``out`` stay float32."""
+        _check(self._lib.nmpc_mmp_block2_f16(self._h, C.byref(args) if args is not None else None))
 
     def mmp_block3_f16(self, args: "NmpcMmpBlock3F16Args"):
         """``nmpc_mmp_block3_f16``: the block of ``mmp_block3`` with binary16 MFMA operands and float32 accumulation (the rounding

@@ -30,6 +30,7 @@
 #include "nmpc_mmp_stem.h"
 #include "nmpc_mmp_block.h"
 #include "nmpc_mmp_block2.h"
+#include "nmpc_mmp_block2_f16.h"
 #include "nmpc_mmp_block3.h"
 #include "nmpc_mmp_block3_f16.h"
 #include "nmpc_mmp_block4.h"
@@ -1765,10 +1766,21 @@ struct MmpLayer2 {
     static constexpr int C = nmpc::kB2C, threads = nmpc::kB2Threads, packed_align = 0;
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk2_kernel<2, true>, nmpc::mmp_blk2_kernel<1, true>, nmpc::mmp_blk2_kernel<1, false>};
     // tiles of 8 x 44 = 352 outputs; reach 11
-    static void tile(Params& p, long long& ty, long long& tx)
+    template <typename P>
+    static void tile(P& p, long long& ty, long long& tx)
     {
         ty = ((long long)p.H2 + nmpc::kB2TH - 1) / nmpc::kB2TH, tx = ((long long)p.W2 + nmpc::kB2TW - 1) / nmpc::kB2TW;
     }
+};
+
+// layer2 with binary16 MFMA operands (csrc/nmpc_mmp_block2_f16.h): layer2's channels, threads and tiles; w1, w2 and wd are the
+// packed fragments, 16 bytes per lane, which is what packed_align adds to the checks
+struct MmpLayer2F16 : MmpLayer2 {
+    using Args = nmpc_mmp_block2_f16_args;
+    using Params = nmpc::MmpBlock2HParams;
+    static constexpr const char* name = "nmpc_mmp_block2_f16";
+    static constexpr int packed_align = 16;
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk2h_kernel<2, true>, nmpc::mmp_blk2h_kernel<1, true>, nmpc::mmp_blk2h_kernel<1, false>};
 };
 
 struct MmpLayer3 {
@@ -2424,6 +2436,7 @@ int nmpc_mmp_stem_f32(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_s
 int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<double>(h, a); }
 int nmpc_mmp_block_f32(nmpc_handle h, const nmpc_mmp_block_args* a) { return mmp_block(h, a); }
 int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return mmp_strided<MmpLayer2>(h, a); }
+int nmpc_mmp_block2_f16(nmpc_handle h, const nmpc_mmp_block2_f16_args* a) { return mmp_strided<MmpLayer2F16>(h, a); }
 int nmpc_mmp_block3_f32(nmpc_handle h, const nmpc_mmp_block3_args* a) { return mmp_strided<MmpLayer3>(h, a); }
 int nmpc_mmp_block3_f16(nmpc_handle h, const nmpc_mmp_block3_f16_args* a) { return mmp_strided<MmpLayer3F16>(h, a); }
 int nmpc_mmp_block4_f32(nmpc_handle h, const nmpc_mmp_block4_args* a) { return mmp_strided<MmpLayer4>(h, a); }

@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
-from .mmp_stem import STAGES, block2_plane, check_head, check_spec, check_stage, head_features, pack_block3_f16, pack_block4_f16
+from .mmp_stem import STAGES, block2_plane, check_head, check_spec, check_stage, head_features, pack_block2_f16, pack_block3_f16, pack_block4_f16
 
 _BLOCK_ARRAYS = ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
 _HEAD_ARRAYS = ("w1", "c1", "w2", "c2")
@@ -24,6 +24,9 @@ _DEVICE = ((_capi.NmpcMmpBlockArgs, "mmp_block"), (_capi.NmpcMmpBlock2Args, "mmp
 # ``half=``: the stages that have a kernel with binary16 MFMA operands -- how their checked specs are packed, the struct, the method
 _HALF = {"layer3": (pack_block3_f16, _capi.NmpcMmpBlock3F16Args, "mmp_block3_f16"),
          "layer4": (pack_block4_f16, _capi.NmpcMmpBlock4F16Args, "mmp_block4_f16")}
+# ``operands=``: every stage that has such a kernel -- ``half``'s, and layer2, which ``half`` refuses
+_F16 = {"layer2": (pack_block2_f16, _capi.NmpcMmpBlock2F16Args, "mmp_block2_f16"), **_HALF}
+_OPERANDS = ("f32", "f16")
 # what each keyword behind ``stem`` needs in front of it, as ``check_specs`` says it
 _NEEDS = (("the blocks run on the fused first layer's output",)
           + tuple(f"the blocks of {st.layer} run on the fused {prev.layer}'s output" for prev, st in zip(STAGES, STAGES[1:]))
@@ -35,7 +38,7 @@ class Stage:
 
     def __init__(self, name, channels, specs, cins, Args, launch, planes, reads_fill):
         self.name, self.channels = name, channels           # "layer1" ..; the output channels of its blocks
-        self.specs, self.cins = specs, cins                 # its specs with their arrays on the device (packed ones with ``half``); each block's Cin
+        self.specs, self.cins = specs, cins                 # its specs with their arrays on the device (packed ones on f16 operands); each block's Cin
         self.Args, self.launch = Args, launch               # the struct of its kernel, the Handle method that launches it
         self.planes = planes                                # the input plane of every block, then the last one's output
         self.buf_row = (channels,) + planes[1]              # a row of its two buffers (planes only shrink: the first output is the largest)
@@ -46,7 +49,8 @@ class Stage:
 
 class MmpFrontEnd:
     def __init__(self, handle: _capi.Handle, dtype, device, Hm: int, Wm: int, n_off: int, transform, rescale: float, sigma: float,
-                 ref_image, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=()):
+                 ref_image, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=(),
+                 operands=None):
         """``dtype``: the element type of ``hist``; ``ref_image``: the float32 label image ``[Hm, Wm]`` on ``device``; ``transform``: the
         :class:`.snap.WorldTransform` between map pixels and the world of ``hist``; ``stem``: a :class:`.mmp_stem.StemSpec`; ``blocks``
         .. ``blocks4``: the specs of ``layer1`` .. ``layer4`` (``mmp_stem.STAGES``), each needing the one before it; ``head`` (needs
@@ -58,6 +62,12 @@ class MmpFrontEnd:
         ``blocks4``; ``nmpc_mmp_block4_f16``, csrc/nmpc_mmp_block4_f16.h, the same rule), both, or ``()``; such a stage's
         record then carries the packed specs, that kernel's struct and its launch method, and nothing else differs: the buffers
         stay float32 where they were.
+        ``operands``: a mapping stage name -> ``"f32"`` or ``"f16"``, the general form of ``half`` (``half=("layer3",)`` means
+        ``operands={"layer3": "f16"}``; both may be given where they do not contradict each other). ``"f16"`` is accepted for
+        ``"layer2"`` (``nmpc_mmp_block2_f16``, csrc/nmpc_mmp_block2_f16.h, the same rule; ``half`` keeps refusing it), ``"layer3"``
+        and ``"layer4"``, each needing its blocks; ``"f32"`` for any stage. ``None``, ``{}`` or all ``"f32"`` changes no bit.
+        ``self.half`` is what ``check_half`` returned, ``self.operands`` what ``check_operands`` did: the operand type of every
+        stage given.
 
         Where a stage's two buffers lie is one rule: the fill's output (the stem's, ``[C, Hp, Wp]`` per row) is idle once layer1's
         first block has read it, so the buffers of the stages behind layer1 are laid INSIDE it one behind the other, at a running
@@ -68,6 +78,7 @@ class MmpFrontEnd:
         import torch
         specs = self.check_specs(stem, blocks, blocks2=blocks2, blocks3=blocks3, blocks4=blocks4, head=head)
         stem, head = specs[0], specs[-1]
+        self.operands = self.check_operands(operands, half, specs)
         self.half = self.check_half(half, specs)
         self.h, self.dt, self.dev, self.n_off = handle, np.dtype(dtype), device, int(n_off)
         bits = lambda a: a.view(np.int16) if a.dtype == np.uint16 else a          # (packed binary16 bit patterns travel as int16)
@@ -88,8 +99,8 @@ class MmpFrontEnd:
         self.row, self.bytes_per_item = self.fill_row, self.n_off * fill_size * 4
         self.stages, offset, inside = [], 0, True           # offset: floats of a fill row given away so far; inside: nothing overflowed yet
         for table, (Args, launch), given in zip(STAGES, _DEVICE, specs[1:-1]):
-            if given is not None and table.layer in self.half:
-                pack, Args, launch = _HALF[table.layer]
+            if given is not None and self.operands[table.layer] == "f16":
+                pack, Args, launch = _F16[table.layer]
                 cins, given = tuple(int(b.w1.shape[1]) for b in given), tuple(pack(b) for b in given)
             elif given is not None:
                 cins = tuple(int(b.w1.shape[1]) for b in given)
@@ -149,6 +160,27 @@ class MmpFrontEnd:
             if specs[1 + k] is None:
                 raise ValueError(f"{prefix}half: {name!r} needs {prefix}{STAGES[k].arg}")
         return tuple(dict.fromkeys(half))
+
+    @staticmethod
+    def check_operands(operands, half, specs, prefix: str = "") -> dict:
+        """The operand type, ``"f32"`` or ``"f16"``, of every stage whose specs were given, from ``operands`` (a mapping stage name
+        -> type, or ``None``) and ``half``, checked against the checked ``specs`` of ``check_specs`` (all six). ``half`` goes
+        through ``check_half`` first, so its refusals speak first and unchanged. ``"f32"`` for a stage whose blocks are not given
+        is accepted and names nothing."""
+        half = MmpFrontEnd.check_half(half, specs, prefix)
+        operands = {} if operands is None else dict(operands)
+        for name, value in operands.items():
+            k = next((i for i, st in enumerate(STAGES) if st.layer == name), None)
+            if value not in _OPERANDS:
+                raise ValueError(f"{prefix}operands: {name!r}: {value!r} is neither 'f32' nor 'f16'")
+            if k is None or (value == "f16" and name not in _F16):
+                raise ValueError(f"{prefix}operands: {name!r}: only layer2, layer3 and layer4 have an f16 kernel")
+            if value == "f16" and specs[1 + k] is None:
+                raise ValueError(f"{prefix}operands: {name!r} needs {prefix}{STAGES[k].arg}")
+            if value == "f32" and name in half:
+                raise ValueError(f"{prefix}operands: {name!r} is 'f32', but {prefix}half names it")
+        return {st.layer: "f16" if st.layer in half or operands.get(st.layer) == "f16" else "f32"
+                for k, st in enumerate(STAGES) if specs[1 + k] is not None}
 
     def stage(self, name: str):
         """The :class:`Stage` called ``name`` (``"layer1"`` ..), or ``None`` if its specs were not given."""

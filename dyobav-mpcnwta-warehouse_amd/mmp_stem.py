@@ -35,7 +35,10 @@ the four tuples of blocks and the head with NO trunk left, for ``BatchEvaluator(
 csrc/nmpc_mmp_block3_f16.h; ``half=("layer3",)`` in the callers): ``pack_block3_f16`` rounds a ``Block3Spec``'s weights once and packs
 them in the order the kernel's lanes load them, ``unpack_block3_f16`` inverts it, ``round_f16`` is the rounding. Layer4 has the
 same under the same rule (``nmpc_mmp_block4_f16``, csrc/nmpc_mmp_block4_f16.h; ``half=("layer4",)`` or ``("layer3", "layer4")``):
-``pack_block4_f16`` and ``unpack_block4_f16`` on a ``Block4Spec``, eight groups of sixteen output channels where layer3 has four."""
+``pack_block4_f16`` and ``unpack_block4_f16`` on a ``Block4Spec``, eight groups of sixteen output channels where layer3 has four.
+Layer2 has it too (``nmpc_mmp_block2_f16``, csrc/nmpc_mmp_block2_f16.h), selected by the callers' ``operands={"layer2": "f16"}`` --
+the mapping stage name -> ``"f32"`` or ``"f16"`` that generalises ``half=`` --: ``pack_block2_f16`` and ``unpack_block2_f16`` on a
+``Block2Spec``, two groups of sixteen output channels, one layout for both strides."""
 from __future__ import annotations
 
 from typing import Callable, NamedTuple, Optional, Tuple
@@ -411,7 +414,7 @@ def round_f16(a) -> np.ndarray:
 
 
 def _pack_f16(w) -> np.ndarray:
-    """``[C, Cin, T]`` -> ``[T, KB, C // 16, 64, 8]`` uint16 in fragment order (``C`` = 64 or 128 output channels: 4 or 8 groups)."""
+    """``[C, Cin, T]`` -> ``[T, KB, C // 16, 64, 8]`` uint16 in fragment order (``C`` = 32, 64 or 128 output channels: 2, 4 or 8 groups)."""
     C, Cin, T = w.shape
     KB = (Cin + 31) // 32
     wp = np.zeros((C, 32 * KB, T), dtype=np.float16)
@@ -465,6 +468,30 @@ def unpack_block4_f16(packed, Cin: int) -> Block4Spec:
     C = BLOCK4_CHANNELS
     wd = None if packed.wd is None else _unpack_f16(np.asarray(packed.wd)[None], Cin).reshape(C, Cin)
     return Block4Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
+                                       w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
+
+
+# Layer2 with binary16 MFMA operands (``nmpc_mmp_block2_f16``, csrc/nmpc_mmp_block2_f16.h): the same rule and the same order with
+# two groups of output channels: w1 [9, KB, 2, 64, 8], w2 [9, 1, 2, 64, 8] (Cin = 32), wd [KB, 2, 64, 8]; the rest is Block2Spec's.
+# The strided block's 16 input channels are half a K block, the other half packed zeros: one layout for both strides.
+Block2F16Spec = NamedTuple("Block2F16Spec", _STRIDED_FIELDS)
+
+
+def pack_block2_f16(spec) -> Block2F16Spec:
+    """A :class:`Block2Spec` -> :class:`Block2F16Spec`: the three weight arrays rounded once (``round_f16``) and packed; everything
+    else passed through. ``ValueError`` for what ``check_block2`` refuses."""
+    spec = check_block2(spec)
+    C, Cin = spec.w1.shape[:2]
+    wd = None if spec.wd is None else _pack_f16(spec.wd.reshape(C, Cin, 1))[0]
+    return Block2F16Spec(*spec._replace(w1=_pack_f16(spec.w1.reshape(C, Cin, 9)), w2=_pack_f16(spec.w2.reshape(C, C, 9)), wd=wd))
+
+
+def unpack_block2_f16(packed, Cin: int) -> Block2Spec:
+    """The inverse of ``pack_block2_f16`` for a block of ``Cin`` input channels: a :class:`Block2Spec` whose ``w1`` [32, Cin, 3, 3],
+    ``w2`` and ``wd`` [32, Cin] are the ROUNDED weights as ``np.float16``."""
+    C = BLOCK2_CHANNELS
+    wd = None if packed.wd is None else _unpack_f16(np.asarray(packed.wd)[None], Cin).reshape(C, Cin)
+    return Block2Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
                                        w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
 
 

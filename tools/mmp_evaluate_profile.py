@@ -48,9 +48,11 @@ three block launches and the head launch alone on that chunk, next to the model 
 ``--half-layer4``: the protocol of ``--half-layer3`` for layer4 on binary16 operands (``nmpc_mmp_block4_f16``). Both arms run layer3
 on binary16 operands, which this option does not touch: ``mmp_half=("layer3",)`` -- layer4 by the float32 launches -- against
 ``mmp_half=("layer3", "layer4")``, alternated in one process: the three launches alone on one chunk, then the closed loop.
+``--half-layer2``: the same protocol for layer2 on binary16 operands (``nmpc_mmp_block2_f16``), both arms with layer3 and layer4 on
+them: ``mmp_half=("layer3", "layer4")`` against the same with ``mmp_operands={"layer2": "f16"}``; the four launches alone, then the loop.
    usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]
           [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS] | --fused-layer4 [REPS] | --half-layer3 [REPS]
-           | --half-layer4 [REPS]]
+           | --half-layer4 [REPS] | --half-layer2 [REPS]]
           (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
@@ -350,11 +352,13 @@ def _strided_kernel_rate(fe, rows, reps, blocks, C, first, plane, run_all, cins=
 
 
 def block2_kernel_rate(ev, n_item, reps=10):
-    """The four nmpc_mmp_block2_f32 launches alone on the layer1 output of ``n_item`` pedestrians (``_strided_kernel_rate``)."""
+    """The four layer2 launches of the evaluator's front end (float32 or binary16 operands) alone on the layer1 output of ``n_item``
+    pedestrians (``_strided_kernel_rate``)."""
     fe = ev.mmp_front
     rows = _fill(ev, n_item)().shape[0]
     fe.run_blocks(rows)
-    return {"items": n_item, **_strided_kernel_rate(fe, rows, reps, fe.blocks2, 32, len(fe.blocks), fe.fill_row[1:], fe.run_blocks2)}
+    return {"items": n_item, **_strided_kernel_rate(fe, rows, reps, fe.blocks2, 32, len(fe.blocks), fe.fill_row[1:], fe.run_blocks2,
+                                                    cins=fe.stage("layer2").cins)}
 
 
 def torch_layer3_alone(ev, layer3, n_item, reps=5):
@@ -833,8 +837,91 @@ def half_layer4_main(out_path, B, steps, dt, n_ped, K, reps):
         print(p, json.dumps({"all": (r["ms_median"], r["TFMAps_median"], r["GBps_median"])}))
 
 
+def half_layer2_main(out_path, B, steps, dt, n_ped, K, reps):
+    """``--half-layer2``: the whole network on the device with ``mmp_half=("layer3", "layer4")`` (layer2 on float32 operands: the parent
+    arrangement) and with ``mmp_operands={"layer2": "f16"}`` on top (nmpc_mmp_block2_f16), alternated in one process: the four
+    launches alone on one chunk, then the closed loop with events around every part."""
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import split_network_whole
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    as_block = lambda b: SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)
+    L = list(net)
+    shaped = SimpleNamespace(resnet34=SimpleNamespace(stem=SimpleNamespace(conv1=L[0], pooling=L[1]), layer1=[as_block(b) for b in L[2:5]],
+                                                      layer2=[as_block(b) for b in L[5:9]], layer3=[as_block(b) for b in L[9:15]],
+                                                      layer4=[as_block(b) for b in L[15:18]], apool=L[18]), fc1=L[20], leaky=L[21], swarm=L[22])
+    spec, blocks, blocks2, blocks3, blocks4, head = split_network_whole(shaped)
+    head = head._replace(c2=head.c2 + np.float32(150.0))   # (the "+ 150" that puts the random network's hypotheses on the map)
+    whole = dict(network=None, mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, mmp_blocks3=blocks3, mmp_blocks4=blocks4, mmp_head=head,
+                 mmp_half=("layer3", "layer4"))
+    paths = {"fp32": dict(whole), "f16": dict(whole, mmp_operands={"layer2": "f16"})}
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rows_step = B * n_ped * nm.default_config_struct().N_hor
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage, the whole network on the device, layer3 "
+                   "and layer4 on binary16 operands in both arms: layer2 on float32 MFMA operands (nmpc_mmp_block2_f32, mmp_half = ('layer3', "
+                   "'layer4')) and on binary16 operands with float32 accumulation (nmpc_mmp_block2_f16, mmp_operands = {'layer2': 'f16'} on "
+                   "top), alternated in one process; random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS, "fp32_peak_TFMAps": PEAK_TFMAS},
+           "model_of_the_f16_header_per_lock_step_ms": {"mfma_pipe_never_waits": 2.7, "activations_at_copy_rate": 5.8},
+           "fp32_mfma_never_waits_floor_over_fp32_measured": 0.56, "chunk_pedestrians": {}, "block2_kernels": {p: [] for p in paths},
+           "runs": {p: [] for p in paths}}
+    for _ in range(reps):                                   # the four launches alone, three runs per arm, alternated (the first also warms up)
+        for path in paths:
+            ev = evaluator(path)
+            rec["chunk_pedestrians"][path] = ev.mmp_chunk
+            try:
+                rec["block2_kernels"][path].append(block2_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped)))
+                ev.run(max_steps=1)
+            finally:
+                ev.close()
+            r = rec["block2_kernels"][path][-1]
+            print(path, json.dumps({"rows": r["rows"], "four_launches_ms": r["ms_median"], "each": [b["ms_median"] for b in r["blocks"]]}), flush=True)
+            with open(out_path, "w") as f:
+                json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = ("input", "layer1", "layer2", "layer3", "layer4", "head")
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names}, stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    rec["stage_median_of_each_run_ms"] = {p: [float(np.median([s["stage_ms"] for s in run])) for run in rec["runs"][p]] for p in paths}
+    rec["layer2_median_of_each_run_ms"] = {p: [float(np.median([s["layer2"] for s in run])) for run in rec["runs"][p]] for p in paths}
+    rec["four_launches_of_each_run_ms"] = {p: [r["ms_median"] for r in rec["block2_kernels"][p]] for p in paths}
+    rec["four_launches_per_lock_step_ms"] = {p: float(np.median([r["ms_median"] * rows_step / r["rows"] for r in rec["block2_kernels"][p]])) for p in paths}
+    four, m = rec["four_launches_of_each_run_ms"], rec["median_per_lock_step_ms"]
+    rec["f16_over_fp32_four_launches"] = float(np.median(four["f16"]) / np.median(four["fp32"]))
+    rec["f16_over_fp32_stage"] = m["f16"]["stage"] / m["fp32"]["stage"]
+    rec["f16_four_launches_over_mfma_model"] = rec["four_launches_per_lock_step_ms"]["f16"] * (20480 / rows_step) / 2.7
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "stage_median_of_each_run_ms", "layer2_median_of_each_run_ms", "four_launches_of_each_run_ms",
+                                          "four_launches_per_lock_step_ms", "f16_over_fp32_four_launches", "f16_over_fp32_stage",
+                                          "f16_four_launches_over_mfma_model", "chunk_pedestrians")}))
+    for p in paths:
+        r = rec["block2_kernels"][p][-1]
+        print(p, json.dumps([(b["Cin"], b["stride"], b["ms_median"], b["TFMAps_median"], b["GBps_median"]) for b in r["blocks"]]))
+        print(p, json.dumps({"all": (r["ms_median"], r["TFMAps_median"], r["GBps_median"])}))
+
+
 def main():
-    for flag, run in (("--half-layer4", half_layer4_main), ("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+    for flag, run in (("--half-layer2", half_layer2_main), ("--half-layer4", half_layer4_main), ("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
         if flag in sys.argv:
             i = sys.argv.index(flag)
             reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
