@@ -1780,7 +1780,7 @@ struct MmpLayer2F16 : MmpLayer2 {
     using Params = nmpc::MmpBlock2HParams;
     static constexpr const char* name = "nmpc_mmp_block2_f16";
     static constexpr int packed_align = 16;
-    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk2h_kernel<2, true>, nmpc::mmp_blk2h_kernel<1, true>, nmpc::mmp_blk2h_kernel<1, false>};
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blkh_kernel<nmpc::MmpBlock2HGeom, 2, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock2HGeom, 1, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock2HGeom, 1, false>};
 };
 
 struct MmpLayer3 {
@@ -1804,7 +1804,7 @@ struct MmpLayer3F16 : MmpLayer3 {
     using Params = nmpc::MmpBlock3HParams;
     static constexpr const char* name = "nmpc_mmp_block3_f16";
     static constexpr int packed_align = 16;
-    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk3h_kernel<2, true>, nmpc::mmp_blk3h_kernel<1, true>, nmpc::mmp_blk3h_kernel<1, false>};
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blkh_kernel<nmpc::MmpBlock3HGeom, 2, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock3HGeom, 1, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock3HGeom, 1, false>};
 };
 
 struct MmpLayer4 {
@@ -1830,7 +1830,7 @@ struct MmpLayer4F16 : MmpLayer4 {
     using Params = nmpc::MmpBlock4HParams;
     static constexpr const char* name = "nmpc_mmp_block4_f16";
     static constexpr int threads = nmpc::kB4HThreads, packed_align = 16;
-    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk4h_kernel<2, true>, nmpc::mmp_blk4h_kernel<1, true>, nmpc::mmp_blk4h_kernel<1, false>};
+    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 2, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 1, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 1, false>};
 };
 
 template <typename Stage>

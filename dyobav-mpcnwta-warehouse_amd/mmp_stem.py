@@ -31,16 +31,16 @@ blocks2=blocks2, ...)``. The network's end -- ``AvgPool2d(2, 2)``, flatten,
 ``fc1 = Linear(F, 128)``, ``leaky``, ``swarm.layer_hypos = Linear(128, 2 K)`` -- is one launch (``nmpc_mmp_head_f32``,
 csrc/nmpc_mmp_head.h): ``HeadSpec(w1, c1, slope, w2, c2)`` from ``fold_head``, and ``split_network_whole(net)`` returns the stem,
 the four tuples of blocks and the head with NO trunk left, for ``BatchEvaluator(..., mmp_blocks4=blocks4, mmp_head=head)`` and
-``MmpInterface(None, ..., blocks4=blocks4, head=head)``. Layer3 also has a kernel on binary16 MFMA operands (``nmpc_mmp_block3_f16``,
-csrc/nmpc_mmp_block3_f16.h; ``half=("layer3",)`` in the callers): ``pack_block3_f16`` rounds a ``Block3Spec``'s weights once and packs
-them in the order the kernel's lanes load them, ``unpack_block3_f16`` inverts it, ``round_f16`` is the rounding. Layer4 has the
-same under the same rule (``nmpc_mmp_block4_f16``, csrc/nmpc_mmp_block4_f16.h; ``half=("layer4",)`` or ``("layer3", "layer4")``):
-``pack_block4_f16`` and ``unpack_block4_f16`` on a ``Block4Spec``, eight groups of sixteen output channels where layer3 has four.
-Layer2 has it too (``nmpc_mmp_block2_f16``, csrc/nmpc_mmp_block2_f16.h), selected by the callers' ``operands={"layer2": "f16"}`` --
-the mapping stage name -> ``"f32"`` or ``"f16"`` that generalises ``half=`` --: ``pack_block2_f16`` and ``unpack_block2_f16`` on a
-``Block2Spec``, two groups of sixteen output channels, one layout for both strides."""
+``MmpInterface(None, ..., blocks4=blocks4, head=head)``. Layer2, layer3 and layer4 also have
+a kernel on binary16 MFMA operands (``nmpc_mmp_block{2,3,4}_f16``, one kernel with a geometry per stage: csrc/nmpc_mmp_block_f16.h;
+``half=("layer3", "layer4")`` or, for all three, ``operands={"layer2": "f16", ...}`` in the callers, the mapping stage name ->
+``"f32"`` or ``"f16"`` that generalises ``half=``): ``pack_block_f16`` rounds a stage's spec's weights once and packs them in the order
+the kernel's lanes load them -- two, four or eight groups of sixteen output channels, one layout for both strides --,
+``unpack_block_f16`` inverts it, ``round_f16`` is the rounding; ``pack_block{2,3,4}_f16`` and ``unpack_block{2,3,4}_f16`` are the
+stages' names for them."""
 from __future__ import annotations
 
+import functools
 from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -398,12 +398,17 @@ def check_block4(spec) -> Block4Spec:
     return _check_strided(spec, BLOCK4_CHANNELS, Block4Spec)
 
 
-# Layer3 with binary16 MFMA operands (``nmpc_mmp_block3_f16``, csrc/nmpc_mmp_block3_f16.h): Block3Spec's fields with ``w1``, ``w2`` and
-# ``wd`` rounded to binary16 and packed in the order the kernel's lanes load them, as uint16 bit patterns:
-#   w1 [9, KB, 4, 64, 8]: [tap 3 ky + kx][K block kb][group g][lane l][j] = f16(w1[16 g + (l & 15), 32 kb + 8 (l >> 4) + j, ky, kx]),
-#   KB = ceil(Cin / 32), zero where the input channel is >= Cin; w2 the same with Cin = 64; wd [KB, 4, 64, 8] without the tap.
-# The scales, the shifts, the slopes and the stride are Block3Spec's, unchanged, in float32.
+# layer2, layer3 and layer4 with binary16 MFMA operands (``nmpc_mmp_block{2,3,4}_f16``, csrc/nmpc_mmp_block_f16.h): the stage's spec with
+# ``w1``, ``w2`` and ``wd`` rounded to binary16 and packed in the order the kernel's lanes load them, as uint16 bit patterns. With C
+# output channels (32, 64, 128: 2, 4, 8 groups of sixteen) and KB = ceil(Cin / 32):
+#   w1 [9, KB, C / 16, 64, 8]: [tap 3 ky + kx][K block kb][group g][lane l][j] = f16(w1[16 g + (l & 15), 32 kb + 8 (l >> 4) + j, ky, kx]),
+#   zero where the input channel is >= Cin; w2 the same with Cin = C; wd [KB, C / 16, 64, 8] without the tap.
+# Layer2's strided block has 16 input channels, half a K block, the other half packed zeros: one layout for both strides. The scales,
+# the shifts, the slopes and the stride are the float32 spec's, unchanged.
+Block2F16Spec = NamedTuple("Block2F16Spec", _STRIDED_FIELDS)
 Block3F16Spec = NamedTuple("Block3F16Spec", _STRIDED_FIELDS)
+Block4F16Spec = NamedTuple("Block4F16Spec", _STRIDED_FIELDS)
+_F16_SPECS = {BLOCK2_CHANNELS: Block2F16Spec, BLOCK3_CHANNELS: Block3F16Spec, BLOCK4_CHANNELS: Block4F16Spec}
 F16_MAX = 65504.0
 
 
@@ -430,69 +435,39 @@ def _unpack_f16(p, Cin: int) -> np.ndarray:
     return np.ascontiguousarray(w.reshape(16 * G, 32 * KB, T)[:, :Cin])
 
 
-def pack_block3_f16(spec) -> Block3F16Spec:
-    """A :class:`Block3Spec` -> :class:`Block3F16Spec`: the three weight arrays rounded once (``round_f16``) and packed; everything
-    else passed through. ``ValueError`` for what ``check_block3`` refuses."""
-    spec = check_block3(spec)
+def _f16_stage(channels: int) -> "Stage":
+    """The row of ``STAGES`` (below) whose blocks have ``channels`` output channels and an f16 kernel."""
+    for st in STAGES:
+        if st.channels == channels and channels in _F16_SPECS:
+            return st
+    raise ValueError(f"no f16 kernel for blocks of {channels} output channels")
+
+
+def pack_block_f16(spec, channels: Optional[int] = None):
+    """A stage's spec (:class:`Block2Spec`, :class:`Block3Spec`, :class:`Block4Spec`) -> its ``Block{2,3,4}F16Spec``: the three weight
+    arrays rounded once (``round_f16``) and packed; everything else passed through. The stage is the one of ``channels`` output
+    channels, by default the spec's own; ``ValueError`` for what that stage's checker refuses."""
+    st = _f16_stage(np.shape(spec.w1)[0] if channels is None else channels)
+    spec = st.check(spec)
     C, Cin = spec.w1.shape[:2]
     wd = None if spec.wd is None else _pack_f16(spec.wd.reshape(C, Cin, 1))[0]
-    return Block3F16Spec(*spec._replace(w1=_pack_f16(spec.w1.reshape(C, Cin, 9)), w2=_pack_f16(spec.w2.reshape(C, C, 9)), wd=wd))
+    return _F16_SPECS[C](*spec._replace(w1=_pack_f16(spec.w1.reshape(C, Cin, 9)), w2=_pack_f16(spec.w2.reshape(C, C, 9)), wd=wd))
 
 
-def unpack_block3_f16(packed, Cin: int) -> Block3Spec:
-    """The inverse of ``pack_block3_f16`` for a block of ``Cin`` input channels: a :class:`Block3Spec` whose ``w1`` [64, Cin, 3, 3],
-    ``w2`` and ``wd`` [64, Cin] are the ROUNDED weights as ``np.float16``."""
-    C = BLOCK3_CHANNELS
+def unpack_block_f16(packed, Cin: int):
+    """The inverse of ``pack_block_f16`` for a block of ``Cin`` input channels: the stage's float32 spec type whose ``w1``
+    [C, Cin, 3, 3], ``w2`` and ``wd`` [C, Cin] are the ROUNDED weights as ``np.float16``."""
+    C = 16 * np.shape(packed.w2)[2]
     wd = None if packed.wd is None else _unpack_f16(np.asarray(packed.wd)[None], Cin).reshape(C, Cin)
-    return Block3Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
-                                       w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
+    return _f16_stage(C).Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
+                                               w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
 
 
-# Layer4 with binary16 MFMA operands (``nmpc_mmp_block4_f16``, csrc/nmpc_mmp_block4_f16.h): the same rule and the same order with
-# eight groups of output channels: w1 [9, KB, 8, 64, 8], w2 [9, 4, 8, 64, 8] (Cin = 128), wd [KB, 8, 64, 8]; the rest is Block4Spec's.
-Block4F16Spec = NamedTuple("Block4F16Spec", _STRIDED_FIELDS)
-
-
-def pack_block4_f16(spec) -> Block4F16Spec:
-    """A :class:`Block4Spec` -> :class:`Block4F16Spec`: the three weight arrays rounded once (``round_f16``) and packed; everything
-    else passed through. ``ValueError`` for what ``check_block4`` refuses."""
-    spec = check_block4(spec)
-    C, Cin = spec.w1.shape[:2]
-    wd = None if spec.wd is None else _pack_f16(spec.wd.reshape(C, Cin, 1))[0]
-    return Block4F16Spec(*spec._replace(w1=_pack_f16(spec.w1.reshape(C, Cin, 9)), w2=_pack_f16(spec.w2.reshape(C, C, 9)), wd=wd))
-
-
-def unpack_block4_f16(packed, Cin: int) -> Block4Spec:
-    """The inverse of ``pack_block4_f16`` for a block of ``Cin`` input channels: a :class:`Block4Spec` whose ``w1`` [128, Cin, 3, 3],
-    ``w2`` and ``wd`` [128, Cin] are the ROUNDED weights as ``np.float16``."""
-    C = BLOCK4_CHANNELS
-    wd = None if packed.wd is None else _unpack_f16(np.asarray(packed.wd)[None], Cin).reshape(C, Cin)
-    return Block4Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
-                                       w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
-
-
-# Layer2 with binary16 MFMA operands (``nmpc_mmp_block2_f16``, csrc/nmpc_mmp_block2_f16.h): the same rule and the same order with
-# two groups of output channels: w1 [9, KB, 2, 64, 8], w2 [9, 1, 2, 64, 8] (Cin = 32), wd [KB, 2, 64, 8]; the rest is Block2Spec's.
-# The strided block's 16 input channels are half a K block, the other half packed zeros: one layout for both strides.
-Block2F16Spec = NamedTuple("Block2F16Spec", _STRIDED_FIELDS)
-
-
-def pack_block2_f16(spec) -> Block2F16Spec:
-    """A :class:`Block2Spec` -> :class:`Block2F16Spec`: the three weight arrays rounded once (``round_f16``) and packed; everything
-    else passed through. ``ValueError`` for what ``check_block2`` refuses."""
-    spec = check_block2(spec)
-    C, Cin = spec.w1.shape[:2]
-    wd = None if spec.wd is None else _pack_f16(spec.wd.reshape(C, Cin, 1))[0]
-    return Block2F16Spec(*spec._replace(w1=_pack_f16(spec.w1.reshape(C, Cin, 9)), w2=_pack_f16(spec.w2.reshape(C, C, 9)), wd=wd))
-
-
-def unpack_block2_f16(packed, Cin: int) -> Block2Spec:
-    """The inverse of ``pack_block2_f16`` for a block of ``Cin`` input channels: a :class:`Block2Spec` whose ``w1`` [32, Cin, 3, 3],
-    ``w2`` and ``wd`` [32, Cin] are the ROUNDED weights as ``np.float16``."""
-    C = BLOCK2_CHANNELS
-    wd = None if packed.wd is None else _unpack_f16(np.asarray(packed.wd)[None], Cin).reshape(C, Cin)
-    return Block2Spec(*packed._replace(w1=_unpack_f16(np.asarray(packed.w1), Cin).reshape(C, Cin, 3, 3),
-                                       w2=_unpack_f16(np.asarray(packed.w2), C).reshape(C, C, 3, 3), wd=wd))
+# the stages' own names (INTEGRATION.md): a spec of another stage is refused by this stage's checker, in its words
+pack_block2_f16 = functools.partial(pack_block_f16, channels=BLOCK2_CHANNELS)
+pack_block3_f16 = functools.partial(pack_block_f16, channels=BLOCK3_CHANNELS)
+pack_block4_f16 = functools.partial(pack_block_f16, channels=BLOCK4_CHANNELS)
+unpack_block2_f16 = unpack_block3_f16 = unpack_block4_f16 = unpack_block_f16
 
 
 def _linear(fn, name, layer, n_in, n_out):

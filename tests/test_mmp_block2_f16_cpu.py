@@ -141,16 +141,18 @@ def test_kernels_use_no_scratch_and_fit_the_occupancy_the_header_states():
         sys.path.remove(os.path.join(ROOT, "tools"))
     nm.build_library()
     res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
-    mine = {k: v for k, v in res.items() if re.search(r"mmp_blk2h_kernel", k)}
+    mine = {k: v for k, v in res.items() if re.search(r"mmp_blkh_kernel<nmpc::MmpBlock2HGeom, ", k)}
     assert len(mine) == 3, sorted(mine)
     assert not any(re.search(r"mmp_blk2_kernel", k) for k in mine)                 # the f32 family's pattern does not take these in
     header = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block2_f16.h")).read()
-    assert "__launch_bounds__(kB2Threads, STRIDE == 2 ? 2 : 4)" in header
+    assert "Threads = kB2Threads" in header and "min_wg(int stride) { return stride == 2 ? 2 : 4; }" in header   # the geometry's figures ...
+    shared = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block_f16.h")).read()
+    assert "__launch_bounds__(G::Threads, G::min_wg(STRIDE))" in shared   # ... are the one kernel's launch bound
     for name, r in mine.items():
         print(name, r)
-        claimed = 2 if "<2" in name else 4                                         # workgroups per CU = waves per SIMD (four waves, four SIMDs)
+        claimed = 2 if "Geom, 2," in name else 4                                         # workgroups per CU = waves per SIMD (four waves, four SIMDs)
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0, (name, r)
-        assert r["lds_static"] == (8 if "<2" in name else 4) * 592 * 16, (name, r)
+        assert r["lds_static"] == (8 if "Geom, 2," in name else 4) * 592 * 16, (name, r)
         assert (160 * 1024) // r["lds_static"] == claimed, (name, r)
         regs = r["vgpr"] + max(r["agpr"], 0)
         assert 512 // (-(-regs // 8) * 8) >= claimed, (name, r)                     # the registers hold as many waves per SIMD

@@ -127,13 +127,15 @@ def test_kernels_use_no_scratch_and_fit_the_occupancy_the_header_states():
         sys.path.remove(os.path.join(ROOT, "tools"))
     nm.build_library()
     res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
-    mine = {k: v for k, v in res.items() if re.search(r"mmp_blk3h_kernel", k)}
+    mine = {k: v for k, v in res.items() if re.search(r"mmp_blkh_kernel<nmpc::MmpBlock3HGeom, ", k)}
     assert len(mine) == 3, sorted(mine)
     header = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block3_f16.h")).read()
-    assert "__launch_bounds__(kB3Threads, STRIDE == 2 ? 2 : 4)" in header
+    assert "Threads = kB3Threads" in header and "min_wg(int stride) { return stride == 2 ? 2 : 4; }" in header   # the geometry's figures ...
+    shared = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block_f16.h")).read()
+    assert "__launch_bounds__(G::Threads, G::min_wg(STRIDE))" in shared   # ... are the one kernel's launch bound
     for name, r in mine.items():
         print(name, r)
-        strided = "<2" in name
+        strided = "Geom, 2," in name
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0, (name, r)
         assert r["lds_static"] == (73728 if strided else 36864), (name, r)
         assert r["vgpr"] + max(r["agpr"], 0) <= (256 if strided else 128), (name, r)

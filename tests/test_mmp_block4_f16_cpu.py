@@ -128,11 +128,13 @@ def test_kernels_use_no_scratch_and_fit_the_occupancy_the_header_states():
         sys.path.remove(os.path.join(ROOT, "tools"))
     nm.build_library()
     res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
-    mine = {k: v for k, v in res.items() if re.search(r"mmp_blk4h_kernel", k)}
+    mine = {k: v for k, v in res.items() if re.search(r"mmp_blkh_kernel<nmpc::MmpBlock4HGeom, ", k)}
     assert len(mine) == 3, sorted(mine)
     assert not any(re.search(r"mmp_blk4_kernel", k) for k in mine)                 # the f32 family's pattern does not take these in
     header = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block4_f16.h")).read()
-    assert "__launch_bounds__(kB4HThreads, 3)" in header and "kB4HThreads = 256" in header
+    assert "Threads = kB4HThreads" in header and "min_wg(int) { return 3; }" in header and "kB4HThreads = 256" in header   # the geometry's figures ...
+    shared = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block_f16.h")).read()
+    assert "__launch_bounds__(G::Threads, G::min_wg(STRIDE))" in shared   # ... are the one kernel's launch bound
     for name, r in mine.items():
         print(name, r)
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0, (name, r)

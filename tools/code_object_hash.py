@@ -1,10 +1,12 @@
 """sha256 of the .text / .rodata sections of the gfx950 code object inside one or more builds of libnmpc_hip.so.
 
-    python tools/code_object_hash.py [lib.so ...]          (default: the in-tree library)
+    python tools/code_object_hash.py [--renamed 'PATTERN=REPLACEMENT' ...] [lib.so ...]          (default: the in-tree library)
 
 Two builds whose hashes agree run the same device code: the check behind "moved out of the product headers without
 changing a single instruction" (profiles/r06_hygiene_code_object_identity.txt) and behind any A/B claim of "same bits".
-Host-side changes (layout bookkeeping, the C ABI) do not show up here by construction.
+Host-side changes (layout bookkeeping, the C ABI) do not show up here by construction. A kernel that one build has under another
+name is compared too where ``--renamed`` says so: PATTERN is a regular expression on the demangled names of the first build,
+REPLACEMENT (``re.sub`` syntax) gives the name in the second.
 """
 import hashlib
 import os
@@ -58,7 +60,12 @@ def demangle(names):
 
 
 if __name__ == "__main__":
-    libs = sys.argv[1:] or [DEFAULT_LIB]
+    args, renamed = sys.argv[1:], []
+    while "--renamed" in args:
+        k = args.index("--renamed")
+        renamed.append(args[k + 1].split("=", 1))
+        del args[k:k + 2]
+    libs = args or [DEFAULT_LIB]
     seen = []
     for lib in libs:
         h = code_object_hashes(lib)
@@ -74,6 +81,14 @@ if __name__ == "__main__":
         diff = sorted(k for k in a if k in b and a[k] != b[k])
         only = sorted(set(a) ^ set(b))
         print(f"kernels byte-identical: {len(same)} of {len(set(a) | set(b))}")
+        new_name = dict(zip(demangle(sorted(b)), sorted(b)))
+        for k, d in zip(list(only), demangle(only)):                       # renamed kernels: compared under both names
+            to = [re.sub(pat, rep, d) for pat, rep in renamed if k in a and re.search(pat, d)]
+            if to and new_name.get(to[0]) in only:
+                k2 = new_name[to[0]]
+                verdict = "byte-identical" if a[k] == b[k2] else f"differs ({a[k][0]} B -> {b[k2][0]} B)"
+                print(f"  renamed, {verdict}: {d} -> {to[0]}  ({a[k][0]} B, sha256 {a[k][1][:16]} / {b[k2][1][:16]})")
+                only.remove(k), only.remove(k2)
         for k, d in zip(diff, demangle(diff)):
             print(f"  differs: {d}  ({a[k][0]} B -> {b[k][0]} B)")
         for k, d in zip(only, demangle(only)):
