@@ -228,6 +228,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_dwa_step_lists_f32", "nmpc_dwa_step_lists_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
     "nmpc_mmp_block2_f32", "nmpc_mmp_block2_f16", "nmpc_mmp_block3_f32", "nmpc_mmp_block3_f16", "nmpc_mmp_block4_f32", "nmpc_mmp_block4_f16", "nmpc_mmp_head_f32",
+    "nmpc_mmp_block2_f16_io", "nmpc_mmp_block3_f16_io", "nmpc_mmp_block4_f16_io",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
     "nmpc_last_error",
 )
@@ -327,6 +328,9 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     lib.nmpc_mmp_block3_f16.argtypes = [vp, C.POINTER(NmpcMmpBlock3F16Args)]
     lib.nmpc_mmp_block4_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock4Args)]
     lib.nmpc_mmp_block4_f16.argtypes = [vp, C.POINTER(NmpcMmpBlock4F16Args)]
+    lib.nmpc_mmp_block2_f16_io.argtypes = [vp, C.POINTER(NmpcMmpBlock2F16Args), i32, i32]
+    lib.nmpc_mmp_block3_f16_io.argtypes = [vp, C.POINTER(NmpcMmpBlock3F16Args), i32, i32]
+    lib.nmpc_mmp_block4_f16_io.argtypes = [vp, C.POINTER(NmpcMmpBlock4F16Args), i32, i32]
     lib.nmpc_mmp_head_f32.argtypes = [vp, C.POINTER(NmpcMmpHeadArgs)]
     lib.nmpc_solve_trace_f64.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     lib.nmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -593,6 +597,20 @@ class Handle:
         """``nmpc_mmp_block4_f16``: the block of ``mmp_block4`` with binary16 MFMA operands and float32 accumulation (the rounding
         rule: include/nmpc_hip.h), on the packed weights of ``mmp_stem.pack_block4_f16``; ``x`` and ``out`` stay float32."""
         _check(self._lib.nmpc_mmp_block4_f16(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_block2_f16_io(self, args: "NmpcMmpBlock2F16Args", x_f16: int, out_f16: int):
+        """``nmpc_mmp_block2_f16_io``: ``mmp_block2_f16`` with ``args.x`` (``x_f16 = 1``) and / or ``args.out`` (``out_f16 = 1``) in the
+        octet form of binary16 activations, ``[M][C / 8][H][W][8]`` (include/nmpc_hip.h; ``mmp_stem.pack_activations_f16``), aligned to
+        16 bytes; ``(0, 0)`` is ``mmp_block2_f16``."""
+        _check(self._lib.nmpc_mmp_block2_f16_io(self._h, C.byref(args) if args is not None else None, x_f16, out_f16))
+
+    def mmp_block3_f16_io(self, args: "NmpcMmpBlock3F16Args", x_f16: int, out_f16: int):
+        """``nmpc_mmp_block3_f16_io``: as ``mmp_block2_f16_io``, for ``mmp_block3_f16``."""
+        _check(self._lib.nmpc_mmp_block3_f16_io(self._h, C.byref(args) if args is not None else None, x_f16, out_f16))
+
+    def mmp_block4_f16_io(self, args: "NmpcMmpBlock4F16Args", x_f16: int, out_f16: int):
+        """``nmpc_mmp_block4_f16_io``: as ``mmp_block2_f16_io``, for ``mmp_block4_f16``."""
+        _check(self._lib.nmpc_mmp_block4_f16_io(self._h, C.byref(args) if args is not None else None, x_f16, out_f16))
 
     def mmp_block4(self, args: "NmpcMmpBlock4Args"):
         """``nmpc_mmp_block4_f32``: one fused residual block of the network's layer4 (as ``mmp_block3``, at 128 output channels),

@@ -1755,10 +1755,23 @@ int mmp_block(nmpc_handle_s* h, const nmpc_mmp_block_args* g)
 // The three strided stages (layer2 .. layer4) behind one entry, mmp_strided<Stage>. A Stage says what differs: the name in the
 // messages, the structs, the output channels C, the threads of a workgroup, how the plane of outputs H2 x W2 is cut into ty x tx
 // tiles, the alignment of packed weights (0: plain float arrays), and the kernels <stride 2, projection>, <stride 1, projection>,
-// <stride 1, identity>. Two numbers of the entry follow from
+// <stride 1, identity>; a stage on binary16 operands has an Io beside them: the same three kernels for each other form of x and
+// out in memory (MmpBlkhIoKernels below; nmpc_mmp_blockN_f16_io). Two numbers of the entry follow from
 // a stage's tile: the kernels' pixel coordinates are ints and reach 2 (tile origin + reach) + 1, which must not wrap -- hence no
 // plane over 2^30 --, and once the workgroup count has passed H2 W2 M <= (outputs of a tile) x 2^31, with H W <= 4 H2 W2: the byte
 // counts of the overlap test do not overflow.
+// The kernels of a geometry G on the octet form of binary16 activations (csrc/nmpc_mmp_block_f16.h): table[2 x_f16 + out_f16 - 1]
+// holds <stride 2, projection>, <stride 1, projection>, <stride 1, identity>, as a stage's kernels[] does for float32 memory
+template <typename G>
+struct MmpBlkhIoKernels {
+    template <bool XH, bool OH>
+    using Io = nmpc::MmpBlkhIo<G, XH, OH>;
+    static constexpr void (*table[3][3])(typename G::Params) = {
+        {nmpc::mmp_blkh_kernel<Io<false, true>, 2, true>, nmpc::mmp_blkh_kernel<Io<false, true>, 1, true>, nmpc::mmp_blkh_kernel<Io<false, true>, 1, false>},
+        {nmpc::mmp_blkh_kernel<Io<true, false>, 2, true>, nmpc::mmp_blkh_kernel<Io<true, false>, 1, true>, nmpc::mmp_blkh_kernel<Io<true, false>, 1, false>},
+        {nmpc::mmp_blkh_kernel<Io<true, true>, 2, true>, nmpc::mmp_blkh_kernel<Io<true, true>, 1, true>, nmpc::mmp_blkh_kernel<Io<true, true>, 1, false>}};
+};
+
 struct MmpLayer2 {
     using Args = nmpc_mmp_block2_args;
     using Params = nmpc::MmpBlock2Params;
@@ -1778,7 +1791,9 @@ struct MmpLayer2 {
 struct MmpLayer2F16 : MmpLayer2 {
     using Args = nmpc_mmp_block2_f16_args;
     using Params = nmpc::MmpBlock2HParams;
+    using Io = MmpBlkhIoKernels<nmpc::MmpBlock2HGeom>;
     static constexpr const char* name = "nmpc_mmp_block2_f16";
+    static constexpr const char* io_name = "nmpc_mmp_block2_f16_io";
     static constexpr int packed_align = 16;
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blkh_kernel<nmpc::MmpBlock2HGeom, 2, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock2HGeom, 1, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock2HGeom, 1, false>};
 };
@@ -1802,7 +1817,9 @@ struct MmpLayer3 {
 struct MmpLayer3F16 : MmpLayer3 {
     using Args = nmpc_mmp_block3_f16_args;
     using Params = nmpc::MmpBlock3HParams;
+    using Io = MmpBlkhIoKernels<nmpc::MmpBlock3HGeom>;
     static constexpr const char* name = "nmpc_mmp_block3_f16";
+    static constexpr const char* io_name = "nmpc_mmp_block3_f16_io";
     static constexpr int packed_align = 16;
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blkh_kernel<nmpc::MmpBlock3HGeom, 2, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock3HGeom, 1, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock3HGeom, 1, false>};
 };
@@ -1828,16 +1845,22 @@ struct MmpLayer4 {
 struct MmpLayer4F16 : MmpLayer4 {
     using Args = nmpc_mmp_block4_f16_args;
     using Params = nmpc::MmpBlock4HParams;
+    using Io = MmpBlkhIoKernels<nmpc::MmpBlock4HGeom>;
     static constexpr const char* name = "nmpc_mmp_block4_f16";
+    static constexpr const char* io_name = "nmpc_mmp_block4_f16_io";
     static constexpr int threads = nmpc::kB4HThreads, packed_align = 16;
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 2, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 1, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 1, false>};
 };
 
-template <typename Stage>
-int mmp_strided(nmpc_handle_s* h, const typename Stage::Args* g)
+// IO: the entry nmpc_mmp_blockN_f16_io, whose x (x_f16 = 1) and out (out_f16 = 1) are binary16 in the octet form
+template <typename Stage, bool IO = false>
+int mmp_strided(nmpc_handle_s* h, const typename Stage::Args* g, int32_t x_f16 = 0, int32_t out_f16 = 0)
 {
     const char* fn = Stage::name;
+    if constexpr (IO) fn = Stage::io_name;
     if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if ((x_f16 != 0 && x_f16 != 1) || (out_f16 != 0 && out_f16 != 1))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: x_f16 = %d, out_f16 = %d (each is 0 or 1)", fn, x_f16, out_f16);
     if (g->M < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: M = %d < 0", fn, g->M);
     if (g->H < 1 || g->W < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: plane %d x %d", fn, g->H, g->W);
     if (g->stride != 1 && g->stride != 2) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: stride = %d is neither 1 nor 2", fn, g->stride);
@@ -1852,6 +1875,8 @@ int mmp_strided(nmpc_handle_s* h, const typename Stage::Args* g)
         return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: a required array is NULL", fn);
     if (reinterpret_cast<uintptr_t>(g->out) % 4 || reinterpret_cast<uintptr_t>(g->x) % 4)
         return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: x or out is not aligned to float", fn);
+    if ((x_f16 && reinterpret_cast<uintptr_t>(g->x) % 16) || (out_f16 && reinterpret_cast<uintptr_t>(g->out) % 16)) // (an octet is one 16-byte access)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: a binary16 x or out is not aligned to 16 bytes", fn);
     if constexpr (Stage::packed_align != 0) { // (the stages with packed weights: each lane loads a whole fragment)
         const void* packed[] = {g->w1, g->w2, g->wd};
         for (const void* q : packed)
@@ -1870,7 +1895,9 @@ int mmp_strided(nmpc_handle_s* h, const typename Stage::Args* g)
     const long long groups = tiles * g->M;
     p.ty = (int)ty, p.tx = (int)tx;
     // out must not overlap x: a tile's halo is read after the neighbouring tiles have been written
-    const unsigned long long xb = (unsigned long long)g->H * g->W * g->M * 4 * g->Cin, ob = (unsigned long long)p.H2 * p.W2 * g->M * 4 * Stage::C;
+    // (2 bytes per element on a binary16 side)
+    const unsigned long long xb = (unsigned long long)g->H * g->W * g->M * (x_f16 ? 2 : 4) * g->Cin;
+    const unsigned long long ob = (unsigned long long)p.H2 * p.W2 * g->M * (out_f16 ? 2 : 4) * Stage::C;
     const uintptr_t x0 = reinterpret_cast<uintptr_t>(g->x), o0 = reinterpret_cast<uintptr_t>(g->out);
     if (x0 < o0 + ob && o0 < x0 + xb) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: out overlaps x", fn);
     HIP_TRY(hipSetDevice(h->cfg.device_id));
@@ -1883,7 +1910,12 @@ int mmp_strided(nmpc_handle_s* h, const typename Stage::Args* g)
     p.M = g->M, p.Cin = g->Cin, p.H = g->H, p.W = g->W;
     p.x = g->x, p.w1 = g->w1, p.s1 = g->s1, p.b1 = g->b1, p.w2 = g->w2, p.s2 = g->s2, p.b2 = g->b2;
     p.wd = g->wd, p.sd = g->sd, p.bd = g->bd, p.slope_mid = g->slope_mid, p.slope_out = g->slope_out, p.out = g->out;
-    hipLaunchKernelGGL(Stage::kernels[g->stride == 2 ? 0 : g->wd ? 1 : 2], dim3((unsigned)groups), dim3(Stage::threads), 0, h->stream, p);
+    const int variant = g->stride == 2 ? 0 : g->wd ? 1 : 2;
+    auto kernel = Stage::kernels[variant];
+    if constexpr (IO) {
+        if (x_f16 || out_f16) kernel = Stage::Io::table[2 * x_f16 + out_f16 - 1][variant]; // (p.x / p.out point at binary16: the kernel casts them)
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(Stage::threads), 0, h->stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2437,10 +2469,13 @@ int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_s
 int nmpc_mmp_block_f32(nmpc_handle h, const nmpc_mmp_block_args* a) { return mmp_block(h, a); }
 int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return mmp_strided<MmpLayer2>(h, a); }
 int nmpc_mmp_block2_f16(nmpc_handle h, const nmpc_mmp_block2_f16_args* a) { return mmp_strided<MmpLayer2F16>(h, a); }
+int nmpc_mmp_block2_f16_io(nmpc_handle h, const nmpc_mmp_block2_f16_args* a, int32_t x_f16, int32_t out_f16) { return mmp_strided<MmpLayer2F16, true>(h, a, x_f16, out_f16); }
 int nmpc_mmp_block3_f32(nmpc_handle h, const nmpc_mmp_block3_args* a) { return mmp_strided<MmpLayer3>(h, a); }
 int nmpc_mmp_block3_f16(nmpc_handle h, const nmpc_mmp_block3_f16_args* a) { return mmp_strided<MmpLayer3F16>(h, a); }
+int nmpc_mmp_block3_f16_io(nmpc_handle h, const nmpc_mmp_block3_f16_args* a, int32_t x_f16, int32_t out_f16) { return mmp_strided<MmpLayer3F16, true>(h, a, x_f16, out_f16); }
 int nmpc_mmp_block4_f32(nmpc_handle h, const nmpc_mmp_block4_args* a) { return mmp_strided<MmpLayer4>(h, a); }
 int nmpc_mmp_block4_f16(nmpc_handle h, const nmpc_mmp_block4_f16_args* a) { return mmp_strided<MmpLayer4F16>(h, a); }
+int nmpc_mmp_block4_f16_io(nmpc_handle h, const nmpc_mmp_block4_f16_args* a, int32_t x_f16, int32_t out_f16) { return mmp_strided<MmpLayer4F16, true>(h, a, x_f16, out_f16); }
 int nmpc_mmp_head_f32(nmpc_handle h, const nmpc_mmp_head_args* a) { return mmp_head(h, a); }
 int nmpc_mmp_stem_shape(int32_t Hm, int32_t Wm, int32_t* Hp, int32_t* Wp)
 {

@@ -59,8 +59,9 @@
 // what waits is, from the code and not from counters (no counter run was made), the staging loads in front of the first barrier
 // and the stores behind the last MFMA, as expected. The strided block runs at half the others' rate: 144 loads per thread (18
 // octets, two floats apart along x), two workgroups per CU to cover them where the others have four, and its projection's 8
-// loads per pixel group in the epilogue. Not built: tap pairing (decision 4), a register prefetch of the next tile, f16
-// activations in memory.
+// loads per pixel group in the epilogue. Not built: tap pairing (decision 4), a register prefetch of the next tile. Built since:
+// binary16 activations in memory (nmpc_mmp_block_f16.h, MmpBlkhIo): the 32 -> 32 blocks 0.105-0.107 -> 0.069-0.070 ms, the strided
+// block, whose x stays layer1's float32 output, 0.193 -> 0.175 ms (profiles/mmp_f16_activations_evaluate.json).
 //
 // Compiler (hipcc -O3 --offload-arch=gfx950; tools/kernel_resources.py on the shipped code object): mmp_blkh_kernel<MmpBlock2HGeom, 2, true>
 // 126 VGPRs, 80 SGPRs, 75 776 B LDS; <1, true> 126 VGPRs, 80 SGPRs, 37 888 B; <1, false> 122 VGPRs, 70 SGPRs, 37 888 B; 0 AGPRs, no

@@ -5,7 +5,7 @@
 // channels), nmpc_mmp_block3_f16.h (64) and nmpc_mmp_block4_f16.h (128) hold one each, with the stage's Params, its decisions, its
 // model and its measured figures; the block itself, its strides, its padding and the zero ring of m are defined by the float32
 // siblings nmpc_mmp_block{2,3,4}.h, whose flat domains and pixel groups the geometries take over. x [M][Cin][H][W] and out
-// [M][C][H2][W2] stay float32 in memory.
+// [M][C][H2][W2] stay float32 in memory, unless the launch says otherwise (binary16 activations in memory, below).
 //
 // The rounding rule -- whatever an MFMA reads is f16, nothing else is:
 //   - the weights w1, w2, wd are rounded ONCE on the host (mmp_stem.pack_block_f16) and arrive packed in fragment order (below);
@@ -17,6 +17,8 @@
 //     the gfx950 MFMA does not flush them: tests/test_gpu_mmp_block{2,3,4}_f16.py pin that on the device);
 //   - float32, as in the siblings: the accumulation (the MFMA's), the two affines and both LeakyReLUs, the addition z + id, x as
 //     the identity when there is no projection (read again UNROUNDED), x and out in memory.
+//   - the tensor between two blocks is binary16 where both blocks say so (XH / OH below): the identity of a block without
+//     projection is then that binary16 value, and out is rounded once, after the last LeakyReLU.
 // tests/mmp_block_f16_reference.py states the same rule in float64 with a derived bound.
 //
 // Instruction: v_mfma_f32_16x16x32_f16, K = 32 per instruction against the float32 kernels' 4 at half its cycles (16 against 32
@@ -55,6 +57,45 @@
 // instruction's own order over its 32 channels; then one fma per affine and one addition. A row's bits depend on that row of x
 // and the weights only: not on M, the row's position, the launch or the alignment of out.
 //
+// Binary16 activations in memory (opt-in per tensor: MmpFrontEnd(activations="f16"), nmpc_mmp_block{2,3,4}_f16_io): a tensor of
+// C channels (C % 8 == 0) on an H x W plane in the OCTET FORM a[n][o = c / 8][y][x][j = c % 8], uint16_t bit patterns, row n
+// n C H W halves in, the base aligned to 16 bytes; the values are mmp_blkh_round's. It is the LDS layout's own slot, and half of
+// it is a D fragment, so with XH (x is in that form) a staging item is ONE 16-byte load without conversion (zeros outside the
+// plane or for octets >= Cin / 8), the projection's B fragment one 16-byte load of octet 4 kb + k4 at the pixel, the identity one
+// 8-byte load of channels 16 (hb + h) + 4 k4 .. + 3, converted to float; with OH (out is in that form) the epilogue packs the
+// four values of a D fragment with mmp_blkh_round into one 8-byte store at octet 2 (hb + h) + (k4 >> 1), half k4 & 1. The sixteen
+// lanes l & 15 of a fragment touch 256 consecutive bytes either way. Fragments, LDS layout, chunking, barriers, m, the ring and
+// the summation order do not depend on the two flags: on x that holds binary16 values the bits of a float32 out are those of the
+// float32 form, and a binary16 out is mmp_blkh_round of them (tests/test_gpu_mmp_block_f16_io.py, bit for bit).
+// The flags travel in the geometry's TYPE, MmpBlkhIo<G, XH, OH> below, not as two further template parameters: the kernels of
+// float32 memory keep their names mmp_blkh_kernel<G, STRIDE, PROJ> and their bytes, and tests/test_mmp_block{2,3,4}_f16_cpu.py,
+// which count exactly three kernels of that name per stage, keep holding. Everything that follows from the flags is derived in
+// the body, as for HALF and ROWS; the geometries gained no switch.
+// Modelled before the device run, from the code only. Global memory instructions per thread and tile, float32 form -> octet
+// form: staging loads of x in front of the first barrier / loads of x in the epilogue / stores of out:
+//   layer2  32 -> 32 identity    72 dwords -> 9 of 16 B   /  48 dwords -> 12 of 8 B              /  48 dwords -> 12 of 8 B
+//   layer2  16 -> 32 strided    144 -> 18                 /  6 groups x 8 = 48 -> 6 of 16 B      /  48 -> 12
+//   layer3  64 -> 64 identity    72 -> 9                  /  48 -> 12                            /  48 -> 12
+//   layer3  32 -> 64 strided    144 -> 18                 /  6 x 8 = 48 -> 6                     /  48 -> 12
+//   layer4 128 -> 128 identity   80 -> 10                 /  64 -> 16                            /  64 -> 16
+//   layer4  64 -> 128 strided   160 -> 20 (two chunks)    /  4 groups x 2 K blocks x 8 = 64 -> 8 /  64 -> 16
+// Bytes per element 4 -> 2 on each binary16 side. 7 / 8 of the staging and projection loads, 3 / 4 of the identity loads and
+// 3 / 4 of the stores go, and with them the 8 conversions per staged item. Expected from this: every launch faster, the strided
+// layer2 block (144 loads under two workgroups per CU) most; by how much is for the run to say (DESIGN.md section 7,
+// profiles/mmp_f16_activations_evaluate.json).
+// Measured (both arms on f16 operands in one process, three runs each, 440 rows): the 13 launches of layer2 .. layer4 0.936-0.946 ms
+// against 1.291-1.296 on float32 memory, 0.72-0.73 x; the stage 180.5 ms per lock-step against 197.0. The eleven blocks with both
+// sides binary16 run at 0.62-0.71 x; the strided layer2 block, expected to gain most, gained least (0.193 -> 0.175 ms): its x is
+// layer1's float32 output, so only its stores changed. No counter run was made.
+// Compiler (hipcc -O3 --offload-arch=gfx950; tools/kernel_resources.py on the shipped code object), VGPRs of <2, true> / <1, true> /
+// <1, false> on float32 x and binary16 out, binary16 x and float32 out, both binary16:
+//   layer2 126 / 126 / 128,  126 / 118 / 128,  122 / 118 / 118   (siblings 126 / 126 / 122; bound 256 at stride 2, else 128)
+//   layer3 163 / 122 / 124,  171 / 128 / 122,  169 / 128 / 122   (siblings 165 / 124 / 124; bound 256 at stride 2, else 128)
+//   layer4 140 / 126 / 146,  138 / 128 / 144,  138 / 122 / 144   (siblings 162 / 142 / 146; bound 168)
+// each with its sibling's LDS, no spills, scratch 0 (tests/test_mmp_activations_cpu.py). The one thing a register count forced is in
+// the epilogue, where it is said; the nine kernels of float32 memory are byte for byte the parent's
+// (profiles/mmp_f16_activations_code_object_identity.txt).
+//
 // A geometry G holds (nmpc_mmp_block3_f16.h is the plainest to read):
 //   Params                   the kernel's argument, a true __global__ argument: handed on by value or by reference it costs
 //                            registers (layer3 <1, false>: 124 VGPRs -> 128 and 6 spilled), so helpers take the ints they need
@@ -91,10 +132,26 @@ __device__ __forceinline__ _Float16 mmp_blkh_round(float v)
     return (_Float16)v;
 }
 
+// A geometry with the form of x and out in memory: G itself is float32 both ways; MmpBlkhIo<G, XH, OH> is G on the octet form
+// of x (XH) and / or of out (OH), p.x / p.out then pointing at binary16 (the Params are G's, the pointers are cast)
+template <typename G, bool XH_, bool OH_>
+struct MmpBlkhIo : G {
+    static constexpr bool XH = XH_, OH = OH_;
+};
+template <typename G>
+struct mmp_blkh_io {
+    static constexpr bool XH = false, OH = false;
+};
+template <typename G, bool XH_, bool OH_>
+struct mmp_blkh_io<MmpBlkhIo<G, XH_, OH_>> {
+    static constexpr bool XH = XH_, OH = OH_;
+};
+
 template <typename G, int STRIDE, bool PROJ>
 __global__ __launch_bounds__(G::Threads, G::min_wg(STRIDE)) void mmp_blkh_kernel(typename G::Params p)
 {
     static_assert(STRIDE == 1 || STRIDE == 2, "stride");
+    constexpr bool XH = mmp_blkh_io<G>::XH, OH = mmp_blkh_io<G>::OH; // x / out in memory in the octet form of binary16
     constexpr int CK = G::ck(STRIDE);                  // input channels per chunk
     constexpr bool HALF = CK < 32;                     // a chunk is half a K block
     constexpr int NOC = CK / 8;                        // octets of channels per chunk
@@ -121,6 +178,7 @@ __global__ __launch_bounds__(G::Threads, G::min_wg(STRIDE)) void mmp_blkh_kernel
     const int gy0 = tyi * G::TH - oy, gx0 = txi * G::TW - ox; // the output pixel of position 0
     const size_t plane = (size_t)p.H * p.W, plane2 = (size_t)p.H2 * p.W2;
     const float* xn = p.x + (size_t)n * p.Cin * plane;
+    const _Float16* xh = reinterpret_cast<const _Float16*>(p.x) + (size_t)n * p.Cin * plane; // (XH: the row in the octet form)
     const int KB1 = (p.Cin + 31) >> 5;               // K blocks of the first convolution and the projection
 
     const mmp_blkh_f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -148,8 +206,12 @@ __global__ __launch_bounds__(G::Threads, G::min_wg(STRIDE)) void mmp_blkh_kernel
                 const bool in = ch < p.Cin && y >= 0 && y < p.H && xx >= 0 && xx < p.W;
                 const size_t at = in ? (size_t)ch * plane + (size_t)y * p.W + xx : (size_t)0;
                 mmp_blkh_h8 v;
+                if constexpr (XH) { // octet ch / 8 of the pixel: one 16-byte load, already rounded
+                    v = in ? *reinterpret_cast<const mmp_blkh_h8*>(xh + 8 * ((size_t)(ch >> 3) * plane + (size_t)y * p.W + xx)) : zero8;
+                } else {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = mmp_blkh_round(in ? xn[at + (size_t)j * plane] : 0.0f);
+                    for (int j = 0; j < 8; ++j) v[j] = mmp_blkh_round(in ? xn[at + (size_t)j * plane] : 0.0f);
+                }
                 *reinterpret_cast<mmp_blkh_h8*>(lds + 8 * (pl * PL + q + SH)) = v;
             }
         }
@@ -250,6 +312,7 @@ __global__ __launch_bounds__(G::Threads, G::min_wg(STRIDE)) void mmp_blkh_kernel
 
     // ---- 4. the projection, the affine, the identity, the activation and the store
     float* on = p.out + (size_t)n * G::C * plane2;
+    _Float16* oh = reinterpret_cast<_Float16*>(p.out) + (size_t)n * G::C * plane2; // (OH: the row in the octet form)
 #pragma unroll
     for (int i = 0; i < G::NO; ++i) {
         if constexpr (G::RegTight) __builtin_amdgcn_sched_barrier(0); // (the loads of one pixel group at a time)
@@ -267,8 +330,12 @@ __global__ __launch_bounds__(G::Threads, G::min_wg(STRIDE)) void mmp_blkh_kernel
                 const int ch = 32 * kb + 8 * k4;
                 const bool ld = valid && ch < p.Cin;
                 mmp_blkh_h8 b;
+                if constexpr (XH) { // octet 4 kb + k4 at the pixel
+                    b = ld ? *reinterpret_cast<const mmp_blkh_h8*>(xh + 8 * ((size_t)(4 * kb + k4) * plane + (size_t)(STRIDE * y) * p.W + STRIDE * xx)) : zero8;
+                } else {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) b[j] = mmp_blkh_round(ld ? xc[(size_t)(ch + j) * plane] : 0.0f);
+                    for (int j = 0; j < 8; ++j) b[j] = mmp_blkh_round(ld ? xc[(size_t)(ch + j) * plane] : 0.0f);
+                }
 #pragma unroll
                 for (int h = 0; h < NH; ++h)
                     idacc[h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
@@ -277,17 +344,30 @@ __global__ __launch_bounds__(G::Threads, G::min_wg(STRIDE)) void mmp_blkh_kernel
         }
         if (!valid) continue;
         const size_t pix = (size_t)y * p.W2 + xx;
+        // (with OH the fragment's offset is worked out here, not kept across the second convolution: kept, layer2 <1, false> on
+        // float32 x spilled 1 register at its bound of 128 and layer3 <1, true> on binary16 x spilled 3; worked out here with XH
+        // alone, layer2 <1, false> spilled 2)
+        int k4o = k4;
+        if constexpr (OH) asm volatile("" : "+v"(k4o));
 #pragma unroll
-        for (int h = 0; h < NH; ++h)
+        for (int h = 0; h < NH; ++h) {
+            // the D fragment's four channels in the octet form: half k4 & 1 of octet 2 (hb + h) + (k4 >> 1) at the pixel
+            const size_t ho = 8 * ((size_t)(2 * (hb + h) + (k4o >> 1)) * plane2 + pix) + 4 * (k4o & 1);
+            mmp_blkh_h4 idh = {0, 0, 0, 0}, ov;
+            if constexpr (XH && !PROJ) idh = *reinterpret_cast<const mmp_blkh_h4*>(xh + ho); // (no projection: plane2 == plane)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int co = 16 * (hb + h) + 4 * k4 + r;
                 const size_t o = (size_t)co * plane2 + pix;
                 const float z = fmaf(p.s2[co], acc[i][h][r], p.b2[co]);
-                const float id = PROJ ? fmaf(p.sd[co], idacc[h][r], p.bd[co]) : xn[o]; // (no projection: plane2 == plane)
+                const float id = PROJ ? fmaf(p.sd[co], idacc[h][r], p.bd[co]) : XH ? (float)idh[r] : xn[o]; // (no projection: plane2 == plane)
                 const float v = z + id;
-                on[o] = v > 0.0f ? v : v * p.slope_out;
+                const float w = v > 0.0f ? v : v * p.slope_out;
+                if constexpr (OH) ov[r] = mmp_blkh_round(w);
+                else on[o] = w;
             }
+            if constexpr (OH) *reinterpret_cast<mmp_blkh_h4*>(oh + ho) = ov;
+        }
     }
 }
 

@@ -27,6 +27,8 @@ _HALF = {"layer3": (pack_block3_f16, _capi.NmpcMmpBlock3F16Args, "mmp_block3_f16
 # ``operands=``: every stage that has such a kernel -- ``half``'s, and layer2, which ``half`` refuses
 _F16 = {"layer2": (pack_block2_f16, _capi.NmpcMmpBlock2F16Args, "mmp_block2_f16"), **_HALF}
 _OPERANDS = ("f32", "f16")
+# ``activations="f16"``: the Handle method of such a stage that takes the form of x and of out in memory beside the struct
+_F16_IO = {name: launch + "_io" for name, (_, _, launch) in _F16.items()}
 # what each keyword behind ``stem`` needs in front of it, as ``check_specs`` says it
 _NEEDS = (("the blocks run on the fused first layer's output",)
           + tuple(f"the blocks of {st.layer} run on the fused {prev.layer}'s output" for prev, st in zip(STAGES, STAGES[1:]))
@@ -45,12 +47,24 @@ class Stage:
         self.reads_fill = reads_fill                        # its first block reads the fill's output, so its buffers cannot lie there
         self.in_fill, self.offset = False, None             # the buffers lie inside the fill's output, that many floats into each row
         self.pp, self.args = None, ()                       # allocate(): the two buffers [2, rows * prod(buf_row)], one struct per block
+        self.io = None                                      # with binary16 activations: per block (x_f16, out_f16), which ``launch`` then takes
+
+    @property
+    def out_f16(self) -> bool:
+        """Whether the last block's output lies in its buffer as binary16 in the octet form."""
+        return self.io is not None and bool(self.io[-1][1])
+
+    def run(self, j: int, rows: int):
+        """Launches block ``j`` of the stage on ``rows`` rows."""
+        a = self.args[j]
+        a.M = rows
+        return self.launch(a) if self.io is None else self.launch(a, *self.io[j])
 
 
 class MmpFrontEnd:
     def __init__(self, handle: _capi.Handle, dtype, device, Hm: int, Wm: int, n_off: int, transform, rescale: float, sigma: float,
                  ref_image, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=(),
-                 operands=None):
+                 operands=None, activations=None):
         """``dtype``: the element type of ``hist``; ``ref_image``: the float32 label image ``[Hm, Wm]`` on ``device``; ``transform``: the
         :class:`.snap.WorldTransform` between map pixels and the world of ``hist``; ``stem``: a :class:`.mmp_stem.StemSpec`; ``blocks``
         .. ``blocks4``: the specs of ``layer1`` .. ``layer4`` (``mmp_stem.STAGES``), each needing the one before it; ``head`` (needs
@@ -68,6 +82,14 @@ class MmpFrontEnd:
         and ``"layer4"``, each needing its blocks; ``"f32"`` for any stage. ``None``, ``{}`` or all ``"f32"`` changes no bit.
         ``self.half`` is what ``check_half`` returned, ``self.operands`` what ``check_operands`` did: the operand type of every
         stage given.
+        ``activations``: ``None`` or ``"f32"`` changes no bit and no launch. ``"f16"`` (needs a stage on f16 operands): every tensor
+        that a block on f16 operands writes AND a block on f16 operands reads -- across stage borders too -- lies in memory as
+        binary16 in the octet form ``[rows, C / 8, H, W, 8]`` (``mmp_stem.pack_activations_f16``, csrc/nmpc_mmp_block_f16.h, whose rule
+        then rounds ``out`` once, after the last LeakyReLU), launched through ``nmpc_mmp_block{2,3,4}_f16_io``; with layer2 .. layer4 on
+        ``"f16"`` that is 12 of their 13 blocks' inputs. Every other tensor stays float32 NCHW: what layer1 or a float32 stage writes,
+        what a float32 stage, the head or the caller's network reads. A binary16 tensor lies in the same two buffers of its stage, in
+        the front half of the float slot; the placement rule and ``bytes_per_item`` do not change: the halved footprint is not
+        exploited. ``self.activations`` is ``"f32"`` or ``"f16"``; a stage's ``io`` holds the two flags of each of its blocks.
 
         Where a stage's two buffers lie is one rule: the fill's output (the stem's, ``[C, Hp, Wp]`` per row) is idle once layer1's
         first block has read it, so the buffers of the stages behind layer1 are laid INSIDE it one behind the other, at a running
@@ -80,6 +102,7 @@ class MmpFrontEnd:
         stem, head = specs[0], specs[-1]
         self.operands = self.check_operands(operands, half, specs)
         self.half = self.check_half(half, specs)
+        self.activations = self.check_activations(activations, self.operands)
         self.h, self.dt, self.dev, self.n_off = handle, np.dtype(dtype), device, int(n_off)
         bits = lambda a: a.view(np.int16) if a.dtype == np.uint16 else a          # (packed binary16 bit patterns travel as int16)
         dev = lambda spec, names: spec._replace(**{n: torch.as_tensor(bits(getattr(spec, n)), device=device) for n in names if getattr(spec, n) is not None})
@@ -120,7 +143,17 @@ class MmpFrontEnd:
             inside = st.in_fill or st.reads_fill
             self.row = (st.channels,) + planes[-1]
             self.stages.append(st)
-        self.head = None if head is None else dev(head, _HEAD_ARRAYS)      # (uploaded last: the weights keep the order of the network)
+        if self.activations == "f16":
+            # a tensor is binary16 where the block that writes it and the block that reads it both run on f16 operands
+            f16 = [self.operands[st.name] == "f16" for st in self.stages for _ in st.specs]
+            between = [False] + [a and b for a, b in zip(f16, f16[1:])] + [False]      # in front of block k: between[k]
+            k = 0
+            for st in self.stages:
+                if self.operands[st.name] == "f16":
+                    st.launch = getattr(handle, _F16_IO[st.name])
+                    st.io = tuple((int(between[k + j]), int(between[k + j + 1])) for j in range(len(st.specs)))
+                k += len(st.specs)
+        self.head =None if head is None else dev(head, _HEAD_ARRAYS)      # (uploaded last: the weights keep the order of the network)
         if head is not None:
             F, want = int(head.w1.shape[1]), head_features(*self.row)
             if F != want or min(self.row[1:]) < 2:
@@ -182,6 +215,15 @@ class MmpFrontEnd:
         return {st.layer: "f16" if st.layer in half or operands.get(st.layer) == "f16" else "f32"
                 for k, st in enumerate(STAGES) if specs[1 + k] is not None}
 
+    @staticmethod
+    def check_activations(activations, operands, prefix: str = "") -> str:
+        """``activations`` as ``"f32"`` (also for ``None``) or ``"f16"``, checked against what ``check_operands`` returned."""
+        if activations is not None and activations not in _OPERANDS:
+            raise ValueError(f"{prefix}activations: {activations!r} is none of None, 'f32' and 'f16'")
+        if activations == "f16" and "f16" not in operands.values():
+            raise ValueError(f"{prefix}activations: 'f16' needs a stage on f16 operands ({prefix}operands)")
+        return activations or "f32"
+
     def stage(self, name: str):
         """The :class:`Stage` called ``name`` (``"layer1"`` ..), or ``None`` if its specs were not given."""
         return next((st for st in self.stages if st.name == name), None)
@@ -241,22 +283,35 @@ class MmpFrontEnd:
         j = i
         for st in self.stages:
             if 0 <= j < len(st.args):
-                st.args[j].M = rows
-                return st.launch(st.args[j])
+                return st.run(j, rows)
             j -= len(st.args)
         counts = [len(st.args) for st in self.stages] + [0, 0]
         raise IndexError(f"block {i} of " + " + ".join(str(c) for c in counts[:2] + [c for c in counts[2:] if c]))
 
     def run_stage(self, name: str, rows: int):
         """All blocks of stage ``name``, one after the other, on the first ``rows`` rows of what the stage in front (for layer1 the
-        fill) left. Returns the last one's ``[rows, channels, H, W]``, a view of the stage's buffer."""
-        self._check_rows(rows)
+        fill) left. Returns the last one's float32 ``[rows, channels, H, W]``: a view of the stage's buffer, or, where that tensor
+        is binary16 in memory (``activations="f16"``, the next stage on f16 operands too), a decoded COPY of it, made with torch
+        operations on the device -- ``run`` launches the same blocks and never decodes."""
         st = self.stage(name)
-        for a in st.args:
-            a.M = rows
-            st.launch(a)
-        row = (st.channels,) + st.planes[-1]
-        return st.pp[(len(st.args) - 1) % 2][:rows * int(np.prod(row))].view(rows, *row)
+        self._launch_stage(st, rows)
+        return self._stage_out(st, rows)
+
+    def _launch_stage(self, st: Stage, rows: int):
+        """The launches of ``run_stage``, and nothing else."""
+        self._check_rows(rows)
+        for j in range(len(st.args)):
+            st.run(j, rows)
+
+    def _stage_out(self, st: Stage, rows: int):
+        """What ``run_stage`` returns, from what the last block of ``st`` left in its buffer."""
+        import torch
+        C, (H, W) = st.channels, st.planes[-1]
+        buf = st.pp[(len(st.args) - 1) % 2]
+        if not st.out_f16:
+            return buf[:rows * C * H * W].view(rows, C, H, W)
+        octets = buf.view(torch.int16)[:rows * C * H * W].view(torch.float16).view(rows, C // 8, H, W, 8)
+        return octets.permute(0, 1, 4, 2, 3).reshape(rows, C, H, W).float()
 
     def run_blocks(self, rows: int):
         """``run_stage("layer1", rows)``: ``[rows, 16, Hp, Wp]``."""
@@ -292,7 +347,9 @@ class MmpFrontEnd:
         part = part or (lambda name, call: call())
         x = part("input", lambda: self.fill(hist, hcount, B, H, items, n))
         for st in self.stages:
-            x = part(st.name, lambda st=st: self.run_stage(st.name, n * self.n_off))
+            part(st.name, lambda st=st: self._launch_stage(st, n * self.n_off))
+        if self.stages:
+            x = self._stage_out(self.stages[-1], n * self.n_off)   # (float32 always: its reader is the head or the caller's network)
         if self._head_args is not None:
             x = part("head", lambda: self.run_head(n * self.n_off))
         return x

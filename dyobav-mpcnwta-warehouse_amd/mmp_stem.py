@@ -470,6 +470,27 @@ pack_block4_f16 = functools.partial(pack_block_f16, channels=BLOCK4_CHANNELS)
 unpack_block2_f16 = unpack_block3_f16 = unpack_block4_f16 = unpack_block_f16
 
 
+def pack_activations_f16(x) -> np.ndarray:
+    """Activations ``[M, C, H, W]`` (float, ``C % 8 == 0``) -> the octet form of binary16 activations in memory (include/nmpc_hip.h,
+    csrc/nmpc_mmp_block_f16.h): uint16 bit patterns ``[M, C // 8, H, W, 8]`` with ``a[n, c // 8, y, x, c % 8] = round_f16(x[n, c, y, x])``,
+    C-contiguous."""
+    x = np.asarray(x)
+    if x.ndim != 4 or x.shape[1] % 8 or x.shape[1] == 0:
+        raise ValueError(f"pack_activations_f16: shape {x.shape} is no [M, C, H, W] with C a positive multiple of 8")
+    M, C, H, W = x.shape
+    return np.ascontiguousarray(round_f16(x).reshape(M, C // 8, 8, H, W).transpose(0, 1, 3, 4, 2)).view(np.uint16)
+
+
+def unpack_activations_f16(a) -> np.ndarray:
+    """The inverse of ``pack_activations_f16``: uint16 ``[M, C // 8, H, W, 8]`` -> float32 ``[M, C, H, W]``, exact (every binary16 value
+    is a float32 value)."""
+    a = np.asarray(a)
+    if a.ndim != 5 or a.shape[4] != 8 or a.dtype != np.uint16:
+        raise ValueError(f"unpack_activations_f16: {a.dtype} {a.shape} is no uint16 [M, C // 8, H, W, 8]")
+    M, O, H, W, _ = a.shape
+    return np.ascontiguousarray(np.ascontiguousarray(a).view(np.float16).transpose(0, 1, 4, 2, 3).reshape(M, 8 * O, H, W).astype(np.float32))
+
+
 def _linear(fn, name, layer, n_in, n_out):
     """(weight [out, in], bias [out]) of a ``torch.nn.Linear`` -like ``layer`` as float32; a missing bias is zeros."""
     import torch

@@ -50,9 +50,13 @@ on binary16 operands, which this option does not touch: ``mmp_half=("layer3",)``
 ``mmp_half=("layer3", "layer4")``, alternated in one process: the three launches alone on one chunk, then the closed loop.
 ``--half-layer2``: the same protocol for layer2 on binary16 operands (``nmpc_mmp_block2_f16``), both arms with layer3 and layer4 on
 them: ``mmp_half=("layer3", "layer4")`` against the same with ``mmp_operands={"layer2": "f16"}``; the four launches alone, then the loop.
+``--activations-f16``: the same protocol for binary16 activations in memory (``nmpc_mmp_block{2,3,4}_f16_io``), both arms with layer2,
+layer3 and layer4 on binary16 operands: ``mmp_activations="f32"`` (the parent's path) against ``"f16"``; the 13 launches alone per run
+and per block, then the loop; the record holds both arms' run-to-run spreads and whether the f16 arm is faster by more than the
+larger of them in every run.
    usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]
           [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS] | --fused-layer4 [REPS] | --half-layer3 [REPS]
-           | --half-layer4 [REPS] | --half-layer2 [REPS]]
+           | --half-layer4 [REPS] | --half-layer2 [REPS] | --activations-f16 [REPS]]
           (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
@@ -920,8 +924,115 @@ def half_layer2_main(out_path, B, steps, dt, n_ped, K, reps):
         print(p, json.dumps({"all": (r["ms_median"], r["TFMAps_median"], r["GBps_median"])}))
 
 
+def activations_kernel_rate(ev, n_item, reps=10):
+    """The 13 launches of layer2, layer3 and layer4 of the evaluator's front end alone on the layer1 output of ``n_item`` pedestrians:
+    ms each and together (``run_block``: the launches only, nothing is decoded), and the bytes of x and out as they lie in memory."""
+    fe = ev.mmp_front
+    rows = _fill(ev, n_item)().shape[0]
+    fe.run_blocks(rows)
+    first, stages = len(fe.blocks), [fe.stage(n) for n in ("layer2", "layer3", "layer4")]
+    count = sum(len(st.args) for st in stages)
+    run_all = lambda: [fe.run_block(first + i, rows) for i in range(count)]
+    run_all()
+    rec, i = {"items": n_item, "rows": rows, "blocks": []}, first
+    for st in stages:
+        for j in range(len(st.args)):
+            xh, oh = st.io[j] if st.io else (0, 0)
+            (H, W), (H2, W2), Cin = st.planes[j], st.planes[j + 1], st.cins[j]
+            nbytes = rows * ((2 if xh else 4) * Cin * H * W + (2 if oh else 4) * st.channels * H2 * W2)
+            t = _timed(lambda i=i: fe.run_block(i, rows), reps, warm=3)
+            rec["blocks"].append(dict(stage=st.name, Cin=Cin, plane_in=[H, W], plane_out=[H2, W2], x_f16=xh, out_f16=oh, bytes=nbytes,
+                                      GBps_median=nbytes / t["ms_median"] * 1e-6, share_of_copy_rate=nbytes / t["ms_median"] * 1e-9 / COPY_TBS, **t))
+            i += 1
+    rec.update(bytes=sum(b["bytes"] for b in rec["blocks"]), **_timed(run_all, reps, warm=3))
+    return rec
+
+
+def activations_f16_main(out_path, B, steps, dt, n_ped, K, reps):
+    """``--activations-f16``: the protocol of ``--half-layer2`` for binary16 activations in memory. Both arms run the whole network on
+    the device with layer2, layer3 and layer4 on binary16 operands; ``f32`` keeps the activations float32 (``mmp_activations="f32"``: the
+    parent's path), ``f16`` keeps them binary16 between those blocks (``mmp_activations="f16"``, nmpc_mmp_block{2,3,4}_f16_io),
+    alternated in one process: the 13 launches alone on one chunk, then the closed loop with events around every part."""
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import split_network_whole
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    as_block = lambda b: SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)
+    L = list(net)
+    shaped = SimpleNamespace(resnet34=SimpleNamespace(stem=SimpleNamespace(conv1=L[0], pooling=L[1]), layer1=[as_block(b) for b in L[2:5]],
+                                                      layer2=[as_block(b) for b in L[5:9]], layer3=[as_block(b) for b in L[9:15]],
+                                                      layer4=[as_block(b) for b in L[15:18]], apool=L[18]), fc1=L[20], leaky=L[21], swarm=L[22])
+    spec, blocks, blocks2, blocks3, blocks4, head = split_network_whole(shaped)
+    head = head._replace(c2=head.c2 + np.float32(150.0))   # (the "+ 150" that puts the random network's hypotheses on the map)
+    whole = dict(network=None, mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, mmp_blocks3=blocks3, mmp_blocks4=blocks4, mmp_head=head,
+                 mmp_operands={"layer2": "f16", "layer3": "f16", "layer4": "f16"})
+    paths = {"f32": dict(whole, mmp_activations="f32"), "f16": dict(whole, mmp_activations="f16")}
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rows_step = B * n_ped * nm.default_config_struct().N_hor
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage, the whole network on the device, layer2, "
+                   "layer3 and layer4 on binary16 operands in both arms: activations float32 in memory (mmp_activations = 'f32', the parent's "
+                   "path) and binary16 in the octet form between those blocks (mmp_activations = 'f16', nmpc_mmp_block{2,3,4}_f16_io), "
+                   "alternated in one process; random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS}, "chunk_pedestrians": {}, "kernels": {p: [] for p in paths}, "runs": {p: [] for p in paths}}
+    for _ in range(reps):                                   # the 13 launches alone, per arm, alternated (the first also warms up)
+        for path in paths:
+            ev = evaluator(path)
+            rec["chunk_pedestrians"][path] = ev.mmp_chunk
+            try:
+                rec["kernels"][path].append(activations_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped)))
+                ev.run(max_steps=1)
+            finally:
+                ev.close()
+            r = rec["kernels"][path][-1]
+            print(path, json.dumps({"rows": r["rows"], "thirteen_launches_ms": r["ms_median"], "each": [b["ms_median"] for b in r["blocks"]]}), flush=True)
+            with open(out_path, "w") as f:
+                json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = ("input", "layer1", "layer2", "layer3", "layer4", "head")
+    spread = lambda v: (max(v) - min(v)) / float(np.median(v))
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names}, stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    rec["stage_median_of_each_run_ms"] = {p: [float(np.median([s["stage_ms"] for s in run])) for run in rec["runs"][p]] for p in paths}
+    rec["thirteen_launches_of_each_run_ms"] = {p: [r["ms_median"] for r in rec["kernels"][p]] for p in paths}
+    rec["thirteen_launches_per_lock_step_ms"] = {p: float(np.median([r["ms_median"] * rows_step / r["rows"] for r in rec["kernels"][p]])) for p in paths}
+    rec["each_block_median_ms"] = {p: [float(np.median([r["blocks"][i]["ms_median"] for r in rec["kernels"][p]])) for i in range(13)] for p in paths}
+    thirteen, stage = rec["thirteen_launches_of_each_run_ms"], rec["stage_median_of_each_run_ms"]
+    rec["run_to_run_spread"] = {"thirteen_launches": {p: spread(thirteen[p]) for p in paths}, "stage": {p: spread(stage[p]) for p in paths}}
+    rec["f16_over_f32_thirteen_launches_of_each_run"] = [a / b for a, b in zip(thirteen["f16"], thirteen["f32"])]
+    rec["f16_over_f32_stage_of_each_run"] = [a / b for a, b in zip(stage["f16"], stage["f32"])]
+    # the criterion: in every run the f16 arm is below the f32 arm by more than the larger of the two arms' run-to-run spreads
+    rec["margin"] = {"thirteen_launches": max(rec["run_to_run_spread"]["thirteen_launches"].values()), "stage": max(rec["run_to_run_spread"]["stage"].values())}
+    rec["faster_in_every_run"] = {"thirteen_launches": all(r < 1.0 - rec["margin"]["thirteen_launches"] for r in rec["f16_over_f32_thirteen_launches_of_each_run"]),
+                                  "stage": all(r < 1.0 - rec["margin"]["stage"] for r in rec["f16_over_f32_stage_of_each_run"])}
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "stage_median_of_each_run_ms", "thirteen_launches_of_each_run_ms",
+                                          "thirteen_launches_per_lock_step_ms", "each_block_median_ms", "run_to_run_spread",
+                                          "f16_over_f32_thirteen_launches_of_each_run", "f16_over_f32_stage_of_each_run", "margin", "faster_in_every_run",
+                                          "chunk_pedestrians")}))
+
+
 def main():
-    for flag, run in (("--half-layer2", half_layer2_main), ("--half-layer4", half_layer4_main), ("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+    for flag, run in (("--activations-f16", activations_f16_main), ("--half-layer2", half_layer2_main), ("--half-layer4", half_layer4_main), ("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
         if flag in sys.argv:
             i = sys.argv.index(flag)
             reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
