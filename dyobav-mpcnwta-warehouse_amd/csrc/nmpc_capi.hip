@@ -1760,6 +1760,12 @@ int mmp_block(nmpc_handle_s* h, const nmpc_mmp_block_args* g)
 // a stage's tile: the kernels' pixel coordinates are ints and reach 2 (tile origin + reach) + 1, which must not wrap -- hence no
 // plane over 2^30 --, and once the workgroup count has passed H2 W2 M <= (outputs of a tile) x 2^31, with H W <= 4 H2 W2: the byte
 // counts of the overlap test do not overflow.
+// The kernels of a geometry G of the float32 block (csrc/nmpc_mmp_block_f32.h), in a stage's order
+template <typename G>
+struct MmpBlkfKernels {
+    static constexpr void (*table[3])(typename G::Params) = {nmpc::mmp_blkf_kernel<G, 2, true>, nmpc::mmp_blkf_kernel<G, 1, true>, nmpc::mmp_blkf_kernel<G, 1, false>};
+};
+
 // The kernels of a geometry G on the octet form of binary16 activations (csrc/nmpc_mmp_block_f16.h): table[2 x_f16 + out_f16 - 1]
 // holds <stride 2, projection>, <stride 1, projection>, <stride 1, identity>, as a stage's kernels[] does for float32 memory
 template <typename G>
@@ -1777,7 +1783,7 @@ struct MmpLayer2 {
     using Params = nmpc::MmpBlock2Params;
     static constexpr const char* name = "nmpc_mmp_block2";
     static constexpr int C = nmpc::kB2C, threads = nmpc::kB2Threads, packed_align = 0;
-    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk2_kernel<2, true>, nmpc::mmp_blk2_kernel<1, true>, nmpc::mmp_blk2_kernel<1, false>};
+    static constexpr auto& kernels = MmpBlkfKernels<nmpc::MmpBlock2Geom>::table;
     // tiles of 8 x 44 = 352 outputs; reach 11
     template <typename P>
     static void tile(P& p, long long& ty, long long& tx)
@@ -1803,7 +1809,7 @@ struct MmpLayer3 {
     using Params = nmpc::MmpBlock3Params;
     static constexpr const char* name = "nmpc_mmp_block3";
     static constexpr int C = nmpc::kB3C, threads = nmpc::kB3Threads, packed_align = 0;
-    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk3_kernel<2, true>, nmpc::mmp_blk3_kernel<1, true>, nmpc::mmp_blk3_kernel<1, false>};
+    static constexpr auto& kernels = MmpBlkfKernels<nmpc::MmpBlock3Geom>::table;
     // tiles of 7 x 21 = 147 outputs; reach 10
     template <typename P>
     static void tile(P& p, long long& ty, long long& tx)
@@ -1829,7 +1835,7 @@ struct MmpLayer4 {
     using Params = nmpc::MmpBlock4Params;
     static constexpr const char* name = "nmpc_mmp_block4";
     static constexpr int C = nmpc::kB4C, threads = nmpc::kB4Threads, packed_align = 0;
-    static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blk4_kernel<2, true>, nmpc::mmp_blk4_kernel<1, true>, nmpc::mmp_blk4_kernel<1, false>};
+    static constexpr auto& kernels = MmpBlkfKernels<nmpc::MmpBlock4Geom>::table;
     // tiles of at most 10 x 11 = 110 outputs; reach 11. A side that fits the tile's plane of m is one tile without a halo; a longer
     // one is cut with a halo of one
     template <typename P>

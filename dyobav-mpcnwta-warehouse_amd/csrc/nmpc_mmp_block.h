@@ -6,7 +6,10 @@
 //   id  = x  (wd == nullptr, Cin == 16)  |  sd * conv1x1(x, wd) + bd                     (the first block's `downsample`)
 //   out = leaky( z + id , slope_out )
 // x [M][Cin][H][W] -> out [M][16][H][W]; m, z and id never exist in memory. The norms are folded into (s, b) on the host
-// (mmp_stem.fold_block). m outside the plane is ZERO (the second convolution's padding), not leaky(b1).
+// (mmp_stem.fold_block). m outside the plane is ZERO (the second convolution's padding), not leaky(b1). The later stages share ONE
+// kernel (nmpc_mmp_block_f32.h, which states the flat domain, the fragments and the summation order they have in common with this
+// one); this kernel stays on its own: it keeps x and m in two LDS arrays, holds the projection's accumulators resident inside the
+// conv1 loop, re-derives its groups of out and has no stride -- a flag each.
 //
 // Instructions: v_mfma_f32_16x16x4_f32 (exact f32: a k-ordered fmaf chain, one rounding per product; 1 024 fma per
 // instruction, 32 cycles per SIMD = the vector fp32 rate, and the issue slots stay free for the LDS reads). An implicit

@@ -99,9 +99,9 @@ static_assert(kB2HPB % 256 == 0, "the plane stride must keep a lane group's two 
 static_assert(kB2S - (kB2S + 1) + 1 >= 0 && (kB2R - 1) * kB2S - 1 + (kB2S + 1) + 1 < kB2P, "a tap leaves the plane");
 static_assert(kB2HMP * kB2HPB * 4 <= 160 * 1024, "four workgroups do not fit a CU's LDS");
 
-// layer2's geometry of mmp_blkh_kernel (nmpc_mmp_block_f16.h): every wave holds both A groups and takes the pixel groups j & 3 ==
-// wave in the sibling's order (decision 1); position q sits at slot q + 1 (decision 2)
-struct MmpBlock2HGeom {
+// layer2's geometry of mmp_blkh_kernel (nmpc_mmp_block_f16.h): the sibling's waves -- every wave holds both A groups and takes the
+// pixel groups j & 3 == wave in the sibling's order (decision 1) --; position q sits at slot q + 1 (decision 2)
+struct MmpBlock2HGeom : MmpBlock2Waves {
     using Params = MmpBlock2HParams;
     static constexpr int C = kB2C, Threads = kB2Threads, S = kB2S, Q = kB2Q, TH = kB2TH, TW = kB2TW;
     static constexpr int PL = kB2P, SH = 1;
@@ -110,11 +110,6 @@ struct MmpBlock2HGeom {
     static constexpr bool Fitted = false, RegTight = false;
     static constexpr int ck(int stride) { return stride == 2 ? 16 : 32; } // (decision 4: half a K block, with zeros)
     static constexpr int min_wg(int stride) { return stride == 2 ? 2 : 4; }
-    // two waves have 7 groups of m: their eighth slot computes the last group again and stores nothing
-    static __device__ __forceinline__ int pixel_wave(int wave) { return wave; }
-    static __device__ __forceinline__ int group(int wave, int i) { return mmp_b2_group(wave + 4 * i < kB2GM ? wave + 4 * i : kB2GM - 1); }
-    static __device__ __forceinline__ int first_a(int) { return 0; }
-    static __device__ __forceinline__ bool live(int wave, int i) { return wave + 4 * i < kB2GM; }
 };
 
 } // namespace nmpc

@@ -78,9 +78,9 @@ constexpr int kB3HPL = 288;                          // positions (of 16 bytes) 
 static_assert(kB3HPL * 16 % 256 == 0, "the plane stride must keep a lane group's two runs on distinct 16-byte slots");
 static_assert(kB3M0 + 16 * kB3GM + kB3S + 1 <= kB3HPL && kB3M0 - kB3S - 1 >= 0, "a tap leaves the plane");
 
-// layer3's geometry of mmp_blkh_kernel (nmpc_mmp_block_f16.h): wave = 2 pw + hw takes the pixel groups of parity pw (7 of m, its
-// first 6 of out, in the sibling's order) and the A groups 2 hw, 2 hw + 1
-struct MmpBlock3HGeom {
+// layer3's geometry of mmp_blkh_kernel (nmpc_mmp_block_f16.h): the sibling's waves -- wave = 2 pw + hw takes the pixel groups of
+// parity pw (7 of m, its first 6 of out, in the sibling's order) and the A groups 2 hw, 2 hw + 1
+struct MmpBlock3HGeom : MmpBlock3Waves {
     using Params = MmpBlock3HParams;
     static constexpr int C = kB3C, Threads = kB3Threads, S = kB3S, Q = kB3Q, TH = kB3TH, TW = kB3TW;
     static constexpr int PL = kB3HPL, SH = 0;
@@ -89,10 +89,6 @@ struct MmpBlock3HGeom {
     static constexpr bool Fitted = false, RegTight = false;
     static constexpr int ck(int stride) { return stride == 2 ? 32 : 64; }
     static constexpr int min_wg(int stride) { return stride == 2 ? 2 : 4; }
-    static __device__ __forceinline__ int pixel_wave(int wave) { return wave >> 1; }
-    static __device__ __forceinline__ int group(int pw, int i) { return mmp_b3_group(pw + 2 * i); }
-    static __device__ __forceinline__ int first_a(int wave) { return 2 * (wave & 1); }
-    static __device__ __forceinline__ bool live(int, int) { return true; }
 };
 
 } // namespace nmpc

@@ -4,8 +4,9 @@
 // float32 stages: MmpFrontEnd(half=...) / MmpFrontEnd(operands=...)). A stage is a GEOMETRY G: nmpc_mmp_block2_f16.h (32 output
 // channels), nmpc_mmp_block3_f16.h (64) and nmpc_mmp_block4_f16.h (128) hold one each, with the stage's Params, its decisions, its
 // model and its measured figures; the block itself, its strides, its padding and the zero ring of m are defined by the float32
-// siblings nmpc_mmp_block{2,3,4}.h, whose flat domains and pixel groups the geometries take over. x [M][Cin][H][W] and out
-// [M][C][H2][W2] stay float32 in memory, unless the launch says otherwise (binary16 activations in memory, below).
+// sibling nmpc_mmp_block_f32.h (mmp_blkf_kernel) and its geometries in nmpc_mmp_block{2,3,4}.h, whose flat domains, pixel groups and,
+// for layer2 and layer3, waves these geometries take over. x [M][Cin][H][W] and out [M][C][H2][W2] stay float32 in memory, unless
+// the launch says otherwise (binary16 activations in memory, below).
 //
 // The rounding rule -- whatever an MFMA reads is f16, nothing else is:
 //   - the weights w1, w2, wd are rounded ONCE on the host (mmp_stem.pack_block_f16) and arrive packed in fragment order (below);

@@ -23,7 +23,8 @@ The four residual stages behind the stem (net_module/net.py:45-61) go the same w
 A spec holds both 3 x 3 convolutions with their folded norms, the 1 x 1 projection of the stage's first block (``None`` for a block
 that adds the identity) and the two slopes -- 0.1 inside the block (``compact_conv_layer``), 0.01 behind the addition (a default
 ``nn.LeakyReLU``). Layer1 runs at stride 1; the first block of each later stage halves the plane, so their specs also hold
-``stride`` (1 or 2, of the first convolution and of the projection). ``check_blocks`` .. ``check_blocks4`` check one stage's specs
+``stride`` (1 or 2, of the first convolution and of the projection), and their float32 kernels are one, ``mmp_blkf_kernel``
+(csrc/nmpc_mmp_block_f32.h), with a geometry per stage in the table's headers. ``check_blocks`` .. ``check_blocks4`` check one stage's specs
 against what the stage in front gives. ``split_network_layer1`` .. ``split_network_layer4`` walk the table up to their stage and
 return the stem, one tuple of specs per stage and the trunk, a callable made of whatever remains, for ``BatchEvaluator(...,
 mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, ..., network=trunk)`` and ``MmpInterface(trunk, stem=spec, blocks=blocks,

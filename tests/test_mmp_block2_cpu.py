@@ -281,7 +281,7 @@ def test_block2_args_layout_matches_the_c_compiler():
 def test_block2_kernels_use_no_scratch_and_fit_two_workgroups_per_cu():
     """Read from the shipped code object: the three kernels (stride 2; stride 1 with and without the projection) without VGPR
     spills or scratch, within the 256 registers of two wavefronts per SIMD, and under 80 KB of LDS (two workgroups in a CU's
-    160 KB): the occupancy csrc/nmpc_mmp_block2.h states in its __launch_bounds__."""
+    160 KB): the occupancy csrc/nmpc_mmp_block2.h states in its geometry's min_wg, the kernel's __launch_bounds__."""
     import re
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
@@ -290,7 +290,7 @@ def test_block2_kernels_use_no_scratch_and_fit_two_workgroups_per_cu():
         sys.path.remove(os.path.join(ROOT, "tools"))
     nm.build_library()
     res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
-    mine = {k: v for k, v in res.items() if re.search(r"mmp_blk2_kernel", k)}
+    mine = {k: v for k, v in res.items() if re.search(r"mmp_blkf_kernel<nmpc::MmpBlock2Geom, ", k)}
     assert len(mine) == 3, sorted(mine)
     assert not any("mmp_block_kernel" in k for k in mine)
     for name, r in mine.items():

@@ -143,7 +143,7 @@ def test_kernels_use_no_scratch_and_fit_the_occupancy_the_header_states():
     res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
     mine = {k: v for k, v in res.items() if re.search(r"mmp_blkh_kernel<nmpc::MmpBlock2HGeom, ", k)}
     assert len(mine) == 3, sorted(mine)
-    assert not any(re.search(r"mmp_blk2_kernel", k) for k in mine)                 # the f32 family's pattern does not take these in
+    assert not any(re.search(r"mmp_blkf_kernel<nmpc::MmpBlock2Geom, ", k) for k in mine)                 # the f32 family's pattern does not take these in
     header = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block2_f16.h")).read()
     assert "Threads = kB2Threads" in header and "min_wg(int stride) { return stride == 2 ? 2 : 4; }" in header   # the geometry's figures ...
     shared = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block_f16.h")).read()

@@ -247,7 +247,7 @@ def test_block3_args_layout_matches_the_c_compiler():
 def test_block3_kernels_use_no_scratch_and_fit_two_workgroups_per_cu():
     """Read from the shipped code object: exactly three kernels (stride 2; stride 1 with and without the projection) without VGPR
     spills or scratch, within the 256 registers of two wavefronts per SIMD, and under 80 KB of LDS (two workgroups in a CU's
-    160 KB): the occupancy csrc/nmpc_mmp_block3.h states in its __launch_bounds__(256, 2)."""
+    160 KB): the occupancy csrc/nmpc_mmp_block3.h states in its geometry, the kernel's __launch_bounds__(256, 2)."""
     import re
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
@@ -256,10 +256,11 @@ def test_block3_kernels_use_no_scratch_and_fit_two_workgroups_per_cu():
         sys.path.remove(os.path.join(ROOT, "tools"))
     nm.build_library()
     res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
-    mine = {k: v for k, v in res.items() if re.search(r"mmp_blk3_kernel", k)}
+    mine = {k: v for k, v in res.items() if re.search(r"mmp_blkf_kernel<nmpc::MmpBlock3Geom, ", k)}
     assert len(mine) == 3, sorted(mine)
     header = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block3.h")).read()
-    assert "__launch_bounds__(kB3Threads, 2)" in header and "kB3Threads = 256" in header
+    shared = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block_f32.h")).read()
+    assert "__launch_bounds__(G::Threads, G::min_wg)" in shared and "Threads = kB3Threads, min_wg = 2," in header and "kB3Threads = 256" in header
     for name, r in mine.items():
         print(name, r)
         assert r["vgpr_spill"] == 0 and r["scratch"] == 0, (name, r)

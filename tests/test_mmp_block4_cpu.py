@@ -261,11 +261,13 @@ def test_block4_kernels_use_no_scratch_and_fit_one_workgroup_of_eight_waves_per_
         sys.path.remove(os.path.join(ROOT, "tools"))
     nm.build_library()
     res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
-    mine = {k: v for k, v in res.items() if re.search(r"mmp_blk4_kernel", k)}
+    mine = {k: v for k, v in res.items() if re.search(r"mmp_blkf_kernel<nmpc::MmpBlock4Geom, ", k)}
     assert len(mine) == 3, sorted(mine)
     header = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block4.h")).read()
-    assert "__launch_bounds__(kB4Threads, 1)" in header and "kB4Threads = 512" in header
-    assert f"kB4MH = {b4.TILE[0]}, kB4MW = {b4.TILE[1]}" in header and "CC = STRIDE == 2 ? 16 : 32" in header and b4.CHUNK == {1: 32, 2: 16}
+    shared = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block_f32.h")).read()
+    assert "__launch_bounds__(G::Threads, G::min_wg)" in shared and "Threads = kB4Threads, min_wg = 1," in header and "kB4Threads = 512" in header
+    assert "constexpr int CC = G::cc(STRIDE);" in shared
+    assert f"kB4MH = {b4.TILE[0]}, kB4MW = {b4.TILE[1]}" in header and "cc(int stride) { return stride == 2 ? 16 : 32; }" in header and b4.CHUNK == {1: 32, 2: 16}
     for name, r in mine.items():
         print(name, r)
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0, (name, r)

@@ -130,7 +130,7 @@ def test_kernels_use_no_scratch_and_fit_the_occupancy_the_header_states():
     res = {kernel_resources.short_name(k): v for k, v in kernel_resources.kernel_resources(nm.library_path()).items()}
     mine = {k: v for k, v in res.items() if re.search(r"mmp_blkh_kernel<nmpc::MmpBlock4HGeom, ", k)}
     assert len(mine) == 3, sorted(mine)
-    assert not any(re.search(r"mmp_blk4_kernel", k) for k in mine)                 # the f32 family's pattern does not take these in
+    assert not any(re.search(r"mmp_blkf_kernel<nmpc::MmpBlock4Geom, ", k) for k in mine)                 # the f32 family's pattern does not take these in
     header = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block4_f16.h")).read()
     assert "Threads = kB4HThreads" in header and "min_wg(int) { return 3; }" in header and "kB4HThreads = 256" in header   # the geometry's figures ...
     shared = open(os.path.join(ROOT, "dyobav-mpcnwta-warehouse_amd", "csrc", "nmpc_mmp_block_f16.h")).read()

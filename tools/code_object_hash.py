@@ -4,7 +4,9 @@
 
 Two builds whose hashes agree run the same device code: the check behind "moved out of the product headers without
 changing a single instruction" (profiles/r06_hygiene_code_object_identity.txt) and behind any A/B claim of "same bits".
-Host-side changes (layout bookkeeping, the C ABI) do not show up here by construction. A kernel that one build has under another
+Host-side changes (layout bookkeeping, the C ABI) do not show up here by construction. Where .text agrees and .rodata does not,
+the kernel descriptors in .rodata are compared field by field: renamed kernels change the sizes of the name tables in front of
+.rodata, and with them the distance from a descriptor to its code, which the descriptor records. A kernel that one build has under another
 name is compared too where ``--renamed`` says so: PATTERN is a regular expression on the demangled names of the first build,
 REPLACEMENT (``re.sub`` syntax) gives the name in the second.
 """
@@ -33,15 +35,17 @@ def code_object_hashes(lib):
             subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", f"--only-section={sec}", co, raw], check=True)
             data = open(raw, "rb").read()
             out[sec] = (len(data), hashlib.sha256(data).hexdigest())
+            out[sec + " bytes"] = data
         # per kernel: the bytes of each function symbol of .text (a kernel whose instructions did not change keeps its hash
         # even when a neighbour grew or shrank; branch offsets inside a function are relative)
         text = open(os.path.join(td, "text.bin"), "rb").read()
         base = None
         for line in subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-S", co], check=True, capture_output=True,
                                    text=True).stdout.splitlines():
-            m = re.search(r"\]\s+\.text\s+PROGBITS\s+([0-9a-f]+)", line)
+            m = re.search(r"\]\s+(\.text|\.rodata)\s+PROGBITS\s+([0-9a-f]+)", line)
             if m:
-                base = int(m.group(1), 16)
+                out[m.group(1) + " address"] = int(m.group(2), 16)
+        base = out.get(".text address")
         kernels = {}
         for line in subprocess.run(["nm", "-S", co], check=True, capture_output=True, text=True).stdout.splitlines():
             m = re.match(r"([0-9a-f]+) ([0-9a-f]+) [Tt] (\S+)$", line)
@@ -94,5 +98,17 @@ if __name__ == "__main__":
         for k, d in zip(only, demangle(only)):
             print(f"  only in one build: {d}")
         whole = seen[0][".text"] == seen[1][".text"] and seen[0][".rodata"] == seen[1][".rodata"]
+        if not whole and seen[0][".text"] == seen[1][".text"]:
+            # .rodata holds one 64-byte descriptor per kernel, in the order of .text; bytes 16 .. 23 are the offset from the
+            # descriptor to the kernel's code, which follows from where the linker put the two sections (longer names move them)
+            ra, rb = seen[0][".rodata bytes"], seen[1][".rodata bytes"]
+            gap = [h[".text address"] - h[".rodata address"] for h in seen]
+            rest = len(ra) == len(rb) and all(ra[i:i + 16] == rb[i:i + 16] and ra[i + 24:i + 64] == rb[i + 24:i + 64] for i in range(0, len(ra), 64))
+            moved = {int.from_bytes(rb[i + 16:i + 24], "little") - int.from_bytes(ra[i + 16:i + 24], "little") for i in range(0, min(len(ra), len(rb)), 64)}
+            if rest and moved == {gap[1] - gap[0]}:
+                print(f"  .rodata: {len(ra) // 64} kernel descriptors, each identical apart from its offset to the code, {gap[1] - gap[0]:+d} B in all "
+                      f"of them: the distance from .rodata to .text changed by as much (section layout; no instruction, no kernel setting)")
+                print("IDENTICAL instructions; .rodata differs by section layout only")
+                sys.exit(1)
         print("IDENTICAL device code" if whole else "device code differs in the kernels listed above")
         sys.exit(0 if whole else 1)
