@@ -264,6 +264,9 @@ PROBE_OPS = {
     "sincos_small": (24, ("sincos_small",), 1, 4, True),
     "fast_rcp": (25, ("fast_rcp",), 1, 2, False),
     "ls_point": (26, ("ls_point",), 4, 1, False),
+    "wave_scan_suffix_incl_masked": (27, ("wave_scan_suffix_incl_masked", "wave_suffix_fix_rows_masked"), 1, 1, True),
+    "wave_scan_suffix_incl2_masked": (28, ("wave_scan_suffix_incl2_masked",), 2, 2, True),
+    "wave_suffix_fix_rows_masked": (29, ("wave_suffix_fix_rows_masked",), 1, 1, True),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -605,6 +605,15 @@ __global__ __launch_bounds__(256) void probe_kernel(const T* __restrict__ in, T*
         o1 = T(1) / x0;
     } else if constexpr (OP == NMPC_PROBE_LS_POINT) {
         o0 = nmpc::ls_point(x0, x1, x2, x3);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SCAN_SUFFIX_INCL_MASKED) {
+        if constexpr (sizeof(T) == 4) o0 = nmpc::wave_scan_suffix_incl_masked(x0);
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SCAN_SUFFIX_INCL2_MASKED) {
+        if constexpr (sizeof(T) == 4) {
+            o0 = x0, o1 = x1;
+            nmpc::wave_scan_suffix_incl2_masked(o0, o1);
+        }
+    } else if constexpr (OP == NMPC_PROBE_WAVE_SUFFIX_FIX_ROWS_MASKED) {
+        if constexpr (sizeof(T) == 4) o0 = nmpc::wave_suffix_fix_rows_masked(x0);
     }
     T* dst = out + (size_t)wave * (6 * 64) + lane;
     dst[0] = o0, dst[64] = o1, dst[128] = o2, dst[192] = o3, dst[256] = o4, dst[320] = o5;
@@ -2106,8 +2115,8 @@ int probe(nmpc_handle_s* h, int op, int block_threads, int n_waves, const T* in,
 {
     // (the arguments before the handle: every refusal below needs no device)
     if (op < 0 || op >= NMPC_PROBE_N_OPS) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: unknown op %d (0 .. %d)", op, NMPC_PROBE_N_OPS - 1);
-    if (sizeof(T) == 8 && (op == NMPC_PROBE_SINCOS_MEDIUM || op == NMPC_PROBE_SINCOS_SMALL))
-        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: unknown op %d for f64 (sincos_medium / sincos_small are float only)", op);
+    if (sizeof(T) == 8 && (op == NMPC_PROBE_SINCOS_MEDIUM || op == NMPC_PROBE_SINCOS_SMALL || op >= NMPC_PROBE_WAVE_SCAN_SUFFIX_INCL_MASKED))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: unknown op %d for f64 (sincos_medium / sincos_small and the masked-row scans are float only)", op);
     if (block_threads != 64 && block_threads != 128 && block_threads != 256)
         return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: block_threads %d is not 64, 128 or 256", block_threads);
     if (n_waves < 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_probe: negative n_waves %d", n_waves);

@@ -236,6 +236,63 @@ __device__ __forceinline__ void wave_scan_suffix_incl2(float& x, float& y)
     x = wave_suffix_fix_rows(x);
     y = wave_suffix_fix_rows(y);
 }
+// The cross-row step as three masked-row adds (float): the row totals t1, t2, t3 (lanes 16, 32, 48) into scalars, the three
+// addends t3, t2 + t3, t1 + (t2 + t3) formed once in wave-uniform vector registers -- the select tree's own candidates --
+// and each added to ITS row by a v_add_f32_dpp with the identity permutation and one row enabled: 10 instructions for the
+// select tree's 15, no lane id, no compare, no select.
+// Wait states (the compiler does not look into an asm block; gfx90a and later): a VALU write of a VGPR -> v_readlane of it:
+// 1 (the s_nop 0 in front: x comes from the last in-row step); v_readlane's SGPR -> a VALU read of it: 2; a VALU write of a
+// VGPR -> a DPP read of it: 2. The DPP operand is the addend, never x, and every scalar and addend is used three
+// instructions after it is written, so nothing else is padded.
+// Same operands, same association in rows 0..2. Row 3 is left alone where wave_suffix_fix_rows adds 0.0: that differs
+// in one case only, an in-row suffix of -0.0 (x + 0.0 = +0.0). Every lane of the row but its first has added a 0.0 from
+// past the end of the row on the way, so that is lane 48 with -0.0 in ALL of lanes 48..63: it keeps -0.0 here. A caller
+// with +0.0 in any lane of row 3 never sees it. (Which NaN's payload survives NaN + NaN follows the operand order, which
+// neither form promises.)
+#define NMPC_ROW_ADD(x, c, mask) "v_add_f32_dpp " x ", " c ", " x " quad_perm:[0,1,2,3] row_mask:" mask " bank_mask:0xf\n\t"
+__device__ __forceinline__ float wave_suffix_fix_rows_masked(float x)
+{
+    int s1, s2, s3;
+    float c3, c23, c123;
+    asm("s_nop 0\n\t"
+        "v_readlane_b32 %3, %0, 48\n\tv_readlane_b32 %2, %0, 32\n\tv_readlane_b32 %1, %0, 16\n\t"
+        "v_mov_b32 %4, %3\n\tv_add_f32 %5, %2, %4\n\tv_add_f32 %6, %1, %5\n\t"
+        NMPC_ROW_ADD("%0", "%4", "0x4") NMPC_ROW_ADD("%0", "%5", "0x2") NMPC_ROW_ADD("%0", "%6", "0x1")
+        : "+v"(x), "=&s"(s1), "=&s"(s2), "=&s"(s3), "=&v"(c3), "=&v"(c23), "=&v"(c123));
+    return x;
+}
+__device__ __forceinline__ float wave_scan_suffix_incl_masked(float x)
+{
+    x += dpp_mov<0x100 + 1, 0xf, 0xf, true>(0.0f, x);
+    x += dpp_mov<0x100 + 2, 0xf, 0xf, true>(0.0f, x);
+    x += dpp_mov<0x100 + 4, 0xf, 0xf, true>(0.0f, x);
+    x += dpp_mov<0x100 + 8, 0xf, 0xf, true>(0.0f, x);
+    return wave_suffix_fix_rows_masked(x);
+}
+// two suffix sums with interleaved chains (every distance above only grows)
+__device__ __forceinline__ void wave_scan_suffix_incl2_masked(float& x, float& y)
+{
+    x += dpp_mov<0x100 + 1, 0xf, 0xf, true>(0.0f, x);
+    y += dpp_mov<0x100 + 1, 0xf, 0xf, true>(0.0f, y);
+    x += dpp_mov<0x100 + 2, 0xf, 0xf, true>(0.0f, x);
+    y += dpp_mov<0x100 + 2, 0xf, 0xf, true>(0.0f, y);
+    x += dpp_mov<0x100 + 4, 0xf, 0xf, true>(0.0f, x);
+    y += dpp_mov<0x100 + 4, 0xf, 0xf, true>(0.0f, y);
+    x += dpp_mov<0x100 + 8, 0xf, 0xf, true>(0.0f, x);
+    y += dpp_mov<0x100 + 8, 0xf, 0xf, true>(0.0f, y);
+    int sx1, sx2, sx3, sy1, sy2, sy3;
+    float cx3, cx23, cx123, cy3, cy23, cy123;
+    asm("s_nop 0\n\t"
+        "v_readlane_b32 %4, %0, 48\n\tv_readlane_b32 %7, %1, 48\n\tv_readlane_b32 %3, %0, 32\n\tv_readlane_b32 %6, %1, 32\n\t"
+        "v_readlane_b32 %2, %0, 16\n\tv_readlane_b32 %5, %1, 16\n\t"
+        "v_mov_b32 %8, %4\n\tv_mov_b32 %11, %7\n\tv_add_f32 %9, %3, %8\n\tv_add_f32 %12, %6, %11\n\t"
+        "v_add_f32 %10, %2, %9\n\tv_add_f32 %13, %5, %12\n\t"
+        NMPC_ROW_ADD("%0", "%8", "0x4") NMPC_ROW_ADD("%1", "%11", "0x4") NMPC_ROW_ADD("%0", "%9", "0x2")
+        NMPC_ROW_ADD("%1", "%12", "0x2") NMPC_ROW_ADD("%0", "%10", "0x1") NMPC_ROW_ADD("%1", "%13", "0x1")
+        : "+v"(x), "+v"(y), "=&s"(sx1), "=&s"(sx2), "=&s"(sx3), "=&s"(sy1), "=&s"(sy2), "=&s"(sy3), "=&v"(cx3), "=&v"(cx23),
+          "=&v"(cx123), "=&v"(cy3), "=&v"(cy23), "=&v"(cy123));
+}
+#undef NMPC_ROW_ADD
 __device__ __forceinline__ double wave_scan_suffix_incl(double x)
 {
     x += dpp_mov<0x100 + 1, 0xf, 0xf, true>(0.0, x); // row_shl:n = 0x100 + n
@@ -351,6 +408,11 @@ __device__ __forceinline__ T wave_shift_down(T x)
     for (int s = 0; s < S; ++s) x = dpp_mov<DPP_WAVE_SHL1, 0xf, 0xf, true>(T(0), x);
     return x;
 }
+
+// (A shift by S lanes as one ds_bpermute_b32 -- address 4 * lane -+ 4 * S in the offset field, the zero fill put back by a
+//  select -- was built and measured in the evaluation and is not kept, HISTORY.md "Lane moves". Two things it needs: full
+//  EXEC, a lane that is masked off being read as 0 by the others, while the compiler moves the read under the select's mask
+//  unless its result is consumed in every lane first (an empty asm volatile on it); and a wait for every LDS read in flight.)
 
 // ---- shuffle-based reference versions (used only by the device self-test) ---------------------------------
 template <typename T>

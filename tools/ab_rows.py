@@ -46,7 +46,7 @@ def plain_bench(args):
            "A": {"lib": os.path.basename(libs[0]), "runs": series[libs[0]], "median_solves_per_s": statistics.median(a)},
            "B": {"lib": os.path.basename(libs[1]), "runs": series[libs[1]], "median_solves_per_s": statistics.median(b)},
            "ratio_B_over_A_of_medians": statistics.median(b) / statistics.median(a),
-           "A_spread_rel": (max(a) - min(a)) / statistics.median(a),
+           "A_spread_rel": (max(a) - min(a)) / statistics.median(a), "B_spread_rel": (max(b) - min(b)) / statistics.median(b),
            "every_B_run_faster_than_every_A_run": min(b) > max(a), "every_B_run_slower_than_every_A_run": max(b) < min(a)}
     print(json.dumps(res))
     if out:
