@@ -166,6 +166,12 @@ class NmpcMmpBlockArgs(C.Structure):
                 [("slope_mid", C.c_float), ("slope_out", C.c_float), ("out", C.c_void_p)])
 
 
+class NmpcMmpBlockF16Args(C.Structure):
+    """Mirror of ``struct nmpc_mmp_block_f16_args`` (device pointers): the fields of ``NmpcMmpBlockArgs`` (no stride), with ``w1``,
+    ``w2`` and ``wd`` the packed binary16 fragments of ``mmp_stem.pack_block1_f16`` (aligned to 16 bytes)."""
+    _fields_ = NmpcMmpBlockArgs._fields_
+
+
 class NmpcMmpBlock2Args(C.Structure):
     """Mirror of ``struct nmpc_mmp_block2_args`` (device pointers): one residual block of the network's layer2, ``x`` [M, Cin, H, W]
     -> ``out`` [M, 32, H2, W2] with ``H2 = (H - 1) // stride + 1``; the fields of ``NmpcMmpBlockArgs``, then ``stride`` (1 or 2, of
@@ -228,7 +234,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_dwa_step_lists_f32", "nmpc_dwa_step_lists_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
     "nmpc_mmp_block2_f32", "nmpc_mmp_block2_f16", "nmpc_mmp_block3_f32", "nmpc_mmp_block3_f16", "nmpc_mmp_block4_f32", "nmpc_mmp_block4_f16", "nmpc_mmp_head_f32",
-    "nmpc_mmp_block2_f16_io", "nmpc_mmp_block3_f16_io", "nmpc_mmp_block4_f16_io",
+    "nmpc_mmp_block2_f16_io", "nmpc_mmp_block3_f16_io", "nmpc_mmp_block4_f16_io", "nmpc_mmp_block_f16", "nmpc_mmp_block_f16_io",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
     "nmpc_last_error",
 )
@@ -331,6 +337,8 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     lib.nmpc_mmp_block3_f16.argtypes = [vp, C.POINTER(NmpcMmpBlock3F16Args)]
     lib.nmpc_mmp_block4_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock4Args)]
     lib.nmpc_mmp_block4_f16.argtypes = [vp, C.POINTER(NmpcMmpBlock4F16Args)]
+    lib.nmpc_mmp_block_f16.argtypes = [vp, C.POINTER(NmpcMmpBlockF16Args)]
+    lib.nmpc_mmp_block_f16_io.argtypes = [vp, C.POINTER(NmpcMmpBlockF16Args), i32, i32]
     lib.nmpc_mmp_block2_f16_io.argtypes = [vp, C.POINTER(NmpcMmpBlock2F16Args), i32, i32]
     lib.nmpc_mmp_block3_f16_io.argtypes = [vp, C.POINTER(NmpcMmpBlock3F16Args), i32, i32]
     lib.nmpc_mmp_block4_f16_io.argtypes = [vp, C.POINTER(NmpcMmpBlock4F16Args), i32, i32]
@@ -585,6 +593,15 @@ class Handle:
         """``nmpc_mmp_block3_f32``: one fused residual block of the network's layer3 (as ``mmp_block2``, at 64 output channels),
         ``out[M, 64, H2, W2]`` from ``x[M, Cin, H, W]``, float32 under both dtypes, one launch enqueued on the handle's stream."""
         _check(self._lib.nmpc_mmp_block3_f32(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_block_f16(self, args: "NmpcMmpBlockF16Args"):
+        """``nmpc_mmp_block_f16``: the block of ``mmp_block`` (layer1) with binary16 MFMA operands and float32 accumulation (the rounding
+        rule: include/nmpc_hip.h), on the packed weights of ``mmp_stem.pack_block1_f16``; ``x`` and ``out`` stay float32."""
+        _check(self._lib.nmpc_mmp_block_f16(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_block_f16_io(self, args: "NmpcMmpBlockF16Args", x_f16: int, out_f16: int):
+        """``nmpc_mmp_block_f16_io``: as ``mmp_block2_f16_io``, for ``mmp_block_f16``."""
+        _check(self._lib.nmpc_mmp_block_f16_io(self._h, C.byref(args) if args is not None else None, x_f16, out_f16))
 
     def mmp_block2_f16(self, args: "NmpcMmpBlock2F16Args"):
         """``nmpc_mmp_block2_f16``: the block of ``mmp_block2`` with binary16 MFMA operands and float32 accumulation (the rounding

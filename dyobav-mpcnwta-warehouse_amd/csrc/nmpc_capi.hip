@@ -30,6 +30,7 @@
 #include "nmpc_mmp_stem.h"
 #include "nmpc_mmp_block.h"
 #include "nmpc_mmp_block2.h"
+#include "nmpc_mmp_block1_f16.h"
 #include "nmpc_mmp_block2_f16.h"
 #include "nmpc_mmp_block3.h"
 #include "nmpc_mmp_block3_f16.h"
@@ -1867,6 +1868,33 @@ struct MmpLayer4F16 : MmpLayer4 {
     static constexpr void (*kernels[3])(Params) = {nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 2, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 1, true>, nmpc::mmp_blkh_kernel<nmpc::MmpBlock4HGeom, 1, false>};
 };
 
+// layer1 with binary16 MFMA operands (csrc/nmpc_mmp_block1_f16.h): 16 channels, tiles of 15 x 28 outputs (reach 3), no stride --
+// the entry hands its struct on with stride = 1 -- and so no kernel <stride 2, .>; the geometry follows the projection
+struct MmpLayer1F16 {
+    struct Args : nmpc_mmp_block_f16_args {
+        int32_t stride;
+    };
+    using Params = nmpc::MmpBlock1HParams;
+    template <bool PROJ, bool XH, bool OH>
+    using G = nmpc::MmpBlkhIo<nmpc::MmpBlock1HGeom<PROJ>, XH, OH>;
+    struct Io {
+        static constexpr void (*table[3][3])(Params) = {
+            {nullptr, nmpc::mmp_blkh_kernel<G<true, false, true>, 1, true>, nmpc::mmp_blkh_kernel<G<false, false, true>, 1, false>},
+            {nullptr, nmpc::mmp_blkh_kernel<G<true, true, false>, 1, true>, nmpc::mmp_blkh_kernel<G<false, true, false>, 1, false>},
+            {nullptr, nmpc::mmp_blkh_kernel<G<true, true, true>, 1, true>, nmpc::mmp_blkh_kernel<G<false, true, true>, 1, false>}};
+    };
+    static constexpr const char* name = "nmpc_mmp_block_f16";
+    static constexpr const char* io_name = "nmpc_mmp_block_f16_io";
+    static constexpr int C = nmpc::kBlkC, threads = nmpc::kBlkThreads, packed_align = 16;
+    static constexpr void (*kernels[3])(Params) = {nullptr, nmpc::mmp_blkh_kernel<nmpc::MmpBlock1HGeom<true>, 1, true>,
+                                                   nmpc::mmp_blkh_kernel<nmpc::MmpBlock1HGeom<false>, 1, false>};
+    template <typename P>
+    static void tile(P& p, long long& ty, long long& tx)
+    {
+        ty = ((long long)p.H2 + nmpc::kBlkTH - 1) / nmpc::kBlkTH, tx = ((long long)p.W2 + nmpc::kBlkTW - 1) / nmpc::kBlkTW;
+    }
+};
+
 // IO: the entry nmpc_mmp_blockN_f16_io, whose x (x_f16 = 1) and out (out_f16 = 1) are binary16 in the octet form
 template <typename Stage, bool IO = false>
 int mmp_strided(nmpc_handle_s* h, const typename Stage::Args* g, int32_t x_f16 = 0, int32_t out_f16 = 0)
@@ -2483,6 +2511,14 @@ int nmpc_mmp_stem_f32(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_s
 int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<double>(h, a); }
 int nmpc_mmp_block_f32(nmpc_handle h, const nmpc_mmp_block_args* a) { return mmp_block(h, a); }
 int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return mmp_strided<MmpLayer2>(h, a); }
+static int mmp_block_f16(nmpc_handle_s* h, const nmpc_mmp_block_f16_args* a, int32_t x_f16, int32_t out_f16, bool io)
+{
+    MmpLayer1F16::Args g;
+    if (a) static_cast<nmpc_mmp_block_f16_args&>(g) = *a, g.stride = 1;
+    return io ? mmp_strided<MmpLayer1F16, true>(h, a ? &g : nullptr, x_f16, out_f16) : mmp_strided<MmpLayer1F16>(h, a ? &g : nullptr);
+}
+int nmpc_mmp_block_f16(nmpc_handle h, const nmpc_mmp_block_f16_args* a) { return mmp_block_f16(h, a, 0, 0, false); }
+int nmpc_mmp_block_f16_io(nmpc_handle h, const nmpc_mmp_block_f16_args* a, int32_t x_f16, int32_t out_f16) { return mmp_block_f16(h, a, x_f16, out_f16, true); }
 int nmpc_mmp_block2_f16(nmpc_handle h, const nmpc_mmp_block2_f16_args* a) { return mmp_strided<MmpLayer2F16>(h, a); }
 int nmpc_mmp_block2_f16_io(nmpc_handle h, const nmpc_mmp_block2_f16_args* a, int32_t x_f16, int32_t out_f16) { return mmp_strided<MmpLayer2F16, true>(h, a, x_f16, out_f16); }
 int nmpc_mmp_block3_f32(nmpc_handle h, const nmpc_mmp_block3_args* a) { return mmp_strided<MmpLayer3>(h, a); }

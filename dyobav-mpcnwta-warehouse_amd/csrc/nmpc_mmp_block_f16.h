@@ -1,7 +1,8 @@
 // nmpc_mmp_block_f16.h -- the residual block of the multi-hypothesis predictor's network (resnet34.layer2 .. layer4: two 3 x 3
 // convolutions with folded affines and LeakyReLUs, stride 1 or 2 on the first, projection or identity) with binary16 MFMA
 // OPERANDS and float32 everything else, stated ONCE for every stage (predictor `mmp`, opt-in per stage on top of the opt-in fused
-// float32 stages: MmpFrontEnd(half=...) / MmpFrontEnd(operands=...)). A stage is a GEOMETRY G: nmpc_mmp_block2_f16.h (32 output
+// float32 stages: MmpFrontEnd(half=...) / MmpFrontEnd(operands=...) / MmpFrontEnd(precision=...)). A stage is a GEOMETRY G:
+// nmpc_mmp_block1_f16.h (16 output channels: layer1, stride 1 only, after nmpc_mmp_block.h), nmpc_mmp_block2_f16.h (32 output
 // channels), nmpc_mmp_block3_f16.h (64) and nmpc_mmp_block4_f16.h (128) hold one each, with the stage's Params, its decisions, its
 // model and its measured figures; the block itself, its strides, its padding and the zero ring of m are defined by the float32
 // sibling nmpc_mmp_block_f32.h (mmp_blkf_kernel) and its geometries in nmpc_mmp_block{2,3,4}.h, whose flat domains, pixel groups and,
@@ -28,7 +29,8 @@
 //   B: lane l holds tile[ci = 32 kb + 8 (l >> 4) + j][q + off(tap)], q = q0 + (l & 15)                   (4 VGPRs, one ds_read_b128)
 //   D: 4 VGPRs: channel 16 g + 4 (l >> 4) + r in register r, pixel q0 + (l & 15)                         (as the f32 form)
 // C output channels are C / 16 A groups g, of which a wave holds G::NH from G::first_a(wave) on; C channels of m are C / 32 K
-// blocks kb per tap. A Cin that is no multiple of 32 has zeros in the last K block (staged zeros in B, packed zeros in A). A
+// blocks kb per tap -- C = 16 is half of ONE K block: the lane groups l >> 4 in {2, 3} of the second convolution feed zeros
+// against the packed zeros of w2. A Cin that is no multiple of 32 has zeros in the last K block (staged zeros in B, packed zeros in A). A
 // chunk of fewer than 32 channels (G::ck(STRIDE) = 16: layer2's strided block) is one HALF of a K block: the chunk c0 is half
 // (c0 >> 4) & 1 of K block c0 >> 5, the lane groups l >> 4 of that half read its two octets and the other two feed zeros.
 //
@@ -160,8 +162,12 @@ __global__ __launch_bounds__(G::Threads, G::min_wg(STRIDE)) void mmp_blkh_kernel
     constexpr int NIT = NPL * G::Q;                    // 16-byte items per chunk
     constexpr int PRE = (NIT + G::Threads - 1) / G::Threads; // items a thread stages per chunk
     constexpr int NA = G::C / 16, MP = G::C / 8;       // A groups; planes of m
+    constexpr int KB2 = (G::C + 31) / 32;              // K blocks of the second convolution
+    constexpr bool MHALF = G::C % 32 != 0;             // m is half a K block (C = 16): the lane groups l >> 4 in {2, 3} feed zeros
     constexpr int S = G::S, PL = G::PL, SH = G::SH, NH = G::NH;
-    constexpr bool ROWS = S % 16 == 0;                 // a pixel group lies in ONE row of the domain: a group of out has no row outside the tile
+    // a pixel group lies in ONE row of the domain and the waves' NO slots are exactly the tile's groups: a group of out has no row
+    // outside the tile (layer1's 30 groups leave two of 32 slots to groups of m alone, which the row test then drops)
+    constexpr bool ROWS = S % 16 == 0 && G::TH * (S / 16) == G::NO * (G::Threads / 64) * NH / NA;
     static_assert(CK % 32 == 0 || CK == 16, "a chunk is K blocks, or half of one");
     static_assert(NPL >= MP, "m does not fit over the chunk");
     __shared__ __attribute__((aligned(16))) _Float16 lds[NPL * PL * 8]; // [plane][slot][8]; m over the last chunk
@@ -293,18 +299,19 @@ __global__ __launch_bounds__(G::Threads, G::min_wg(STRIDE)) void mmp_blkh_kernel
     for (int i = 0; i < G::NO; ++i)
 #pragma unroll
         for (int h = 0; h < NH; ++h) acc[i][h] = zero;
-    for (int kb = 0; kb < G::C / 32; ++kb) {
+    const bool feeds2 = !MHALF || k4 < 2;
+    for (int kb = 0; kb < KB2; ++kb) {
         const uint16_t* wk = p.w2 + ((size_t)kb * NA + hb) * 512 + lane * 8;
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int off = (t / 3 - 1) * S + (t % 3 - 1);
             mmp_blkh_h8 a[NH];
 #pragma unroll
-            for (int h = 0; h < NH; ++h) a[h] = *reinterpret_cast<const mmp_blkh_h8*>(wk + ((size_t)t * (G::C / 32) * NA + h) * 512);
+            for (int h = 0; h < NH; ++h) a[h] = *reinterpret_cast<const mmp_blkh_h8*>(wk + ((size_t)t * KB2 * NA + h) * 512);
             const _Float16* mb = lds + 8 * ((4 * kb + k4) * PL + off + SH);
 #pragma unroll
             for (int i = 0; i < G::NO; ++i) {
-                const mmp_blkh_h8 b = *reinterpret_cast<const mmp_blkh_h8*>(mb + 8 * gq[i]);
+                const mmp_blkh_h8 b = feeds2 ? *reinterpret_cast<const mmp_blkh_h8*>(mb + 8 * gq[i]) : zero8;
 #pragma unroll
                 for (int h = 0; h < NH; ++h) acc[i][h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[h], b, acc[i][h], 0, 0, 0);
             }

@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
-from .mmp_stem import STAGES, block2_plane, check_head, check_spec, check_stage, head_features, pack_block2_f16, pack_block3_f16, pack_block4_f16
+from .mmp_stem import STAGES, block2_plane, check_head, check_spec, check_stage, head_features, pack_block1_f16, pack_block2_f16, pack_block3_f16, pack_block4_f16
 
 _BLOCK_ARRAYS = ("w1", "s1", "b1", "w2", "s2", "b2", "wd", "sd", "bd")
 _HEAD_ARRAYS = ("w1", "c1", "w2", "c2")
@@ -28,7 +28,9 @@ _HALF = {"layer3": (pack_block3_f16, _capi.NmpcMmpBlock3F16Args, "mmp_block3_f16
 _F16 = {"layer2": (pack_block2_f16, _capi.NmpcMmpBlock2F16Args, "mmp_block2_f16"), **_HALF}
 _OPERANDS = ("f32", "f16")
 # ``activations="f16"``: the Handle method of such a stage that takes the form of x and of out in memory beside the struct
-_F16_IO = {name: launch + "_io" for name, (_, _, launch) in _F16.items()}
+# ``precision="f16"``: every stage, layer1 included, which ``operands`` and ``half`` keep refusing
+_F16_ALL = {"layer1": (pack_block1_f16, _capi.NmpcMmpBlockF16Args, "mmp_block_f16"), **_F16}
+_F16_IO = {name: launch + "_io" for name, (_, _, launch) in _F16_ALL.items()}
 # what each keyword behind ``stem`` needs in front of it, as ``check_specs`` says it
 _NEEDS = (("the blocks run on the fused first layer's output",)
           + tuple(f"the blocks of {st.layer} run on the fused {prev.layer}'s output" for prev, st in zip(STAGES, STAGES[1:]))
@@ -64,7 +66,7 @@ class Stage:
 class MmpFrontEnd:
     def __init__(self, handle: _capi.Handle, dtype, device, Hm: int, Wm: int, n_off: int, transform, rescale: float, sigma: float,
                  ref_image, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=(),
-                 operands=None, activations=None):
+                 operands=None, activations=None, precision=None):
         """``dtype``: the element type of ``hist``; ``ref_image``: the float32 label image ``[Hm, Wm]`` on ``device``; ``transform``: the
         :class:`.snap.WorldTransform` between map pixels and the world of ``hist``; ``stem``: a :class:`.mmp_stem.StemSpec`; ``blocks``
         .. ``blocks4``: the specs of ``layer1`` .. ``layer4`` (``mmp_stem.STAGES``), each needing the one before it; ``head`` (needs
@@ -90,6 +92,13 @@ class MmpFrontEnd:
         what a float32 stage, the head or the caller's network reads. A binary16 tensor lies in the same two buffers of its stage, in
         the front half of the float slot; the placement rule and ``bytes_per_item`` do not change: the halved footprint is not
         exploited. ``self.activations`` is ``"f32"`` or ``"f16"``; a stage's ``io`` holds the two flags of each of its blocks.
+        ``precision``: the switch for the whole network. ``None`` or ``"f32"`` changes no bit and no launch. ``"f16"`` (needs
+        ``blocks``): EVERY stage given runs on f16 operands, layer1 included (``nmpc_mmp_block_f16``, csrc/nmpc_mmp_block1_f16.h, the
+        same rule) -- which ``operands`` and ``half`` keep refusing in their own words --, together with ``activations="f16"``: every
+        tensor between two blocks is binary16 in the octet form, layer1's own and the border to layer2 included; layer1's first block
+        still reads the fill's float32 output, the last block still writes float32 NCHW. ``self.operands`` then reports ``"f16"`` for
+        every stage given and ``self.activations`` ``"f16"``. Refused beside an ``operands`` entry ``"f32"`` for a stage given or
+        ``activations="f32"``; accepted beside ``half`` / ``operands`` / ``activations`` that agree (``check_precision``).
 
         Where a stage's two buffers lie is one rule: the fill's output (the stem's, ``[C, Hp, Wp]`` per row) is idle once layer1's
         first block has read it, so the buffers of the stages behind layer1 are laid INSIDE it one behind the other, at a running
@@ -102,7 +111,7 @@ class MmpFrontEnd:
         stem, head = specs[0], specs[-1]
         self.operands = self.check_operands(operands, half, specs)
         self.half = self.check_half(half, specs)
-        self.activations = self.check_activations(activations, self.operands)
+        self.operands, self.activations = self.check_precision(precision, operands, half, activations, specs)
         self.h, self.dt, self.dev, self.n_off = handle, np.dtype(dtype), device, int(n_off)
         bits = lambda a: a.view(np.int16) if a.dtype == np.uint16 else a          # (packed binary16 bit patterns travel as int16)
         dev = lambda spec, names: spec._replace(**{n: torch.as_tensor(bits(getattr(spec, n)), device=device) for n in names if getattr(spec, n) is not None})
@@ -123,7 +132,7 @@ class MmpFrontEnd:
         self.stages, offset, inside = [], 0, True           # offset: floats of a fill row given away so far; inside: nothing overflowed yet
         for table, (Args, launch), given in zip(STAGES, _DEVICE, specs[1:-1]):
             if given is not None and self.operands[table.layer] == "f16":
-                pack, Args, launch = _F16[table.layer]
+                pack, Args, launch = _F16_ALL[table.layer]
                 cins, given = tuple(int(b.w1.shape[1]) for b in given), tuple(pack(b) for b in given)
             elif given is not None:
                 cins = tuple(int(b.w1.shape[1]) for b in given)
@@ -223,6 +232,30 @@ class MmpFrontEnd:
         if activations == "f16" and "f16" not in operands.values():
             raise ValueError(f"{prefix}activations: 'f16' needs a stage on f16 operands ({prefix}operands)")
         return activations or "f32"
+
+    @staticmethod
+    def check_precision(precision, operands, half, activations, specs, prefix: str = "") -> tuple:
+        """``(operands, activations)`` as ``check_operands`` and ``check_activations`` return them, under ``precision``: ``None`` or
+        ``"f32"`` changes neither; ``"f16"`` makes every stage given ``"f16"``, layer1 included, and the activations ``"f16"``.
+        ``operands``, ``half`` and ``activations`` are the caller's own values and go through ``check_operands`` and
+        ``check_activations`` first, so their refusals speak first and unchanged (``activations="f16"`` counts ``precision="f16"`` as
+        the stage on f16 operands it needs). One sentence per refusal: a value that is none of the three; ``"f16"`` without
+        ``blocks``; ``"f16"`` beside an ``operands`` entry ``"f32"`` of a stage given; ``"f16"`` beside ``activations="f32"``."""
+        ops = MmpFrontEnd.check_operands(operands, half, specs, prefix)
+        whole = isinstance(precision, str) and precision == "f16"
+        act = MmpFrontEnd.check_activations(activations, {name: "f16" for name in ops} if whole else ops, prefix)
+        if precision is not None and not (isinstance(precision, str) and precision in _OPERANDS):
+            raise ValueError(f"{prefix}precision: {precision!r} is none of None, 'f32' and 'f16'")
+        if not whole:
+            return ops, act
+        if specs[1] is None:
+            raise ValueError(f"{prefix}precision: 'f16' needs {prefix}blocks (the whole network on f16 operands begins with layer1)")
+        for name, value in (operands or {}).items():
+            if value == "f32" and name in ops:
+                raise ValueError(f"{prefix}precision: 'f16', but {prefix}operands says {name!r} is 'f32'")
+        if activations == "f32":
+            raise ValueError(f"{prefix}precision: 'f16', but {prefix}activations is 'f32'")
+        return {name: "f16" for name in ops}, "f16"
 
     def stage(self, name: str):
         """The :class:`Stage` called ``name`` (``"layer1"`` ..), or ``None`` if its specs were not given."""

@@ -38,7 +38,7 @@ OBSV_LEN = 5        # config.obsv_len of the reference's network configurations
 
 class MmpInterface:
     def __init__(self, network: Optional[Callable] = None, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=(),
-                 operands=None, activations=None):
+                 operands=None, activations=None, precision=None):
         """``stem``: a :class:`.mmp_stem.StemSpec` = the network's first layer, computed on the device without the input stack
         (``nmpc_mmp_stem_f64``); ``network`` is then the trunk behind it, a callable on ``[M, C, Hp, Wp]``. ``blocks`` (needs
         ``stem``): the :class:`.mmp_stem.BlockSpec` s of the residual stage behind the stem (``mmp_stem.split_network_layer1``),
@@ -59,7 +59,9 @@ class MmpInterface:
         the same rule), ``"layer3"`` and ``"layer4"``, ``"f32"`` for any stage; ``None``, ``{}`` or all ``"f32"`` changes no bit
         (``MmpFrontEnd.check_operands``). ``activations``: ``None`` or ``"f32"`` changes no bit; ``"f16"`` (needs a stage on f16
         operands) keeps every tensor between two blocks on f16 operands in memory as binary16 (``MmpFrontEnd``,
-        ``MmpFrontEnd.check_activations``)."""
+        ``MmpFrontEnd.check_activations``). ``precision``: ``None`` or ``"f32"`` changes no bit; ``"f16"`` (needs ``blocks``) runs every
+        stage given on f16 operands, layer1 included (``nmpc_mmp_block_f16``), with binary16 activations between all blocks
+        (``MmpFrontEnd.check_precision``)."""
         if head is not None and network is not None:
             raise TypeError("head is the network's end: network must be None with it")
         if head is None and not callable(network):
@@ -69,7 +71,9 @@ class MmpInterface:
         self._specs = MmpFrontEnd.check_specs(stem, blocks, blocks2=blocks2, blocks3=blocks3, blocks4=blocks4, head=head)
         self._operands = MmpFrontEnd.check_operands(operands, half, self._specs)
         self._half = MmpFrontEnd.check_half(half, self._specs)
-        self._activations = MmpFrontEnd.check_activations(activations, self._operands)
+        self._operands, self._activations = MmpFrontEnd.check_precision(precision, operands, half, activations, self._specs)
+        # (the front ends take the caller's own values: the checked operands name layer1, which ``operands`` refuses)
+        self._switches = dict(operands=None if operands is None else dict(operands), activations=activations, precision=precision)
         for name, spec in zip(SPEC_NAMES, self._specs):
             setattr(self, name, spec)
         self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)
@@ -118,8 +122,7 @@ class MmpInterface:
         key = (N, Hm, Wm, float(rescale))
         if key not in self._fronts:
             d_ref = torch.empty(Hm, Wm, dtype=torch.float32, device=d_hist.device)
-            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, *self._specs, half=self._half, operands=self._operands,
-                                            activations=self._activations)
+            self._fronts[key] = MmpFrontEnd(h, np.float64, d_hist.device, Hm, Wm, N, ident, rescale, SIGMA, d_ref, *self._specs, half=self._half, **self._switches)
             self._fronts[key].allocate(1)
         fe = self._fronts[key]
         fe.ref.copy_(torch.from_numpy(img))

@@ -406,10 +406,14 @@ def check_block4(spec) -> Block4Spec:
 #   zero where the input channel is >= Cin; w2 the same with Cin = C; wd [KB, C / 16, 64, 8] without the tap.
 # Layer2's strided block has 16 input channels, half a K block, the other half packed zeros: one layout for both strides. The scales,
 # the shifts, the slopes and the stride are the float32 spec's, unchanged.
+# Layer1 (``nmpc_mmp_block_f16``, csrc/nmpc_mmp_block1_f16.h) under the same rule: C = 16 is one group, ``w1 [9, KB, 1, 64, 8]``, ``w2 [9, 1, 1,
+# 64, 8]`` whose input channels 16 .. 31 (lanes 32 .. 63) are zeros -- the 16 channels of m are half a K block --, ``wd [KB, 1, 64, 8]``; the
+# spec has ``BlockSpec``'s fields (no stride).
+Block1F16Spec = NamedTuple("Block1F16Spec", list(BlockSpec.__annotations__.items()))
 Block2F16Spec = NamedTuple("Block2F16Spec", _STRIDED_FIELDS)
 Block3F16Spec = NamedTuple("Block3F16Spec", _STRIDED_FIELDS)
 Block4F16Spec = NamedTuple("Block4F16Spec", _STRIDED_FIELDS)
-_F16_SPECS = {BLOCK2_CHANNELS: Block2F16Spec, BLOCK3_CHANNELS: Block3F16Spec, BLOCK4_CHANNELS: Block4F16Spec}
+_F16_SPECS = {BLOCK_CHANNELS: Block1F16Spec, BLOCK2_CHANNELS: Block2F16Spec, BLOCK3_CHANNELS: Block3F16Spec, BLOCK4_CHANNELS: Block4F16Spec}
 F16_MAX = 65504.0
 
 
@@ -420,7 +424,7 @@ def round_f16(a) -> np.ndarray:
 
 
 def _pack_f16(w) -> np.ndarray:
-    """``[C, Cin, T]`` -> ``[T, KB, C // 16, 64, 8]`` uint16 in fragment order (``C`` = 32, 64 or 128 output channels: 2, 4 or 8 groups)."""
+    """``[C, Cin, T]`` -> ``[T, KB, C // 16, 64, 8]`` uint16 in fragment order (``C`` = 16, 32, 64 or 128 output channels: 1, 2, 4 or 8 groups)."""
     C, Cin, T = w.shape
     KB = (Cin + 31) // 32
     wp = np.zeros((C, 32 * KB, T), dtype=np.float16)
@@ -445,7 +449,7 @@ def _f16_stage(channels: int) -> "Stage":
 
 
 def pack_block_f16(spec, channels: Optional[int] = None):
-    """A stage's spec (:class:`Block2Spec`, :class:`Block3Spec`, :class:`Block4Spec`) -> its ``Block{2,3,4}F16Spec``: the three weight
+    """A stage's spec (:class:`BlockSpec`, :class:`Block2Spec`, :class:`Block3Spec`, :class:`Block4Spec`) -> its ``Block{1,2,3,4}F16Spec``: the three weight
     arrays rounded once (``round_f16``) and packed; everything else passed through. The stage is the one of ``channels`` output
     channels, by default the spec's own; ``ValueError`` for what that stage's checker refuses."""
     st = _f16_stage(np.shape(spec.w1)[0] if channels is None else channels)
@@ -465,10 +469,11 @@ def unpack_block_f16(packed, Cin: int):
 
 
 # the stages' own names: a spec of another stage is refused by this stage's checker, in its words
+pack_block1_f16 = functools.partial(pack_block_f16, channels=BLOCK_CHANNELS)
 pack_block2_f16 = functools.partial(pack_block_f16, channels=BLOCK2_CHANNELS)
 pack_block3_f16 = functools.partial(pack_block_f16, channels=BLOCK3_CHANNELS)
 pack_block4_f16 = functools.partial(pack_block_f16, channels=BLOCK4_CHANNELS)
-unpack_block2_f16 = unpack_block3_f16 = unpack_block4_f16 = unpack_block_f16
+unpack_block1_f16 = unpack_block2_f16 = unpack_block3_f16 = unpack_block4_f16 = unpack_block_f16
 
 
 def pack_activations_f16(x) -> np.ndarray:

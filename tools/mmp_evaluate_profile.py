@@ -54,9 +54,12 @@ them: ``mmp_half=("layer3", "layer4")`` against the same with ``mmp_operands={"l
 layer3 and layer4 on binary16 operands: ``mmp_activations="f32"`` (the parent's path) against ``"f16"``; the 13 launches alone per run
 and per block, then the loop; the record holds both arms' run-to-run spreads and whether the f16 arm is faster by more than the
 larger of them in every run.
+``--half-layer1``: the same protocol for layer1 on binary16 operands (``nmpc_mmp_block_f16``): ``parent`` -- layer2 .. layer4 on binary16
+operands with ``mmp_activations="f16"``, layer1 on float32 -- against ``mmp_precision="f16"``; the 16 launches alone per run and per block,
+then the loop; the record holds layer1's three launches and the stage of each run, the spreads and both merge conditions.
    usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]
           [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS] | --fused-layer4 [REPS] | --half-layer3 [REPS]
-           | --half-layer4 [REPS] | --half-layer2 [REPS] | --activations-f16 [REPS]]
+           | --half-layer4 [REPS] | --half-layer2 [REPS] | --activations-f16 [REPS] | --half-layer1 [REPS]]
           (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
@@ -924,13 +927,15 @@ def half_layer2_main(out_path, B, steps, dt, n_ped, K, reps):
         print(p, json.dumps({"all": (r["ms_median"], r["TFMAps_median"], r["GBps_median"])}))
 
 
-def activations_kernel_rate(ev, n_item, reps=10):
+def activations_kernel_rate(ev, n_item, reps=10, names=("layer2", "layer3", "layer4")):
     """The 13 launches of layer2, layer3 and layer4 of the evaluator's front end alone on the layer1 output of ``n_item`` pedestrians:
-    ms each and together (``run_block``: the launches only, nothing is decoded), and the bytes of x and out as they lie in memory."""
+    ms each and together (``run_block``: the launches only, nothing is decoded), and the bytes of x and out as they lie in memory.
+    ``names`` beginning with ``"layer1"``: all 16 launches on the fill's output (the later stages' buffers lie inside it, so behind
+    the first pass the first block reads what they left there: the time of a launch does not depend on the values)."""
     fe = ev.mmp_front
     rows = _fill(ev, n_item)().shape[0]
     fe.run_blocks(rows)
-    first, stages = len(fe.blocks), [fe.stage(n) for n in ("layer2", "layer3", "layer4")]
+    first, stages = (0 if names[0] == "layer1" else len(fe.blocks)), [fe.stage(n) for n in names]
     count = sum(len(st.args) for st in stages)
     run_all = lambda: [fe.run_block(first + i, rows) for i in range(count)]
     run_all()
@@ -1031,8 +1036,100 @@ def activations_f16_main(out_path, B, steps, dt, n_ped, K, reps):
                                           "chunk_pedestrians")}))
 
 
+def half_layer1_main(out_path, B, steps, dt, n_ped, K, reps):
+    """``--half-layer1``: the protocol of ``--half-layer2`` for layer1 on binary16 operands (``nmpc_mmp_block_f16``), reached by the
+    switch for the whole network. Both arms run the whole network on the device, alternated in one process: ``parent`` is layer2 ..
+    layer4 on binary16 operands with binary16 activations between them and layer1 on float32 (``mmp_operands`` + ``mmp_activations =
+    "f16"``: the fastest path without this kernel), ``f16`` is ``mmp_precision="f16"``. The 16 launches alone on one chunk per run and
+    per block, then the closed loop with events around every part. The criterion is the sibling records': layer1's three launches
+    faster in every run by more than the larger of the two arms' run-to-run spreads, the stage not slower by more than its own."""
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import split_network_whole
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    as_block = lambda b: SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)
+    L = list(net)
+    shaped = SimpleNamespace(resnet34=SimpleNamespace(stem=SimpleNamespace(conv1=L[0], pooling=L[1]), layer1=[as_block(b) for b in L[2:5]],
+                                                      layer2=[as_block(b) for b in L[5:9]], layer3=[as_block(b) for b in L[9:15]],
+                                                      layer4=[as_block(b) for b in L[15:18]], apool=L[18]), fc1=L[20], leaky=L[21], swarm=L[22])
+    spec, blocks, blocks2, blocks3, blocks4, head = split_network_whole(shaped)
+    head = head._replace(c2=head.c2 + np.float32(150.0))   # (the "+ 150" that puts the random network's hypotheses on the map)
+    whole = dict(network=None, mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, mmp_blocks3=blocks3, mmp_blocks4=blocks4, mmp_head=head)
+    paths = {"parent": dict(whole, mmp_operands={"layer2": "f16", "layer3": "f16", "layer4": "f16"}, mmp_activations="f16"),
+             "f16": dict(whole, mmp_precision="f16")}
+    layers = ("layer1", "layer2", "layer3", "layer4")
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rows_step = B * n_ped * nm.default_config_struct().N_hor
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage, the whole network on the device: layer2, "
+                   "layer3 and layer4 on binary16 operands with binary16 activations between them and layer1 on float32 (arm 'parent': "
+                   "nmpc_mmp_block_f32) against the whole network on binary16 operands from layer1 on (arm 'f16': mmp_precision = 'f16', "
+                   "nmpc_mmp_block_f16_io), alternated in one process; random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS, "fp32_peak_TFMAps": PEAK_TFMAS},
+           "model_of_the_f16_header_per_lock_step_ms": {"mfma_pipe_never_waits": 4.4, "activations_at_copy_rate": 10.0},
+           "chunk_pedestrians": {}, "kernels": {p: [] for p in paths}, "runs": {p: [] for p in paths}}
+    for _ in range(reps):                                   # the 16 launches alone, per arm, alternated (the first also warms up)
+        for path in paths:
+            ev = evaluator(path)
+            rec["chunk_pedestrians"][path] = ev.mmp_chunk
+            try:
+                rec["kernels"][path].append(activations_kernel_rate(ev, min(ev.mmp_chunk, B * n_ped), names=layers))
+                ev.run(max_steps=1)
+            finally:
+                ev.close()
+            r = rec["kernels"][path][-1]
+            print(path, json.dumps({"rows": r["rows"], "sixteen_launches_ms": r["ms_median"], "each": [b["ms_median"] for b in r["blocks"]]}), flush=True)
+            with open(out_path, "w") as f:
+                json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = ("input",) + layers + ("head",)
+    spread = lambda v: (max(v) - min(v)) / float(np.median(v))
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names}, stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    rec["stage_median_of_each_run_ms"] = {p: [float(np.median([s["stage_ms"] for s in run])) for run in rec["runs"][p]] for p in paths}
+    rec["layer1_median_of_each_run_ms"] = {p: [float(np.median([s["layer1"] for s in run])) for run in rec["runs"][p]] for p in paths}
+    rec["each_block_median_ms"] = {p: [float(np.median([r["blocks"][i]["ms_median"] for r in rec["kernels"][p]])) for i in range(16)] for p in paths}
+    rec["each_block_GBps_median"] = {p: [float(np.median([r["blocks"][i]["GBps_median"] for r in rec["kernels"][p]])) for i in range(16)] for p in paths}
+    rec["layer1_three_launches_of_each_run_ms"] = {p: [sum(b["ms_median"] for b in r["blocks"][:3]) for r in rec["kernels"][p]] for p in paths}
+    rec["layer1_three_launches_per_lock_step_ms"] = {p: float(np.median([sum(b["ms_median"] for b in r["blocks"][:3]) * rows_step / r["rows"]
+                                                                          for r in rec["kernels"][p]])) for p in paths}
+    three, stage = rec["layer1_three_launches_of_each_run_ms"], rec["stage_median_of_each_run_ms"]
+    rec["run_to_run_spread"] = {"layer1_three_launches": {p: spread(three[p]) for p in paths}, "stage": {p: spread(stage[p]) for p in paths}}
+    rec["f16_over_parent_layer1_three_launches_of_each_run"] = [a / b for a, b in zip(three["f16"], three["parent"])]
+    rec["f16_over_parent_stage_of_each_run"] = [a / b for a, b in zip(stage["f16"], stage["parent"])]
+    rec["margin"] = {"layer1_three_launches": max(rec["run_to_run_spread"]["layer1_three_launches"].values()), "stage": max(rec["run_to_run_spread"]["stage"].values())}
+    # the two conditions: layer1 faster in every run by more than the margin; the stage not slower by more than its margin
+    rec["conditions"] = {"layer1_faster_in_every_run": all(r < 1.0 - rec["margin"]["layer1_three_launches"] for r in rec["f16_over_parent_layer1_three_launches_of_each_run"]),
+                         "stage_not_slower": all(r <= 1.0 + rec["margin"]["stage"] for r in rec["f16_over_parent_stage_of_each_run"])}
+    rec["f16_layer1_over_mfma_model"] = rec["layer1_three_launches_per_lock_step_ms"]["f16"] * (20480 / rows_step) / 4.4
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "stage_median_of_each_run_ms", "layer1_median_of_each_run_ms", "each_block_median_ms",
+                                          "each_block_GBps_median", "layer1_three_launches_of_each_run_ms", "layer1_three_launches_per_lock_step_ms",
+                                          "run_to_run_spread", "f16_over_parent_layer1_three_launches_of_each_run", "f16_over_parent_stage_of_each_run",
+                                          "margin", "conditions", "f16_layer1_over_mfma_model", "chunk_pedestrians")}))
+
+
 def main():
-    for flag, run in (("--activations-f16", activations_f16_main), ("--half-layer2", half_layer2_main), ("--half-layer4", half_layer4_main), ("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+    for flag, run in (("--half-layer1", half_layer1_main), ("--activations-f16", activations_f16_main), ("--half-layer2", half_layer2_main), ("--half-layer4", half_layer4_main), ("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
         if flag in sys.argv:
             i = sys.argv.index(flag)
             reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
