@@ -62,6 +62,15 @@ def make_case(rng, axis_aligned=None):
     return lay, rows, P, U, Y, C
 
 
+def eval_modes(ci):
+    """The evaluation code paths of case number `ci`: (name, nmpc_config overrides on top of latency_waves = 1)."""
+    return [("one-wave", dict(coop_waves=1, reg_table=0)), ("one-wave/lds", dict(coop_waves=1, reg_table=-1)),
+            ("one-wave/general", dict(coop_waves=1, reg_table=0, axis_aligned=-1)),
+            ("one-wave/reg64", dict(coop_waves=1, reg_table=1)),     # fp64: register-table kernel wherever it is offered
+            ("coop4", dict(coop_waves=4, reg_table=0)), ("coop4/lds", dict(coop_waves=4, reg_table=-1)),
+            ("coop%d" % (2 + ci % 2), dict(coop_waves=2 + ci % 2, reg_table=-1))]
+
+
 def run(cases=100, seed=0, out=print):
     """returns 0 when every evaluation agrees with the oracle"""
     rng = np.random.default_rng(seed)
@@ -72,11 +81,7 @@ def run(cases=100, seed=0, out=print):
         lay, rows, P, U, Y, C = make_case(rng)
         pr = oracle.Problem(lay.N, lay.Nother, lay.Nstc, lay.Ndyn)
         B = P.shape[0]
-        modes = [("one-wave", dict(coop_waves=1, reg_table=0)), ("one-wave/lds", dict(coop_waves=1, reg_table=-1)),
-                 ("one-wave/general", dict(coop_waves=1, reg_table=0, axis_aligned=-1)),
-                 ("one-wave/reg64", dict(coop_waves=1, reg_table=1)),     # fp64: register-table kernel wherever it is offered
-                 ("coop4", dict(coop_waves=4, reg_table=0)), ("coop4/lds", dict(coop_waves=4, reg_table=-1)),
-                 ("coop%d" % (2 + ci % 2), dict(coop_waves=2 + ci % 2, reg_table=-1))]
+        modes = eval_modes(ci)
         for dtype, tp, tg in ((np.float64, 1e-10, 1e-9), (np.float32, 2e-4, 2e-3)):
             Pd = P.astype(dtype)
             want = []

@@ -21,6 +21,17 @@ CASES = [  # (N, Ndyn, n_ped, n_hyp)
     (22, 15, 3, 5), (32, 20, 4, 5), (33, 24, 4, 6), (40, 96, 8, 12), (40, 97, 1, 97), (40, 160, 8, 20), (40, 400, 20, 20),
     (64, 10, 2, 5), (5, 4, 2, 2),
 ]
+EVAL_REG_TABLES = (0, -1)  # nmpc_config.reg_table of the evaluations
+MODES = (("throughput", dict(latency_waves=1, coop_waves=1)), ("latency", dict(latency_waves=3, coop_waves=1)),
+         ("cooperative", dict(latency_waves=1, coop_waves=4)),
+         ("cooperative-lds", dict(latency_waves=1, coop_waves=4, reg_table=-1)),
+         ("automatic", dict()))
+# (tests/kernel_census.py reads CASES, EVAL_REG_TABLES, MODES and _batch: which kernels this file reaches)
+
+
+def _batch(K, seed, N, Ndyn, n_ped, n_hyp):
+    lay = ParamLayout(N=N, Ndyn=Ndyn)
+    return lay, nm.scenarios.make_batch(K, lay, seed=seed + N + Ndyn, n_ped=n_ped, n_hyp=n_hyp, ped_mode="oncoming")
 
 
 def _cfg(lay, **ov):
@@ -33,16 +44,15 @@ def _cfg(lay, **ov):
 
 @pytest.mark.parametrize("N,Ndyn,n_ped,n_hyp", CASES)
 def test_psi_and_gradient_against_oracle_across_dimensions(N, Ndyn, n_ped, n_hyp):
-    lay = ParamLayout(N=N, Ndyn=Ndyn)
     K = 6
-    P = nm.scenarios.make_batch(K, lay, seed=100 + N + Ndyn, n_ped=n_ped, n_hyp=n_hyp, ped_mode="oncoming")
+    lay, P = _batch(K, 100, N, Ndyn, n_ped, n_hyp)
     rng = np.random.default_rng(N * 1000 + Ndyn)
     U = np.stack([rng.uniform(-0.3, 1.4, (K, N)), rng.uniform(-0.45, 0.45, (K, N))], axis=2).reshape(K, 2 * N)
     Y = rng.normal(size=(K, 2 * N)) * 2
     C = rng.uniform(1, 200, K)
     pr = oracle.Problem(N, lay.Nother, lay.Nstc, Ndyn)
     want = [oracle.psi(pr, U[i], C[i], Y[i], P[i]) for i in range(K)]
-    for reg_table in (0, -1):
+    for reg_table in EVAL_REG_TABLES:
         with nm.Handle(_cfg(lay, reg_table=reg_table)) as h:
             for dtype, tp, tg in ((np.float64, 1e-11, 1e-10), (np.float32, 5e-5, 5e-4)):
                 r = h.eval(P, U, Y, C, dtype=dtype)
@@ -53,17 +63,13 @@ def test_psi_and_gradient_against_oracle_across_dimensions(N, Ndyn, n_ped, n_hyp
 
 @pytest.mark.parametrize("N,Ndyn,n_ped,n_hyp", CASES)
 def test_short_solves_agree_across_kernels_and_dimensions(N, Ndyn, n_ped, n_hyp):
-    lay = ParamLayout(N=N, Ndyn=Ndyn)
-    P = nm.scenarios.make_batch(8, lay, seed=200 + N + Ndyn, n_ped=n_ped, n_hyp=n_hyp, ped_mode="oncoming")
+    lay, P = _batch(8, 200, N, Ndyn, n_ped, n_hyp)
     pr = oracle.Problem(N, lay.Nother, lay.Nstc, Ndyn)
     short = dict(max_outer_iterations=1, max_inner_iterations=3, lip_eps_f64=1e-4, lip_delta_f64=1e-4)
     Uo, ro = oracle.solve_batch(pr, oracle.Options(max_outer=1, max_inner=3, lip_delta=1e-4, lip_eps=1e-4), P, nthreads=HOST_THREADS)
     for dtype, tol in ((np.float64, 1e-7), (np.float32, 2e-2)):
         runs = {}
-        for name, ov in (("throughput", dict(latency_waves=1, coop_waves=1)), ("latency", dict(latency_waves=3, coop_waves=1)),
-                         ("cooperative", dict(latency_waves=1, coop_waves=4)),
-                         ("cooperative-lds", dict(latency_waves=1, coop_waves=4, reg_table=-1)),
-                         ("automatic", dict())):
+        for name, ov in MODES:
             with nm.Handle(_cfg(lay, **short, **ov)) as h:
                 runs[name] = h.solve(P.astype(dtype), dtype=dtype)
         for name, r in runs.items():
