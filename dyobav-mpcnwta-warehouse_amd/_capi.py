@@ -235,6 +235,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
     "nmpc_mmp_block2_f32", "nmpc_mmp_block2_f16", "nmpc_mmp_block3_f32", "nmpc_mmp_block3_f16", "nmpc_mmp_block4_f32", "nmpc_mmp_block4_f16", "nmpc_mmp_head_f32",
     "nmpc_mmp_block2_f16_io", "nmpc_mmp_block3_f16_io", "nmpc_mmp_block4_f16_io", "nmpc_mmp_block_f16", "nmpc_mmp_block_f16_io",
+    "nmpc_mmp_stem_io_f32", "nmpc_mmp_stem_io_f64",
     "nmpc_last_kernel_ms", "nmpc_last_launch_info", "nmpc_kernel_info", "nmpc_selftest", "nmpc_probe_f32", "nmpc_probe_f64",
     "nmpc_last_error",
 )
@@ -329,6 +330,7 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
         getattr(lib, "nmpc_dwa_step_lists_" + sfx).argtypes = [vp, C.POINTER(NmpcDwaListsArgs)]
         getattr(lib, "nmpc_mmp_input_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpArgs)]
         getattr(lib, "nmpc_mmp_stem_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpStemArgs)]
+        getattr(lib, "nmpc_mmp_stem_io_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpStemArgs), i32]
     lib.nmpc_mmp_stem_shape.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.nmpc_mmp_block_f32.argtypes = [vp, C.POINTER(NmpcMmpBlockArgs)]
     lib.nmpc_mmp_block2_f32.argtypes = [vp, C.POINTER(NmpcMmpBlock2Args)]
@@ -576,6 +578,13 @@ class Handle:
         written (``dtype``: the element type of ``hist``), one launch enqueued on the handle's stream."""
         fn = getattr(self._lib, "nmpc_mmp_stem_" + _suffix(dtype))
         _check(fn(self._h, C.byref(args) if args is not None else None))
+
+    def mmp_stem_io(self, dtype, args: "NmpcMmpStemArgs", out_f16: int):
+        """``nmpc_mmp_stem_io_*``: ``mmp_stem`` with the form of ``out`` in memory beside the struct. ``out_f16 = 0``: ``mmp_stem``
+        itself; ``1``: ``out`` is binary16 in the octet form of the blocks' activations, ``[n_item * n_off][C / 8][Hp][Wp][8]``
+        (include/nmpc_hip.h; ``mmp_stem.pack_activations_f16``), aligned to 16 bytes."""
+        fn = getattr(self._lib, "nmpc_mmp_stem_io_" + _suffix(dtype))
+        _check(fn(self._h, C.byref(args) if args is not None else None, out_f16))
 
     def mmp_block(self, args: "NmpcMmpBlockArgs"):
         """``nmpc_mmp_block_f32``: one fused residual block of the network's layer1 (two 3 x 3 convolutions with their folded

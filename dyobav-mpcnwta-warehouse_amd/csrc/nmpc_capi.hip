@@ -1686,10 +1686,15 @@ int mmp_input(nmpc_handle_s* h, const nmpc_mmp_args* g)
     return 0;
 }
 
-template <typename T>
-int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g)
+// IO: the entry nmpc_mmp_stem_io_*, whose out (out_f16 = 1) is binary16 in the octet form (mmp_stem_kernel<MmpStemH<T>>); every other
+// refusal keeps the words of nmpc_mmp_stem_*
+template <typename T, bool IO = false>
+int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g, int32_t out_f16 = 0)
 {
     if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "null argument");
+    if constexpr (IO) {
+        if (out_f16 != 0 && out_f16 != 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem_io: out_f16 = %d (0 or 1)", out_f16);
+    }
     if (const int rc = mmp_check("nmpc_mmp_stem", g)) return rc;
     if (g->C < nmpc::kStemCG || g->C % nmpc::kStemCG) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: C = %d is no positive multiple of 8", g->C);
     if (!std::isfinite(g->slope)) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: slope = %g", (double)g->slope);
@@ -1697,6 +1702,8 @@ int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g)
         return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: a required array is NULL");
     if (g->n_item == 0) return 0;
     if (reinterpret_cast<uintptr_t>(g->out) % 4) return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem: out is not aligned to float");
+    if (out_f16 && reinterpret_cast<uintptr_t>(g->out) % 16) // (half an octet is one 8-byte store, and the blocks load whole octets)
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "nmpc_mmp_stem_io: a binary16 out is not aligned to 16 bytes");
     nmpc::MmpStemParams p;
     std::memset(&p, 0, sizeof p);
     p.Ho = (g->Hm - 1) / 2 + 1, p.Wo = (g->Wm - 1) / 2 + 1;
@@ -1711,7 +1718,9 @@ int mmp_stem(nmpc_handle_s* h, const nmpc_mmp_stem_args* g)
     mmp_fill(p, g);
     p.C = g->C, p.mono = g->slope >= 0.0f;
     p.weight = g->weight, p.bn_scale = g->bn_scale, p.bn_shift = g->bn_shift, p.slope = g->slope, p.out = g->out;
-    hipLaunchKernelGGL(nmpc::mmp_stem_kernel<T>, dim3((unsigned)groups), dim3(nmpc::kStemThreads), 0, h->stream, p);
+    auto kernel = nmpc::mmp_stem_kernel<T>;
+    if (out_f16) kernel = nmpc::mmp_stem_kernel<nmpc::MmpStemH<T>>; // (p.out points at binary16: the kernel casts it)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(nmpc::kStemThreads), 0, h->stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2509,6 +2518,8 @@ int nmpc_mmp_input_f32(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input
 int nmpc_mmp_input_f64(nmpc_handle h, const nmpc_mmp_args* a) { return mmp_input<double>(h, a); }
 int nmpc_mmp_stem_f32(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<float>(h, a); }
 int nmpc_mmp_stem_f64(nmpc_handle h, const nmpc_mmp_stem_args* a) { return mmp_stem<double>(h, a); }
+int nmpc_mmp_stem_io_f32(nmpc_handle h, const nmpc_mmp_stem_args* a, int32_t out_f16) { return mmp_stem<float, true>(h, a, out_f16); }
+int nmpc_mmp_stem_io_f64(nmpc_handle h, const nmpc_mmp_stem_args* a, int32_t out_f16) { return mmp_stem<double, true>(h, a, out_f16); }
 int nmpc_mmp_block_f32(nmpc_handle h, const nmpc_mmp_block_args* a) { return mmp_block(h, a); }
 int nmpc_mmp_block2_f32(nmpc_handle h, const nmpc_mmp_block2_args* a) { return mmp_strided<MmpLayer2>(h, a); }
 static int mmp_block_f16(nmpc_handle_s* h, const nmpc_mmp_block_f16_args* a, int32_t x_f16, int32_t out_f16, bool io)

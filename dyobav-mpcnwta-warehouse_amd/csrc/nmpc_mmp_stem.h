@@ -47,11 +47,45 @@
 // 132 VGPRs, 0 AGPRs, 94 SGPRs, no spills, no scratch, 53 240 B LDS, occupancy 3 waves per SIMD (registers and LDS agree).
 // Not at a hardware bound: 0.77 TB/s stored, 13.1 T fma/s; the halo makes a workgroup compute 1 545
 // input pixels (five float64 exp and fifteen float64 divisions each) for 768 it owns.
+//
+// Binary16 out, opt-in (nmpc_mmp_stem_io_* with out_f16 = 1; MmpFrontEnd(fill="f16")): mmp_stem_kernel<MmpStemH<T>> writes
+// out[n_item * n_off][C / 8][Hp][Wp][8], the octet form of nmpc_mmp_block_f16.h, uint16_t bit patterns, the base aligned to 16
+// bytes; each value is mmp_blkh_round of exactly the float32 value mmp_stem_kernel<T> computes -- steps 1 .. 3b are the same
+// text, and so are the fma order, the pool and the mono / element-wise choice. Only step 3c differs: who holds which outputs.
+//   Mapping chosen: lane = [offset parity s < 2][pixel q < 48][half hf < 2], 192 of the 256 threads. A lane holds the 9 (A, B)
+//   pairs of the FOUR channels 4 hf .. 4 hf + 3 of the pass's octet at one pooled pixel -- half an octet, as a D fragment of the
+//   blocks -- and walks the offsets s, s + 2, ..: per offset 4 x (9 fma, max, leaky), four mmp_blkh_round, ONE 8-byte store.
+//   Lanes 2 q and 2 q + 1 store the two halves of a 16-byte slot and consecutive px are consecutive slots, so a tile row is 384
+//   contiguous bytes per offset and octet.
+//   Counted against it:
+//   - registers: 4 x 9 x 2 = 72 VGPRs of (A, B) per lane; a whole octet per lane (one 16-byte store, 48 lanes per parity) is 144
+//     and does not fit 168 (three waves per SIMD) beside the rest; two channels per lane would be 4-byte stores.
+//   - busy lanes: 192 of 256 for n_off >= 2 (wave 3 idles in 3c); per lane 4 channels x ceil(n_off / 2) offsets = 40 at n_off = 20,
+//     what the parent's busiest lanes do (2 items x 20); in wave-instructions 3 x 40 against the parent's (2 + 2 + 1 + 1) x 20: equal.
+//     Splitting the offsets by parity is what keeps the walk as short as the parent's with half as many (pixel, channel) owners.
+//   - LDS: (A, B) stay [8][NP] as step 3b writes them (shared text), so the re-mapped reads are dwords at (4 hf + c) 245 + (2 pyl +
+//     dy) 49 + 2 pxl + dx: bank (20 hf + 34 pyl + 2 pxl + const) mod 64, even offsets only -- 2-way as the parent's stride-2 reads,
+//     3-way on the banks where the three ranges overlap (34 .. 46 of 0 .. 62); 72 reads per lane and pass (paired by the compiler
+//     into ds_read2_b32 / ds_read_b64) against 343 x 3 in step 3b. A channel-innermost (A, B) would make them 16-byte reads but
+//     changes step 3b and with it the float32 kernels' bytes.
+//   - stores: 96 lanes x 8 B = 1.5 wave-instructions per tile, pass and offset against 6 of dwords.
+//   - scalar registers: the float32 kernels use 94 of 102, and the compiler hoists every workgroup-uniform value of 3c out of the pass
+//     loop into more (5 spilled to VGPR lanes when left alone). So the two strides, the weight pointer and the pass count are held
+//     in VECTOR registers (mmp_stem_in_vgprs, an opaque v_mov), and the two lane masks (valid in 3b, "has offsets" in 3c) are made
+//     pass by pass from a VGPR behind an empty asm instead of being carried as SGPR pairs: 160 VGPRs, 106 SGPRs with VCC, no spills,
+//     no scratch, 53 240 B LDS, occupancy 3 (tools/kernel_resources.py; tests/test_mmp_fill_cpu.py). No atomics.
+//   The float32 kernels keep their bytes (profiles/mmp_fill_f16_code_object_identity.txt: 292 of 292).
+//   Measured (tools/mmp_evaluate_profile.py --fill-f16 -> profiles/mmp_fill_f16_evaluate.json; B = 256, 4 pedestrians, N_hor = 20,
+//   both arms on precision = "f16", three runs each in one process): the launch alone 46.8 / 47.7 / 46.9 ms per lock-step ->
+//   44.2 / 43.8 / 43.7 (0.92-0.94 x) at 0.37 TB/s stored against 0.68: half the bytes bought 7 %, so the stores were not what
+//   bounds this kernel -- the float64 planes of the halo and the fma chains are. The gain is behind it: layer1's first block
+//   22.5 -> 12.6 ms per lock-step, and a chunk of 34 pedestrians instead of 22; the stage 128.1 -> 107.7 ms.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "nmpc_mmp.h"
+#include "nmpc_mmp_block_f16.h"
 
 namespace nmpc {
 
@@ -67,7 +101,7 @@ struct MmpStemParams {
     const float* bn_scale;                                            // [C]
     const float* bn_shift;                                            // [C]
     float slope;
-    float* out;                                                       // [n_item][n_off][C][Hp][Wp]
+    float* out;                                                       // [n_item][n_off][C][Hp][Wp]; MmpStemH: the octet form
 };
 
 constexpr int kStemThreads = 256;
@@ -80,14 +114,46 @@ constexpr int kStemCG = 8;                                            // output 
 constexpr int kStemTaps = 7 * 49;                                     // weights per output channel
 constexpr int kStemXs = 6 * kStemIH * 2 * kStemIW2;                   // floats of the input tile
 constexpr int kStemWab = 2 * kStemCG * kStemNP;                       // floats of (A, B); the weights (8 x 343) fit inside
+constexpr int kStemHQ = 2 * kStemTPH * kStemTPW;                      // binary16 out: (pixel, half octet) pairs of a tile: 96
 static_assert(kStemNP <= kStemThreads && kStemCG * kStemTaps <= kStemWab, "tile does not fit the workgroup");
+static_assert(kStemCG == 8 && 2 * kStemHQ <= kStemThreads, "a pass is one octet; two offset parities fit the workgroup");
 static_assert((kStemXs + kStemWab) * 4 + 5 * 3 * 8 <= 64 * 1024, "static LDS over 64 KB");
 
 __host__ __device__ inline int mmp_stem_out(int n) { return (((n - 1) / 2 + 1) - 1) / 2 + 1; } // conv 7/2/3, then pool 3/2/1
 
+// A workgroup-uniform value kept in vector registers (mmp_stem_kernel<MmpStemH<T>>: the scalar registers are the scarce ones
+// there, 94 of 102 before step 3c adds its strides; left to itself the compiler holds them in SGPRs and spills five)
+__device__ __forceinline__ size_t mmp_stem_in_vgprs(size_t v)
+{
+    unsigned lo, hi;
+    asm("v_mov_b32 %0, %1" : "=v"(lo) : "s"((unsigned)v));
+    asm("v_mov_b32 %0, %1" : "=v"(hi) : "s"((unsigned)(v >> 32)));
+    return ((size_t)hi << 32) | lo;
+}
+
+// The form of out travels in the kernel's TYPE argument, as the blocks' MmpBlkhIo does: T = float / double is the element type of
+// hist with float32 out, and those two kernels keep their names and their bytes; MmpStemH<T> is the same hist with out as
+// binary16 in the octet form [n_item * n_off][C / 8][Hp][Wp][8], the base aligned to 16 bytes (step 3c alone differs). The
+// params are a true __global__ argument: a body handed them by reference compiles to other bytes (tried: 11 300 B -> 11 256 B).
 template <typename T>
+struct MmpStemH {
+};
+template <typename T>
+struct mmp_stem_io {
+    typedef T Hist;
+    static constexpr bool OH = false;
+};
+template <typename T>
+struct mmp_stem_io<MmpStemH<T>> {
+    typedef T Hist;
+    static constexpr bool OH = true;
+};
+
+template <typename TT>
 __global__ __launch_bounds__(kStemThreads) void mmp_stem_kernel(MmpStemParams p)
 {
+    typedef typename mmp_stem_io<TT>::Hist T;
+    constexpr bool OH = mmp_stem_io<TT>::OH;
     __shared__ __attribute__((aligned(16))) float xs[kStemXs];   // [6][IH][parity][IW2]
     __shared__ __attribute__((aligned(16))) float wab[kStemWab]; // weights [7 * 49][8], then A [8][NP], B [8][NP]
     __shared__ double cen[5][3];                                 // cx, cy, zmax
@@ -150,11 +216,32 @@ __global__ __launch_bounds__(kStemThreads) void mmp_stem_kernel(MmpStemParams p)
     }
     const size_t plane = (size_t)p.Hp * p.Wp;
     const float ninf = -__builtin_huge_valf();
+    // binary16 out: the thread's share of step 3c, the same for every pass
+    // lane = [offset parity hs][pixel q][half hf]: channels 4 hf .. 4 hf + 3 of the octet at one pixel, offsets hs, hs + 2, ..
+    int hs = 0, hn = 0, hpos = 0;      // first offset; offsets the lane stores (0: none); (A, B) index of channel 4 hf, tap 0
+    mmp_blkh_h4* hdst = nullptr;       // the lane's 8 bytes of octet 0 at offset hs
+    size_t hpass = 0, hoff2 = 0;       // from one pass to the next; two offsets on (units of 8 bytes)
+    int hng = 0;                       // the passes, C / 8 (read back pass by pass)
+    const float* weight = p.weight;    // (binary16 out: the pointer in vector registers too, two SGPRs fewer live through 3b)
+    if constexpr (OH) {
+        hs = tid / kStemHQ;
+        const int r = tid - hs * kStemHQ, q = r >> 1, hf = r & 1;
+        const int pyl = q / kStemTPW, pxl = q - pyl * kStemTPW;
+        const int py = py0 + pyl, px = px0 + pxl;
+        if (hs < 2 && py < p.Hp && px < p.Wp) hn = (p.n_off - hs + 1) >> 1;
+        hpos = 4 * hf * kStemNP + 2 * pyl * kStemCW + 2 * pxl;
+        hdst = reinterpret_cast<mmp_blkh_h4*>(p.out)
+               + 2 * (((size_t)item * p.n_off + hs) * (size_t)(p.C / kStemCG) * plane + (size_t)py * p.Wp + px) + hf;
+        hng = p.C / kStemCG;
+        asm("" : "+v"(hng));
+        weight = reinterpret_cast<const float*>(mmp_stem_in_vgprs(reinterpret_cast<size_t>(p.weight)));
+        hpass = mmp_stem_in_vgprs(2 * plane), hoff2 = mmp_stem_in_vgprs(4 * (size_t)(p.C / kStemCG) * plane);
+    }
 
-    for (int g = 0; g < p.C / kStemCG; ++g) {
+    for (int g = 0; g < (OH ? __builtin_amdgcn_readfirstlane(hng) : p.C / kStemCG); ++g) {
         __syncthreads(); // the input tile is written; the previous group's (A, B) have been read
         // ---- 3a. weights [8][343] -> [343][8]
-        const float* wg = p.weight + (size_t)g * kStemCG * kStemTaps;
+        const float* wg = weight + (size_t)g * kStemCG * kStemTaps;
         for (int i = tid; i < kStemCG * kStemTaps; i += kStemThreads) {
             const int j = i / kStemTaps, r = i - j * kStemTaps;
             wab[r * kStemCG + j] = wg[i];
@@ -189,52 +276,103 @@ __global__ __launch_bounds__(kStemThreads) void mmp_stem_kernel(MmpStemParams p)
             }
         }
         __syncthreads(); // every weight has been read: (A, B) go over them
+        bool ok = valid;
+        if constexpr (OH) {
+            int t = valid;
+            asm volatile("" : "+v"(t)); // (as n below: the mask is made here, not carried through the passes)
+            ok = t != 0;
+        }
         if (has) {
 #pragma unroll
             for (int j = 0; j < kStemCG; ++j) {
                 const float s = p.bn_scale[g * kStemCG + j], sh = p.bn_shift[g * kStemCG + j];
-                wab[j * kStemNP + tid] = valid ? fmaf(s, acc[j], sh) : ninf;
-                wab[(kStemCG + j) * kStemNP + tid] = valid ? s * e[j] : 0.0f;
+                wab[j * kStemNP + tid] = ok ? fmaf(s, acc[j], sh) : ninf;
+                wab[(kStemCG + j) * kStemNP + tid] = ok ? s * e[j] : 0.0f;
             }
         }
         __syncthreads();
         // ---- 3c. pool and store, n_off times
-        for (int it = tid; it < kStemCG * kStemTPH * kStemTPW; it += kStemThreads) {
-            const int j = it / (kStemTPH * kStemTPW), q = it - j * (kStemTPH * kStemTPW);
-            const int pyl = q / kStemTPW, pxl = q - pyl * kStemTPW;
-            const int py = py0 + pyl, px = px0 + pxl;
-            if (py >= p.Hp || px >= p.Wp) continue;
-            float a[9], b[9];
+        if constexpr (OH) {
+            int n = hn;
+            asm volatile("" : "+v"(n)); // (compared here, pass by pass: hoisted, the lane mask is one more pair of live SGPRs)
+            if (n > 0) {
+                float a[4][9], b[4][9];
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
+                for (int c = 0; c < 4; ++c)
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const int pos = (2 * pyl + dy) * kStemCW + 2 * pxl + dx;
-                    a[dy * 3 + dx] = wab[j * kStemNP + pos];
-                    b[dy * 3 + dx] = wab[(kStemCG + j) * kStemNP + pos];
-                }
-            float* dst = p.out + ((size_t)item * p.n_off * p.C + (size_t)(g * kStemCG + j)) * plane + (size_t)py * p.Wp + px;
-            if (p.mono) {
-                for (int off = 0; off < p.n_off; ++off) {
-                    const float t = (float)(off + 1);
-                    float m = fmaf(t, b[0], a[0]);
+                    for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                    for (int i = 1; i < 9; ++i) m = fmaxf(m, fmaf(t, b[i], a[i]));
-                    *dst = m > 0.0f ? m : m * p.slope;
-                    dst += (size_t)p.C * plane;
-                }
-            } else {
-                for (int off = 0; off < p.n_off; ++off) {
-                    const float t = (float)(off + 1);
-                    float m = ninf;
+                        for (int dx = 0; dx < 3; ++dx) {
+                            const int pos = hpos + c * kStemNP + dy * kStemCW + dx;
+                            a[c][dy * 3 + dx] = wab[pos];
+                            b[c][dy * 3 + dx] = wab[kStemCG * kStemNP + pos];
+                        }
+                mmp_blkh_h4* dst = hdst;
+                for (int k = 0; k < n; ++k) {
+                    const float t = (float)(hs + 2 * k + 1);
+                    mmp_blkh_h4 v;
 #pragma unroll
-                    for (int i = 0; i < 9; ++i) {
-                        const float z = fmaf(t, b[i], a[i]);
-                        const float v = z > 0.0f ? z : z * p.slope;
-                        m = fmaxf(m, a[i] > ninf ? v : ninf);
+                    for (int c = 0; c < 4; ++c) {
+                        float m;
+                        if (p.mono) {
+                            m = fmaf(t, b[c][0], a[c][0]);
+#pragma unroll
+                            for (int i = 1; i < 9; ++i) m = fmaxf(m, fmaf(t, b[c][i], a[c][i]));
+                            m = m > 0.0f ? m : m * p.slope;
+                        } else {
+                            m = ninf;
+#pragma unroll
+                            for (int i = 0; i < 9; ++i) {
+                                const float z = fmaf(t, b[c][i], a[c][i]);
+                                const float w = z > 0.0f ? z : z * p.slope;
+                                m = fmaxf(m, a[c][i] > ninf ? w : ninf);
+                            }
+                        }
+                        v[c] = mmp_blkh_round(m);
                     }
-                    *dst = m;
-                    dst += (size_t)p.C * plane;
+                    *dst = v;
+                    dst += hoff2;
+                }
+            }
+            hdst += hpass;
+        } else {
+            for (int it = tid; it < kStemCG * kStemTPH * kStemTPW; it += kStemThreads) {
+                const int j = it / (kStemTPH * kStemTPW), q = it - j * (kStemTPH * kStemTPW);
+                const int pyl = q / kStemTPW, pxl = q - pyl * kStemTPW;
+                const int py = py0 + pyl, px = px0 + pxl;
+                if (py >= p.Hp || px >= p.Wp) continue;
+                float a[9], b[9];
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx) {
+                        const int pos = (2 * pyl + dy) * kStemCW + 2 * pxl + dx;
+                        a[dy * 3 + dx] = wab[j * kStemNP + pos];
+                        b[dy * 3 + dx] = wab[(kStemCG + j) * kStemNP + pos];
+                    }
+                float* dst = p.out + ((size_t)item * p.n_off * p.C + (size_t)(g * kStemCG + j)) * plane + (size_t)py * p.Wp + px;
+                if (p.mono) {
+                    for (int off = 0; off < p.n_off; ++off) {
+                        const float t = (float)(off + 1);
+                        float m = fmaf(t, b[0], a[0]);
+#pragma unroll
+                        for (int i = 1; i < 9; ++i) m = fmaxf(m, fmaf(t, b[i], a[i]));
+                        *dst = m > 0.0f ? m : m * p.slope;
+                        dst += (size_t)p.C * plane;
+                    }
+                } else {
+                    for (int off = 0; off < p.n_off; ++off) {
+                        const float t = (float)(off + 1);
+                        float m = ninf;
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) {
+                            const float z = fmaf(t, b[i], a[i]);
+                            const float v = z > 0.0f ? z : z * p.slope;
+                            m = fmaxf(m, a[i] > ninf ? v : ninf);
+                        }
+                        *dst = m;
+                        dst += (size_t)p.C * plane;
+                    }
                 }
             }
         }

@@ -131,7 +131,8 @@ class BatchEvaluator:
                  hyp_radius_growth: float = 0.05, predictor: Optional[str] = "cvmp", kf_Q=None, kf_R=None, kf_P0=None,
                  tracker: str = "mpc", dwa_config=None, network=None, mmp_hyp: int = 20, mmp_chunk: Optional[int] = None,
                  ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None, mmp_blocks=None, mmp_blocks2=None, mmp_blocks3=None,
-                 mmp_blocks4=None, mmp_head=None, mmp_half=(), mmp_operands=None, mmp_activations=None, mmp_precision=None):
+                 mmp_blocks4=None, mmp_head=None, mmp_half=(), mmp_operands=None, mmp_activations=None, mmp_precision=None,
+                 mmp_fill=None):
         """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
@@ -216,6 +217,11 @@ class BatchEvaluator:
         csrc/nmpc_mmp_block1_f16.h, the same rule; ``mmp_operands`` and ``mmp_half`` keep refusing layer1), with binary16 activations
         between all blocks. Refused beside an ``mmp_operands`` entry ``"f32"`` of a stage given or ``mmp_activations="f32"``; checked
         by ``MmpFrontEnd.check_precision``.
+        ``mmp_fill``: the form of the fused first layer's output in memory. ``None``, the default, or ``"f32"`` changes no bit, no
+        launch and no buffer; ``"f16"`` (needs ``mmp_stem`` and ``mmp_precision="f16"``) makes that layer write binary16 in the octet
+        form (``nmpc_mmp_stem_io_*``, csrc/nmpc_mmp_stem.h), which layer1's first block reads as such: the same bits behind a first
+        block with a projection, half the fill's bytes per pedestrian, which the chunking sees. Checked by
+        ``MmpFrontEnd.check_fill``. Measured: DESIGN.md section 7, ``profiles/mmp_fill_f16_evaluate.json``.
 
         ``n_hyp`` > 1: every pedestrian enters the solver as ``n_hyp`` obstacle rows fanned around its constant-velocity
         prediction by ``(j - (n_hyp - 1) / 2) * hyp_fan`` rad, radii ``HUMAN_SIZE + hyp_radius_growth * t`` -- the
@@ -241,7 +247,8 @@ class BatchEvaluator:
             raise ValueError("mmp_half needs predictor = 'mmp'")
         if mmp_operands and predictor != "mmp":
             raise ValueError("mmp_operands needs predictor = 'mmp'")
-        mmp_switches = dict(operands=None if mmp_operands is None else dict(mmp_operands), activations=mmp_activations, precision=mmp_precision)
+        mmp_switches = dict(operands=None if mmp_operands is None else dict(mmp_operands), activations=mmp_activations, precision=mmp_precision,
+                            fill=mmp_fill)
         mmp_operands = MmpFrontEnd.check_operands(mmp_operands, mmp_half, mmp_specs, prefix="mmp_")
         mmp_half = MmpFrontEnd.check_half(mmp_half, mmp_specs, prefix="mmp_")
         if mmp_activations and predictor != "mmp":
@@ -251,6 +258,9 @@ class BatchEvaluator:
         # (checks the activations too, in front of its own refusals; the front end takes the caller's own values: the checked
         # operands name layer1, which ``mmp_operands`` refuses)
         MmpFrontEnd.check_precision(mmp_precision, mmp_switches["operands"], mmp_half, mmp_activations, mmp_specs, prefix="mmp_")
+        if mmp_fill and predictor != "mmp":
+            raise ValueError("mmp_fill needs predictor = 'mmp'")
+        MmpFrontEnd.check_fill(mmp_fill, mmp_precision, mmp_specs, prefix="mmp_")
         if predictor == "mmp":
             if self.n_hyp != 1 or not fused:
                 raise ValueError("predictor = 'mmp' needs n_hyp = 1 and fused = True")
@@ -419,7 +429,8 @@ class BatchEvaluator:
         self._info, self._evals = self._full(B, 8), self._full(B)
         self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
 
-    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, specs, half=(), operands=None, activations=None, precision=None):
+    def _init_mmp(self, network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, specs, half=(), operands=None, activations=None, precision=None,
+                  fill=None):
         """The multi-hypothesis predictor's constants: the label image on the device, the map of the snap stage, the device front
         end (``mmp_front``: its kernels, weights and buffers) and from it the shape of one row of the network's input -- the stack's
         [7, Hm, Wm] or, with a fused first layer, its output [C, Hp, Wp], or behind the last fused stage its [channels, H, W], or with a
@@ -436,7 +447,8 @@ class BatchEvaluator:
         # mmp_interface.py:60 snaps on 255 - ref_image; its grey levels decide the edges (Handle.set_map)
         self.h.set_map(255.0 - img.astype(np.float64))
         fe = self.mmp_front = MmpFrontEnd(self.h, self.dt, self.dev, self.mmp_Hm, self.mmp_Wm, self.N, transform, self.mmp_rescale, MMP_SIGMA,
-                                          self.mmp_ref, *specs, half=half, operands=operands, activations=activations, precision=precision)
+                                          self.mmp_ref, *specs, half=half, operands=operands, activations=activations, precision=precision,
+                                          fill=fill)
         self.mmp_row = fe.row
         for name in SPEC_NAMES:
             setattr(self, "mmp_" + name, getattr(fe, name))

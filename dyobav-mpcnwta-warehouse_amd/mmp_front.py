@@ -66,7 +66,7 @@ class Stage:
 class MmpFrontEnd:
     def __init__(self, handle: _capi.Handle, dtype, device, Hm: int, Wm: int, n_off: int, transform, rescale: float, sigma: float,
                  ref_image, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=(),
-                 operands=None, activations=None, precision=None):
+                 operands=None, activations=None, precision=None, fill=None):
         """``dtype``: the element type of ``hist``; ``ref_image``: the float32 label image ``[Hm, Wm]`` on ``device``; ``transform``: the
         :class:`.snap.WorldTransform` between map pixels and the world of ``hist``; ``stem``: a :class:`.mmp_stem.StemSpec`; ``blocks``
         .. ``blocks4``: the specs of ``layer1`` .. ``layer4`` (``mmp_stem.STAGES``), each needing the one before it; ``head`` (needs
@@ -99,19 +99,28 @@ class MmpFrontEnd:
         still reads the fill's float32 output, the last block still writes float32 NCHW. ``self.operands`` then reports ``"f16"`` for
         every stage given and ``self.activations`` ``"f16"``. Refused beside an ``operands`` entry ``"f32"`` for a stage given or
         ``activations="f32"``; accepted beside ``half`` / ``operands`` / ``activations`` that agree (``check_precision``).
+        ``fill``: the form of the fill's output in memory. ``None`` or ``"f32"`` changes no bit, no launch and no buffer. ``"f16"``
+        (needs ``stem`` and ``precision="f16"``; ``check_fill``): the fused first layer writes binary16 in the octet form
+        (``nmpc_mmp_stem_io_*`` with ``out_f16 = 1``, csrc/nmpc_mmp_stem.h) and layer1's first block reads it as such, its flags
+        ``(1, 1)``. That block rounds the float32 values by the same rule when it stages them, and so does its projection, so
+        behind a first block WITH a projection (the reference's 64 -> 16) every bit is that of ``precision="f16"`` alone; without one
+        the block's identity is the binary16 value, as the rule's last clause says. The fill's buffer is half of what it was, and
+        ``bytes_per_item`` says so; ``fill()`` then returns a decoded float32 COPY. ``self.fill_f16`` reports the choice.
 
-        Where a stage's two buffers lie is one rule: the fill's output (the stem's, ``[C, Hp, Wp]`` per row) is idle once layer1's
-        first block has read it, so the buffers of the stages behind layer1 are laid INSIDE it one behind the other, at a running
-        offset, as long as the sum still fits (``2 * 32 * H2 * W2 + 2 * 64 * H3 * W3 + 2 * 128 * H4 * W4 <= C * Hp * Wp``: the
-        64-channel stem); from the first stage that does not fit on they are allocated and counted in ``bytes_per_item``. Layer1
-        itself reads the fill's output (``Stage.reads_fill``), so its buffers are always allocated and counted. The head's output
-        ``[rows, O]`` is always allocated and counted."""
+        Where a stage's two buffers lie is one rule, evaluated in BYTES (``place_stages``): the fill's output (the stem's,
+        ``[C, Hp, Wp]`` per row) is idle once layer1's first block has read it, so the buffers of the stages behind layer1 are laid
+        INSIDE it one behind the other, at a running offset, as long as the sum still fits (``4 * (2 * 32 * H2 * W2 + 2 * 64 * H3 *
+        W3 + 2 * 128 * H4 * W4) <= e * C * Hp * Wp``, ``e`` = 4 bytes, or 2 with ``fill="f16"``: the 64-channel stem); from the first
+        stage that does not fit on they are allocated and counted in ``bytes_per_item``. Layer1 itself reads the fill's output
+        (``Stage.reads_fill``), so its buffers are always allocated and counted. The head's output ``[rows, O]`` is always allocated
+        and counted."""
         import torch
         specs = self.check_specs(stem, blocks, blocks2=blocks2, blocks3=blocks3, blocks4=blocks4, head=head)
         stem, head = specs[0], specs[-1]
         self.operands = self.check_operands(operands, half, specs)
         self.half = self.check_half(half, specs)
         self.operands, self.activations = self.check_precision(precision, operands, half, activations, specs)
+        self.fill_f16 = self.check_fill(fill, precision, specs) == "f16"
         self.h, self.dt, self.dev, self.n_off = handle, np.dtype(dtype), device, int(n_off)
         bits = lambda a: a.view(np.int16) if a.dtype == np.uint16 else a          # (packed binary16 bit patterns travel as int16)
         dev = lambda spec, names: spec._replace(**{n: torch.as_tensor(bits(getattr(spec, n)), device=device) for n in names if getattr(spec, n) is not None})
@@ -123,13 +132,16 @@ class MmpFrontEnd:
         else:
             self.fill_row = (int(stem.weight.shape[0]),) + _capi.mmp_stem_shape(Hm, Wm)
             a, self._fill = _capi.NmpcMmpStemArgs(), handle.mmp_stem
+            if self.fill_f16:
+                self._fill = lambda dt, args: handle.mmp_stem_io(dt, args, 1)
             a.C, a.slope = self.fill_row[0], stem.slope
             a.weight, a.bn_scale, a.bn_shift = self.stem.weight.data_ptr(), self.stem.scale.data_ptr(), self.stem.shift.data_ptr()
         a.set_transform(transform, rescale, sigma)
         a.n_off, a.Hm, a.Wm, a.ref_image = self.n_off, int(Hm), int(Wm), ref_image.data_ptr()
         fill_size = int(np.prod(self.fill_row))
-        self.row, self.bytes_per_item = self.fill_row, self.n_off * fill_size * 4
-        self.stages, offset, inside = [], 0, True           # offset: floats of a fill row given away so far; inside: nothing overflowed yet
+        self._fill_bytes = fill_size * (2 if self.fill_f16 else 4)              # of a row of the fill's buffer
+        self.row, self.bytes_per_item = self.fill_row, self.n_off * self._fill_bytes
+        self.stages = []
         for table, (Args, launch), given in zip(STAGES, _DEVICE, specs[1:-1]):
             if given is not None and self.operands[table.layer] == "f16":
                 pack, Args, launch = _F16_ALL[table.layer]
@@ -143,19 +155,20 @@ class MmpFrontEnd:
             for b in given:
                 planes.append(block2_plane(*planes[-1], getattr(b, "stride", 1)))       # (layer1's blocks have no stride: 1)
             st = Stage(table.layer, table.channels, getattr(self, table.arg), cins, Args, getattr(handle, launch), planes, reads_fill=not self.stages)
-            size = 2 * int(np.prod(st.buf_row))
-            st.in_fill = inside and not st.reads_fill and offset + size <= fill_size
-            if st.in_fill:
-                st.offset, offset = offset, offset + size
-            else:
-                self.bytes_per_item += self.n_off * size * 4
-            inside = st.in_fill or st.reads_fill
             self.row = (st.channels,) + planes[-1]
             self.stages.append(st)
+        slots = [2 * int(np.prod(st.buf_row)) * 4 for st in self.stages]       # bytes of a row of each stage's two float-sized buffers
+        for st, slot, at in zip(self.stages, slots, self.place_stages(self._fill_bytes, slots)):
+            st.in_fill = at is not None
+            if st.in_fill:
+                st.offset = at // 4                         # (floats: every slot is a multiple of 4 bytes)
+            else:
+                self.bytes_per_item += self.n_off * slot
         if self.activations == "f16":
             # a tensor is binary16 where the block that writes it and the block that reads it both run on f16 operands
             f16 = [self.operands[st.name] == "f16" for st in self.stages for _ in st.specs]
-            between = [False] + [a and b for a, b in zip(f16, f16[1:])] + [False]      # in front of block k: between[k]
+            # in front of block k: between[k] (the first tensor is the fill's: binary16 with ``fill="f16"``, which needs layer1 on f16)
+            between = [self.fill_f16] + [a and b for a, b in zip(f16, f16[1:])] + [False]
             k = 0
             for st in self.stages:
                 if self.operands[st.name] == "f16":
@@ -257,6 +270,35 @@ class MmpFrontEnd:
             raise ValueError(f"{prefix}precision: 'f16', but {prefix}activations is 'f32'")
         return {name: "f16" for name in ops}, "f16"
 
+    @staticmethod
+    def check_fill(fill, precision, specs, prefix: str = "") -> str:
+        """``fill`` as ``"f32"`` (also for ``None``) or ``"f16"``, checked against the caller's ``precision`` and the checked ``specs`` of
+        ``check_specs`` (all six). It is called behind ``check_precision``, so earlier refusals speak first and unchanged. One
+        sentence per refusal: a value that is none of the three; ``"f16"`` without a stem; ``"f16"`` without ``precision="f16"``."""
+        if fill is not None and not (isinstance(fill, str) and fill in _OPERANDS):
+            raise ValueError(f"{prefix}fill: {fill!r} is none of None, 'f32' and 'f16'")
+        if fill == "f16" and specs[0] is None:
+            raise ValueError(f"{prefix}fill: 'f16' needs {prefix}stem (the input stack stays float32: only the fused first layer writes binary16)")
+        if fill == "f16" and not (isinstance(precision, str) and precision == "f16"):
+            raise ValueError(f"{prefix}fill: 'f16' needs {prefix}precision = 'f16' (layer1's first block reads binary16 only on f16 operands)")
+        return fill or "f32"
+
+    @staticmethod
+    def place_stages(fill_bytes: int, slots) -> tuple:
+        """Where each stage's two buffers lie, in BYTES of a row: ``fill_bytes`` is a row of the fill's output, ``slots`` the bytes of
+        a row of each stage's two buffers, first stage first. Per stage the byte offset into the fill's row, or ``None`` = allocated
+        on its own. The first stage reads the fill's output and is never inside it; the others are laid inside one behind the
+        other while the running sum still fits, and from the first that does not fit on none is."""
+        out, offset, inside = [], 0, True
+        for k, slot in enumerate(slots):
+            inside = inside and (k == 0 or offset + slot <= fill_bytes)
+            if k == 0 or not inside:
+                out.append(None)
+            else:
+                out.append(offset)
+                offset += slot
+        return tuple(out)
+
     def stage(self, name: str):
         """The :class:`Stage` called ``name`` (``"layer1"`` ..), or ``None`` if its specs were not given."""
         return next((st for st in self.stages if st.name == name), None)
@@ -268,7 +310,8 @@ class MmpFrontEnd:
             return
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.dev)
         rows = chunk * self.n_off
-        self._fill_buf = x = new(chunk, self.n_off, *self.fill_row)
+        # (binary16 in the octet form: the same rows at half the bytes, kept as floats for the stages' views into it)
+        self._fill_buf = x = new(chunk, self.n_off, self._fill_bytes // 4) if self.fill_f16 else new(chunk, self.n_off, *self.fill_row)
         self._fill_args.out = x.data_ptr()
         for st in self.stages:
             n, args = int(np.prod(st.buf_row)), []
@@ -296,13 +339,29 @@ class MmpFrontEnd:
 
     def fill(self, hist: int, hcount: int, B: int, H: int, items, n: int):
         """The fill alone for ``n`` pedestrians: ``hist`` ``[B, H, 5, 2]`` / ``hcount`` ``[B, H]`` device pointers, ``items`` a device
-        pointer to their int64 indices or ``None`` = 0 .. n - 1. Returns its output ``[n * n_off, *fill_row]``."""
+        pointer to their int64 indices or ``None`` = 0 .. n - 1. Returns its output ``[n * n_off, *fill_row]``: a view of its
+        buffer, or, with ``fill="f16"``, a decoded float32 COPY of it, made with torch operations on the device -- ``run`` makes
+        the same launch and never decodes."""
+        self._launch_fill(hist, hcount, B, H, items, n)
+        return self._fill_out(n)
+
+    def _launch_fill(self, hist: int, hcount: int, B: int, H: int, items, n: int):
+        """The launch of ``fill``, and nothing else."""
         if not 0 <= n <= self.chunk:
             raise ValueError(f"{n} items; allocate() was called for {self.chunk}")
         a = self._fill_args
         a.B, a.H, a.n_item, a.hist, a.hcount, a.items = B, H, n, hist, hcount, items
         self._fill(self.dt, a)
-        return self._fill_buf.view(-1, *self.fill_row)[:n * self.n_off]
+
+    def _fill_out(self, n: int):
+        """What ``fill`` returns, from what the launch left in the fill's buffer."""
+        import torch
+        rows = n * self.n_off
+        if not self.fill_f16:
+            return self._fill_buf.view(-1, *self.fill_row)[:rows]
+        C, H, W = self.fill_row
+        octets = self._fill_buf.view(torch.int16).view(-1)[:rows * C * H * W].view(torch.float16).view(rows, C // 8, H, W, 8)
+        return octets.permute(0, 1, 4, 2, 3).reshape(rows, C, H, W).float()
 
     def _check_rows(self, rows: int):
         if not 0 <= rows <= self.chunk * self.n_off:
@@ -378,10 +437,12 @@ class MmpFrontEnd:
         Returns the view ``[n * n_off, *row]`` the network is to be called on -- with a head the network's output ``[n * n_off, O]``
         itself; the next ``run`` overwrites it."""
         part = part or (lambda name, call: call())
-        x = part("input", lambda: self.fill(hist, hcount, B, H, items, n))
+        part("input", lambda: self._launch_fill(hist, hcount, B, H, items, n))
         for st in self.stages:
             part(st.name, lambda st=st: self._launch_stage(st, n * self.n_off))
-        if self.stages:
+        if not self.stages:
+            x = self._fill_out(n)                                  # (a view: ``fill="f16"`` needs layer1, so it is never decoded here)
+        else:
             x = self._stage_out(self.stages[-1], n * self.n_off)   # (float32 always: its reader is the head or the caller's network)
         if self._head_args is not None:
             x = part("head", lambda: self.run_head(n * self.n_off))

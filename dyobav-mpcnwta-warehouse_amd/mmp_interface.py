@@ -38,7 +38,7 @@ OBSV_LEN = 5        # config.obsv_len of the reference's network configurations
 
 class MmpInterface:
     def __init__(self, network: Optional[Callable] = None, stem=None, blocks=None, blocks2=None, blocks3=None, blocks4=None, head=None, half=(),
-                 operands=None, activations=None, precision=None):
+                 operands=None, activations=None, precision=None, fill=None):
         """``stem``: a :class:`.mmp_stem.StemSpec` = the network's first layer, computed on the device without the input stack
         (``nmpc_mmp_stem_f64``); ``network`` is then the trunk behind it, a callable on ``[M, C, Hp, Wp]``. ``blocks`` (needs
         ``stem``): the :class:`.mmp_stem.BlockSpec` s of the residual stage behind the stem (``mmp_stem.split_network_layer1``),
@@ -61,7 +61,9 @@ class MmpInterface:
         operands) keeps every tensor between two blocks on f16 operands in memory as binary16 (``MmpFrontEnd``,
         ``MmpFrontEnd.check_activations``). ``precision``: ``None`` or ``"f32"`` changes no bit; ``"f16"`` (needs ``blocks``) runs every
         stage given on f16 operands, layer1 included (``nmpc_mmp_block_f16``), with binary16 activations between all blocks
-        (``MmpFrontEnd.check_precision``)."""
+        (``MmpFrontEnd.check_precision``). ``fill``: ``None`` or ``"f32"`` changes no bit; ``"f16"`` (needs ``stem`` and
+        ``precision="f16"``) makes the fused first layer write binary16 too (``nmpc_mmp_stem_io_*``), which layer1's first block then
+        reads as such (``MmpFrontEnd.check_fill``)."""
         if head is not None and network is not None:
             raise TypeError("head is the network's end: network must be None with it")
         if head is None and not callable(network):
@@ -72,8 +74,9 @@ class MmpInterface:
         self._operands = MmpFrontEnd.check_operands(operands, half, self._specs)
         self._half = MmpFrontEnd.check_half(half, self._specs)
         self._operands, self._activations = MmpFrontEnd.check_precision(precision, operands, half, activations, self._specs)
+        self._fill = MmpFrontEnd.check_fill(fill, precision, self._specs)
         # (the front ends take the caller's own values: the checked operands name layer1, which ``operands`` refuses)
-        self._switches = dict(operands=None if operands is None else dict(operands), activations=activations, precision=precision)
+        self._switches = dict(operands=None if operands is None else dict(operands), activations=activations, precision=precision, fill=fill)
         for name, spec in zip(SPEC_NAMES, self._specs):
             setattr(self, name, spec)
         self._handles = {}        # pred_offset -> device handle (the snap stage takes its N_hor from the handle)

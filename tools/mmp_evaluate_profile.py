@@ -57,9 +57,12 @@ larger of them in every run.
 ``--half-layer1``: the same protocol for layer1 on binary16 operands (``nmpc_mmp_block_f16``): ``parent`` -- layer2 .. layer4 on binary16
 operands with ``mmp_activations="f16"``, layer1 on float32 -- against ``mmp_precision="f16"``; the 16 launches alone per run and per block,
 then the loop; the record holds layer1's three launches and the stage of each run, the spreads and both merge conditions.
+``--fill-f16``: the same protocol for the fused first layer writing binary16 (``nmpc_mmp_stem_io_*``): ``parent`` -- ``mmp_precision="f16"``
+-- against the same with ``mmp_fill="f16"``; the fill's launch and the 16 block launches alone per run, then the loop; the record holds
+every part, every block of layer1 and the stage of each run, the stage's spreads and both merge conditions.
    usage: mmp_evaluate_profile.py OUT.json [B] [steps] [f32|f64] [n_ped] [n_hyp]
           [--fused-stem [REPS] | --fused-layer1 [REPS] | --fused-layer2 [REPS] | --fused-layer3 [REPS] | --fused-layer4 [REPS] | --half-layer3 [REPS]
-           | --half-layer4 [REPS] | --half-layer2 [REPS] | --activations-f16 [REPS] | --half-layer1 [REPS]]
+           | --half-layer4 [REPS] | --half-layer2 [REPS] | --activations-f16 [REPS] | --half-layer1 [REPS] | --fill-f16 [REPS]]
           (defaults 256 3 f32 4 20; 3)"""
 import json
 import os
@@ -1128,8 +1131,121 @@ def half_layer1_main(out_path, B, steps, dt, n_ped, K, reps):
                                           "margin", "conditions", "f16_layer1_over_mfma_model", "chunk_pedestrians")}))
 
 
+def fill_launch_rate(ev, n_item, reps=10):
+    """ms and GB/s stored of the fill's launch alone (``nmpc_mmp_stem_*`` or ``nmpc_mmp_stem_io_*``: nothing is decoded) on ``n_item``
+    pedestrians of the evaluator's start state, with the bytes of its output as they lie in memory."""
+    fe = ev.mmp_front
+    fe.allocate(n_item)
+    hist, hcount = ev.hist.contiguous(), ev.hcount.contiguous()
+    t = _timed(lambda: fe._launch_fill(hist.data_ptr(), hcount.data_ptr(), ev.B, ev.H, None, n_item), reps, warm=3)
+    nbytes = n_item * ev.N * int(np.prod(fe.fill_row)) * (2 if fe.fill_f16 else 4)
+    return {"items": n_item, "out_f16": int(fe.fill_f16), "bytes_stored": nbytes, **t, "store_GBps_median": nbytes / t["ms_median"] * 1e-6}
+
+
+def fill_f16_main(out_path, B, steps, dt, n_ped, K, reps):
+    """``--fill-f16``: the protocol of ``--half-layer1`` for the fused first layer writing binary16 (``nmpc_mmp_stem_io_*``). Both arms
+    run the whole network on the device on binary16 operands, alternated in one process: ``parent`` is ``mmp_precision="f16"``,
+    ``fill16`` the same with ``mmp_fill="f16"``. The fill's launch and the 16 block launches alone on one chunk per run and per block,
+    then the closed loop with events around every part. The two merge conditions, each in each run against the parent arm of the same
+    process: (a) the stage per lock-step faster by more than the larger of the two arms' run-to-run spreads; (b) neither ``input``
+    nor layer1's first block slower."""
+    from types import SimpleNamespace
+
+    from dyobav_mpcnwta_warehouse_amd.mmp_stem import split_network_whole
+    Hm, Wm, ref, tf, sc = _world(B, n_ped)
+    torch.manual_seed(0)
+    net = make_network(K).cuda().eval()
+    as_block = lambda b: SimpleNamespace(conv1=b.a, conv2=b.b, downsample=b.skip, leaky=b.act)
+    L = list(net)
+    shaped = SimpleNamespace(resnet34=SimpleNamespace(stem=SimpleNamespace(conv1=L[0], pooling=L[1]), layer1=[as_block(b) for b in L[2:5]],
+                                                      layer2=[as_block(b) for b in L[5:9]], layer3=[as_block(b) for b in L[9:15]],
+                                                      layer4=[as_block(b) for b in L[15:18]], apool=L[18]), fc1=L[20], leaky=L[21], swarm=L[22])
+    spec, blocks, blocks2, blocks3, blocks4, head = split_network_whole(shaped)
+    head = head._replace(c2=head.c2 + np.float32(150.0))   # (the "+ 150" that puts the random network's hypotheses on the map)
+    whole = dict(network=None, mmp_stem=spec, mmp_blocks=blocks, mmp_blocks2=blocks2, mmp_blocks3=blocks3, mmp_blocks4=blocks4, mmp_head=head,
+                 mmp_precision="f16")
+    paths = {"parent": dict(whole), "fill16": dict(whole, mmp_fill="f16")}
+    layers = ("layer1", "layer2", "layer3", "layer4")
+
+    def evaluator(path):
+        return BatchEvaluator(nm.default_config_struct(), dtype=np.float32 if dt == "f32" else np.float64, predictor="mmp", mmp_hyp=K,
+                              ref_image=ref, transform=tf, **paths[path], **sc)
+    rows_step = B * n_ped * nm.default_config_struct().N_hor
+    rec = {"what": "closed loop (row f3) on the reference scenarios, multi-hypothesis predictor stage, the whole network on the device on "
+                   "binary16 operands with binary16 activations between all blocks in both arms: the fused first layer writing float32 (arm "
+                   "'parent': mmp_precision = 'f16', nmpc_mmp_stem_*) against the same layer writing binary16 in the octet form, which "
+                   "layer1's first block reads as such (arm 'fill16': mmp_fill = 'f16', nmpc_mmp_stem_io_*), alternated in one process; "
+                   "random network of the reference's layer shapes",
+           "B": B, "n_ped": n_ped, "n_hyp": K, "dtype": dt, "max_steps": steps, "map": [Hm, Wm], "repetitions": reps,
+           "compared_with": {"float4_copy_TBps": COPY_TBS}, "chunk_pedestrians": {}, "bytes_per_item": {},
+           "fill": {p: [] for p in paths}, "kernels": {p: [] for p in paths}, "runs": {p: [] for p in paths}}
+    for _ in range(reps):                                   # the launches alone, per arm, alternated (the first also warms up)
+        for path in paths:
+            ev = evaluator(path)
+            rec["chunk_pedestrians"][path], rec["bytes_per_item"][path] = ev.mmp_chunk, ev.mmp_front.bytes_per_item
+            try:
+                n_item = min(ev.mmp_chunk, B * n_ped)
+                rec["fill"][path].append(fill_launch_rate(ev, n_item))
+                rec["kernels"][path].append(activations_kernel_rate(ev, n_item, names=layers))
+                ev.run(max_steps=1)
+            finally:
+                ev.close()
+            r, f = rec["kernels"][path][-1], rec["fill"][path][-1]
+            print(path, json.dumps({"items": f["items"], "fill_ms": f["ms_median"], "fill_GBps": f["store_GBps_median"], "rows": r["rows"],
+                                    "sixteen_launches_ms": r["ms_median"], "each": [b["ms_median"] for b in r["blocks"]]}), flush=True)
+            with open(out_path, "w") as f:
+                json.dump(rec, f, indent=1)
+    for _ in range(reps):
+        for path in paths:
+            ev = evaluator(path)
+            ev.time_predictor = ev.time_predictor_parts = True
+            try:
+                res = ev.run(max_steps=steps)
+            finally:
+                ev.close()
+            parts = ev.predictor_part_ms
+            rec["runs"][path].append([dict(step=t, stage_ms=ev.predictor_ms[t], solve_ms=res.solve_ms[t], **{k: v[t] for k, v in parts.items()})
+                                      for t in range(len(ev.predictor_ms))])
+            print(path, json.dumps(rec["runs"][path][-1]), flush=True)
+            with open(out_path, "w") as f:                  # (kept even if a later run does not finish)
+                json.dump(rec, f, indent=1)
+    med = lambda path, key: float(np.median([key(s) for run in rec["runs"][path] for s in run]))
+    names = ("input",) + layers + ("head",)
+    spread = lambda v: (max(v) - min(v)) / float(np.median(v))
+    per_run = lambda key: {p: [float(np.median([s[key] for s in run])) for run in rec["runs"][p]] for p in paths}
+    rec["median_per_lock_step_ms"] = {p: dict({k: med(p, lambda s, k=k: s[k]) for k in names}, stage=med(p, lambda s: s["stage_ms"])) for p in paths}
+    rec["stage_median_of_each_run_ms"], rec["input_median_of_each_run_ms"] = per_run("stage_ms"), per_run("input")
+    rec["layer1_median_of_each_run_ms"] = per_run("layer1")
+    rec["each_block_median_ms"] = {p: [float(np.median([r["blocks"][i]["ms_median"] for r in rec["kernels"][p]])) for i in range(16)] for p in paths}
+    rec["each_block_GBps_median"] = {p: [float(np.median([r["blocks"][i]["GBps_median"] for r in rec["kernels"][p]])) for i in range(16)] for p in paths}
+    # per lock-step: the launch alone on one chunk, scaled to the rows of a lock-step (the arms' chunks differ: bytes_per_item does)
+    rec["rows_of_a_chunk"] = {p: rec["kernels"][p][0]["rows"] for p in paths}
+    rec["each_block_per_lock_step_ms"] = {p: [float(np.median([r["blocks"][i]["ms_median"] * rows_step / r["rows"] for r in rec["kernels"][p]]))
+                                              for i in range(16)] for p in paths}
+    rec["fill_launch_of_each_run_ms"] = {p: [f["ms_median"] * B * n_ped / f["items"] for f in rec["fill"][p]] for p in paths}
+    rec["fill_store_GBps_of_each_run"] = {p: [f["store_GBps_median"] for f in rec["fill"][p]] for p in paths}
+    rec["first_block_of_each_run_ms"] = {p: [r["blocks"][0]["ms_median"] * rows_step / r["rows"] for r in rec["kernels"][p]] for p in paths}
+    stage, inp, first, fill = (rec[k] for k in ("stage_median_of_each_run_ms", "input_median_of_each_run_ms", "first_block_of_each_run_ms",
+                                                "fill_launch_of_each_run_ms"))
+    rec["run_to_run_spread"] = {"stage": {p: spread(stage[p]) for p in paths}}
+    ratio = lambda v: [a / b for a, b in zip(v["fill16"], v["parent"])]
+    rec["fill16_over_parent_of_each_run"] = {"stage": ratio(stage), "input": ratio(inp), "first_block": ratio(first), "fill_launch": ratio(fill)}
+    rec["margin"] = {"stage": max(rec["run_to_run_spread"]["stage"].values())}
+    # (a) the stage faster in every run by more than the margin; (b) neither input nor layer1's first block slower in any run
+    rec["conditions"] = {"a_stage_faster_in_every_run": all(r < 1.0 - rec["margin"]["stage"] for r in rec["fill16_over_parent_of_each_run"]["stage"]),
+                         "b_input_not_slower": all(r <= 1.0 for r in rec["fill16_over_parent_of_each_run"]["input"]),
+                         "b_first_block_not_slower": all(r <= 1.0 for r in rec["fill16_over_parent_of_each_run"]["first_block"])}
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("median_per_lock_step_ms", "stage_median_of_each_run_ms", "input_median_of_each_run_ms",
+                                          "layer1_median_of_each_run_ms", "rows_of_a_chunk", "each_block_median_ms", "each_block_per_lock_step_ms",
+                                          "each_block_GBps_median", "fill_launch_of_each_run_ms",
+                                          "fill_store_GBps_of_each_run", "first_block_of_each_run_ms", "run_to_run_spread",
+                                          "fill16_over_parent_of_each_run", "margin", "conditions", "chunk_pedestrians", "bytes_per_item")}))
+
+
 def main():
-    for flag, run in (("--half-layer1", half_layer1_main), ("--activations-f16", activations_f16_main), ("--half-layer2", half_layer2_main), ("--half-layer4", half_layer4_main), ("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
+    for flag, run in (("--fill-f16", fill_f16_main), ("--half-layer1", half_layer1_main), ("--activations-f16", activations_f16_main), ("--half-layer2", half_layer2_main), ("--half-layer4", half_layer4_main), ("--half-layer3", half_layer3_main), ("--fused-layer4", fused_layer4_main), ("--fused-layer3", fused_layer3_main), ("--fused-layer2", fused_layer2_main), ("--fused-layer1", fused_layer1_main), ("--fused-stem", fused_stem_main)):
         if flag in sys.argv:
             i = sys.argv.index(flag)
             reps = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 3
