@@ -96,6 +96,12 @@ class NmpcKfArgs(C.Structure):
         return self
 
 
+class NmpcFleetArgs(C.Structure):
+    """Mirror of ``struct nmpc_fleet_args`` (device pointers; ``ts`` / ``width`` <= 0: the handle's ``ts`` / ``vehicle_width``)."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "R", "n_run", "reserved")] + [("run", C.c_void_p), ("ts", C.c_double), ("width", C.c_double)] +
+                [(n, C.c_void_p) for n in ("robot", "U_prev", "alive", "other_c", "clr_fleet", "collision", "complete", "collision_fleet")])
+
+
 class NmpcDwaArgs(C.Structure):
     """Mirror of ``struct nmpc_dwa_args`` (device pointers)."""
     _fields_ = ([(n, C.c_int32) for n in ("B", "n_run", "H", "M", "Pmax", "cap", "dyn_mode", "reserved")] +
@@ -232,6 +238,7 @@ EXPORTED_SYMBOLS = (
     "nmpc_loop_pre_f32", "nmpc_loop_pre_f64", "nmpc_loop_post_f32", "nmpc_loop_post_f64",
     "nmpc_kf_predict_f32", "nmpc_kf_predict_f64", "nmpc_dwa_step_f32", "nmpc_dwa_step_f64",
     "nmpc_dwa_step_lists_f32", "nmpc_dwa_step_lists_f64",
+    "nmpc_fleet_exchange_f32", "nmpc_fleet_exchange_f64", "nmpc_fleet_post_f32", "nmpc_fleet_post_f64",
     "nmpc_mmp_input_f32", "nmpc_mmp_input_f64", "nmpc_mmp_stem_f32", "nmpc_mmp_stem_f64", "nmpc_mmp_stem_shape", "nmpc_mmp_block_f32",
     "nmpc_mmp_block2_f32", "nmpc_mmp_block2_f16", "nmpc_mmp_block3_f32", "nmpc_mmp_block3_f16", "nmpc_mmp_block4_f32", "nmpc_mmp_block4_f16", "nmpc_mmp_head_f32",
     "nmpc_mmp_block2_f16_io", "nmpc_mmp_block3_f16_io", "nmpc_mmp_block4_f16_io", "nmpc_mmp_block_f16", "nmpc_mmp_block_f16_io",
@@ -328,6 +335,8 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
         getattr(lib, "nmpc_kf_predict_" + sfx).argtypes = [vp, C.POINTER(NmpcKfArgs)]
         getattr(lib, "nmpc_dwa_step_" + sfx).argtypes = [vp, C.POINTER(NmpcDwaArgs)]
         getattr(lib, "nmpc_dwa_step_lists_" + sfx).argtypes = [vp, C.POINTER(NmpcDwaListsArgs)]
+        getattr(lib, "nmpc_fleet_exchange_" + sfx).argtypes = [vp, C.POINTER(NmpcFleetArgs)]
+        getattr(lib, "nmpc_fleet_post_" + sfx).argtypes = [vp, C.POINTER(NmpcFleetArgs)]
         getattr(lib, "nmpc_mmp_input_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpArgs)]
         getattr(lib, "nmpc_mmp_stem_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpStemArgs)]
         getattr(lib, "nmpc_mmp_stem_io_" + sfx).argtypes = [vp, C.POINTER(NmpcMmpStemArgs), i32]
@@ -563,6 +572,19 @@ class Handle:
         ``dyn_count[n_run, N+1]`` (int32), as ``hypotheses_to_ellipses(..., counts=)`` writes them; everything else as ``dwa_step``
         with ``dyn_mode`` 2. One launch enqueued on the handle's stream."""
         fn = getattr(self._lib, "nmpc_dwa_step_lists_" + _suffix(dtype))
+        _check(fn(self._h, C.byref(args) if args is not None else None))
+
+    def fleet_exchange(self, dtype, args: "NmpcFleetArgs"):
+        """``nmpc_fleet_exchange_*``: the other-robot blocks ``other_c[n_run, 3 (N + 1) Nother]`` of the running robots from their
+        group's peers (current states, previous solutions rolled out; nearest ``Nother - 1``, slot 0 zero), one launch enqueued on
+        the handle's stream. The block is what ``assemble_params(..., other_robots=)`` takes."""
+        fn = getattr(self._lib, "nmpc_fleet_exchange_" + _suffix(dtype))
+        _check(fn(self._h, C.byref(args) if args is not None else None))
+
+    def fleet_post(self, dtype, args: "NmpcFleetArgs"):
+        """``nmpc_fleet_post_*``: robot-robot clearance and collision of the robots that ran this step, after ``loop_step(post=True)``
+        on the same run list; one launch enqueued on the handle's stream."""
+        fn = getattr(self._lib, "nmpc_fleet_post_" + _suffix(dtype))
         _check(fn(self._h, C.byref(args) if args is not None else None))
 
     def mmp_input(self, dtype, args: "NmpcMmpArgs"):

@@ -24,6 +24,7 @@
 #include "nmpc_hypotheses.h"
 #include "nmpc_step.h"
 #include "nmpc_kf.h"
+#include "nmpc_fleet.h"
 #include "nmpc_dwa.h"
 #include "nmpc_snap.h"
 #include "nmpc_mmp.h"
@@ -1618,6 +1619,50 @@ int kf_predict(nmpc_handle_s* h, const nmpc_kf_args* g)
     return 0;
 }
 
+// nmpc_fleet_exchange_* (post = false) and nmpc_fleet_post_* (post = true): csrc/nmpc_fleet.h
+template <typename T>
+int fleet_step(nmpc_handle_s* h, const nmpc_fleet_args* g, bool post)
+{
+    const char* fn = post ? "nmpc_fleet_post" : "nmpc_fleet_exchange";
+    if (!h || !g) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: the handle or the argument block is NULL", fn);
+    if (g->R < 1) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: R = %d, a fleet has at least one member", fn, g->R);
+    if (g->R > 64) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: R = %d exceeds the 64 members one wavefront holds", fn, g->R);
+    if (g->B < 1 || g->B % g->R != 0) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: B = %d is not a positive multiple of R = %d", fn, g->B, g->R);
+    if (g->n_run <= 0) return g->n_run == 0 ? 0 : fail(NMPC_ERR_INVALID_ARGUMENT, "%s: n_run = %d < 0", fn, g->n_run);
+    if (g->n_run > g->B) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: n_run = %d exceeds B = %d", fn, g->n_run, g->B);
+    if (!g->run && g->n_run != g->B) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: run = NULL needs n_run = B", fn);
+    if (!g->robot) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: robot is NULL", fn);
+    if (post) {
+        if (!g->alive || !g->clr_fleet || !g->collision || !g->complete)
+            return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: alive, clr_fleet, collision or complete is NULL", fn);
+    } else {
+        if (!g->other_c) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: other_c is NULL", fn);
+        if (g->U_prev && !g->alive) return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: alive is NULL beside a U_prev", fn);
+    }
+    const size_t row_bytes = (size_t)3 * (h->cfg.N_hor + 1) * h->cfg.Nother * sizeof(T);
+    if (!post && row_bytes > kLdsOptIn)
+        return fail(NMPC_ERR_UNSUPPORTED, "%s: the staged row of 3 (N_hor + 1) Nother reals = %zu bytes exceeds 48 KB", fn, row_bytes);
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    // (a host pointer here would fault inside the kernel: samples of the argument block are looked up)
+    if (h->ptr_mode != NMPC_PTR_DEVICE && (!is_device_ptr(g->robot) || !is_device_ptr(post ? g->clr_fleet : g->other_c) ||
+                                           (g->run && !is_device_ptr(g->run))))
+        return fail(NMPC_ERR_INVALID_ARGUMENT, "%s: every array must be a device pointer", fn);
+    nmpc::FleetParams<T> p;
+    std::memset(&p, 0, sizeof p);
+    p.B = g->B, p.R = g->R, p.n_run = g->n_run, p.N = h->cfg.N_hor, p.Nother = h->cfg.Nother;
+    p.run = reinterpret_cast<const long long*>(g->run);
+    p.ts = (T)(g->ts > 0.0 ? g->ts : h->cfg.ts), p.width = (T)(g->width > 0.0 ? g->width : h->cfg.vehicle_width);
+    p.robot = static_cast<const T*>(g->robot), p.U = static_cast<const T*>(g->U_prev);
+    p.alive = g->alive, p.collision = g->collision, p.complete = g->complete, p.collision_fleet = g->collision_fleet;
+    p.other_c = static_cast<T*>(g->other_c), p.clr_fleet = static_cast<T*>(g->clr_fleet);
+    if (post)
+        hipLaunchKernelGGL(nmpc::fleet_post_kernel<T>, dim3(g->n_run), dim3(64), 0, h->stream, p);
+    else
+        hipLaunchKernelGGL(nmpc::fleet_exchange_kernel<T>, dim3(g->n_run), dim3(64), row_bytes, h->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // What nmpc_mmp_input and nmpc_mmp_stem share (their args and params structs agree in these names): the refusals both open
 // with, under the name fn, and the item list, history and plane constants -- both kernels must compute the same planes.
 template <typename Args>
@@ -2510,6 +2555,11 @@ int nmpc_loop_post_f64(nmpc_handle h, const nmpc_loop_args* a) { return loop_ste
 
 int nmpc_kf_predict_f32(nmpc_handle h, const nmpc_kf_args* a) { return kf_predict<float>(h, a); }
 int nmpc_kf_predict_f64(nmpc_handle h, const nmpc_kf_args* a) { return kf_predict<double>(h, a); }
+
+int nmpc_fleet_exchange_f32(nmpc_handle h, const nmpc_fleet_args* a) { return fleet_step<float>(h, a, false); }
+int nmpc_fleet_exchange_f64(nmpc_handle h, const nmpc_fleet_args* a) { return fleet_step<double>(h, a, false); }
+int nmpc_fleet_post_f32(nmpc_handle h, const nmpc_fleet_args* a) { return fleet_step<float>(h, a, true); }
+int nmpc_fleet_post_f64(nmpc_handle h, const nmpc_fleet_args* a) { return fleet_step<double>(h, a, true); }
 int nmpc_dwa_step_f32(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<float>(h, a); }
 int nmpc_dwa_step_f64(nmpc_handle h, const nmpc_dwa_args* a) { return dwa_step<double>(h, a); }
 int nmpc_dwa_step_lists_f32(nmpc_handle h, const nmpc_dwa_lists_args* a) { return dwa_step<float, true, nmpc_dwa_lists_args>(h, a); }

@@ -41,6 +41,11 @@ scenarios still running:
    order, status counts, ``_solve``); or ``_dwa_step`` = ``nmpc_dwa_step_*`` (behind ``_mmp_predict``: ``nmpc_dwa_step_lists_*``);
 4. ``nmpc_loop_post_*``: first action, agent motion, metrics, flags.
 
+With ``fleet=R`` the scenarios form groups of R consecutive robots in one world (``csrc/nmpc_fleet.h``): between
+stages 2 and 3 ``nmpc_fleet_exchange_*`` writes every running robot's other-robot block from its group's peers (their current
+states and their previous solutions rolled out), which f1 copies into the parameter vector, and after stage 4
+``nmpc_fleet_post_*`` adds robot-robot clearance and collision on the same run list.
+
 A run starts in ``_start_run`` (flags and metrics, one namespace with the ``_loop_args`` / ``_kf_args`` / ``_mmp_args`` / ``_dwa_args`` buffers)
 and ends in ``_finish_run``. ``_run_torch`` (``fused=False``) is stages 1 and 4 written out op by op in torch around the same
 ``_mpc_step`` -- the implementation of rounds 1-2, kept as the independent check of the kernels. Where the reference runs
@@ -80,6 +85,8 @@ class EvaluationResult:
     n_obs: Optional[np.ndarray] = None       # [T, B] int32, predictor "mmp": clusters found per step (> Ndynobs: the obstacle
     #                                          list was truncated), -1 where the scenario was not running
     n_outside: Optional[np.ndarray] = None   # [T, B] int32, predictor "mmp": hypotheses the network put outside the map
+    clearance_fleet: Optional[np.ndarray] = None   # [B], ``fleet=R``: min distance to another member of the robot's group (inf for R = 1)
+    collision_fleet: Optional[np.ndarray] = None   # [B] bool, ``fleet=R``: the run ended in a robot-robot collision (``collision`` counts it too)
 
 
 def action_smoothness(A):
@@ -132,8 +139,21 @@ class BatchEvaluator:
                  tracker: str = "mpc", dwa_config=None, network=None, mmp_hyp: int = 20, mmp_chunk: Optional[int] = None,
                  ref_image=None, transform=None, rescale: float = 1.0, mmp_stem=None, mmp_blocks=None, mmp_blocks2=None, mmp_blocks3=None,
                  mmp_blocks4=None, mmp_head=None, mmp_half=(), mmp_operands=None, mmp_activations=None, mmp_precision=None,
-                 mmp_fill=None):
-        """``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
+                 mmp_fill=None, fleet: Optional[int] = None, fleet_coupling: bool = True):
+        """``fleet``: ``None`` (default) launches nothing new and changes no bit. ``R`` (1 .. 64, ``B % R == 0``): scenarios
+        ``g R .. g R + R - 1`` are the robots of one group, which share the static map and the pedestrians -- every member gets the
+        pedestrian starts and paths of the group's member 0 and the same stagger draw per step ([G, H] drawn, expanded to [B, H]).
+        Per time step ``nmpc_fleet_exchange_*`` (csrc/nmpc_fleet.h) fills the other-robot blocks ``[c_0 | c]`` of the running robots
+        from their peers -- current state in ``c_0``, the previous solution's N controls rolled out from the current state in ``c``
+        (at rest on the first step and for robots that have stopped), the nearest ``Nother - 1`` peers nearest first from slot 1, slot 0
+        and unused slots zero -- into ``other_c`` (allocated once), which ``assemble_params(..., other_robots=)`` copies into ``P``; after
+        ``loop_step(post=True)`` ``nmpc_fleet_post_*`` keeps ``clearance_fleet`` and turns a centre distance ``<= vehicle_width`` into a
+        collision (``collision_fleet``; it beats a completion of the same step; a parked robot's outcome is never changed).
+        ``fleet_coupling=False`` runs that epilogue only, the blocks stay zeros: the uncoupled arm of a comparison. ``fleet=1`` computes
+        the same ``P``, bit for bit, as ``fleet=None``. Needs ``tracker="mpc"`` and ``fused=True`` (the torch path does not have it); works
+        with every predictor. Not modelled: priorities, deadlock resolution, any negotiation between robots.
+
+        ``tracker``: ``"mpc"`` = the NMPC solver (f1 + solve), ``"dwa"`` = the reference's dynamic-window baseline
         (``pkg_dwa_tracker``; one kernel, ``nmpc_dwa_step_*``, csrc/nmpc_dwa.h, in place of f1 + solve; ``dwa_config``: a
         :class:`.configs.DwaConfiguration`, default = the reference's ``dwa_test.yaml`` values; its ``ts`` / ``N_hor`` must be the
         configuration's). It runs with ``predictor`` ``None`` (the pedestrians' current positions, as the reference without a
@@ -279,6 +299,21 @@ class BatchEvaluator:
             raise ValueError("tracker = 'dwa' needs n_hyp = 1 and fused = True")
         if config is None:
             raise ValueError("config is None: an NmpcConfigStruct is needed (default_config_struct())")
+        self.fleet, self.fleet_coupling = None, bool(fleet_coupling)
+        if fleet is not None:
+            if not fused:
+                raise ValueError("fleet needs fused = True: the torch path does not have the fleet kernels")
+            if tracker != "mpc":
+                raise ValueError("fleet needs tracker = 'mpc': the dynamic-window tracker has no other-robot terms")
+            if int(fleet) != fleet or not 1 <= int(fleet) <= 64:
+                raise ValueError(f"fleet = {fleet!r}: a group has 1 .. 64 robots")
+            if robot_starts.shape[0] % int(fleet) != 0:
+                raise ValueError(f"fleet = {fleet}: B = {robot_starts.shape[0]} scenarios are not a whole number of groups")
+            self.fleet = int(fleet)
+            if self.fleet > 1:      # one pedestrian set per group: member 0's
+                R, G = self.fleet, robot_starts.shape[0] // self.fleet
+                human_starts = np.repeat(np.asarray(human_starts).reshape((G, R) + np.shape(human_starts)[1:])[:, 0], R, axis=0)
+                human_paths = np.repeat(np.asarray(human_paths).reshape((G, R) + np.shape(human_paths)[1:])[:, 0], R, axis=0)
         self.tracker, self.predictor = tracker, predictor
         self.dwa_config = None
         if tracker == "dwa":
@@ -298,6 +333,8 @@ class BatchEvaluator:
         # predictor_part_ms: name -> ms per step)
         self.time_predictor, self.time_tracker, self.time_predictor_parts = False, False, False
         self.predictor_ms, self.tracker_ms, self.predictor_part_ms = [], [], {}
+        # time_fleet: HIP events around every nmpc_fleet_exchange / nmpc_fleet_post call; run() leaves fleet_ms: name -> ms per step
+        self.time_fleet, self.fleet_ms = False, {}
         self.time_solves = True     # record the HIP-event time of every batched solve (one event wait per time step)
         self.dt = np.dtype(dtype)
         self.tdt = torch.float32 if self.dt == np.float32 else torch.float64
@@ -369,6 +406,8 @@ class BatchEvaluator:
             self._init_dwa(robot_paths)
         if predictor == "mmp":
             self._init_mmp(network, mmp_hyp, mmp_chunk, ref_image, transform, rescale, mmp_specs, mmp_half, **mmp_switches)
+        if self.fleet is not None and self.fleet_coupling:
+            self.other_c = torch.empty(B, 3 * (self.N + 1) * int(config.Nother), dtype=self.tdt, device=self.dev)
 
     def _tensor(self, x):
         return self.torch.as_tensor(np.ascontiguousarray(x), dtype=self.tdt, device=self.dev)
@@ -548,9 +587,11 @@ class BatchEvaluator:
         if self.stagger_replay is not None:
             return self.stagger_replay.pop(0).to(self.tdt).contiguous()
         if self.stagger > 0:
-            sign = torch.randint(0, 2, (self.B, self.H), generator=self.gen, device=self.dev) * 2 - 1
-            mag = torch.randint(0, 11, (self.B, self.H), generator=self.gen, device=self.dev).to(self.tdt) / 10
-            return (sign.to(self.tdt) * mag * self.stagger).contiguous()
+            R = self.fleet or 1     # one draw per group: its members see the same pedestrians
+            sign = torch.randint(0, 2, (self.B // R, self.H), generator=self.gen, device=self.dev) * 2 - 1
+            mag = torch.randint(0, 11, (self.B // R, self.H), generator=self.gen, device=self.dev).to(self.tdt) / 10
+            st = sign.to(self.tdt) * mag * self.stagger
+            return (st if R == 1 else st.repeat_interleave(R, dim=0)).contiguous()
         return None
 
     def _step_humans(self):
@@ -609,7 +650,9 @@ class BatchEvaluator:
             collision=collision.cpu().numpy(), complete=r.complete.bool().cpu().numpy(), steps=r.steps.cpu().numpy(),
             smoothness=action_smoothness(acts).cpu().numpy(), clearance=r.clr_stc.cpu().numpy(), clearance_dyn=r.clr_dyn.cpu().numpy(),
             deviation=torch.stack([r.dev_sum / r.n_traj, r.dev_max], dim=1).cpu().numpy(),
-            trajectory=traj.cpu().numpy(), actions=acts.cpu().numpy(), solve_ms=solve_ms)
+            trajectory=traj.cpu().numpy(), actions=acts.cpu().numpy(), solve_ms=solve_ms,
+            clearance_fleet=r.clr_fleet.cpu().numpy() if hasattr(r, "clr_fleet") else None,
+            collision_fleet=r.collision_fleet.bool().cpu().numpy() if hasattr(r, "collision_fleet") else None)
 
     def _loop_args(self, r, max_steps):
         """``NmpcLoopArgs`` of a run: the evaluator's state (made contiguous: the kernels update it in place), the run's
@@ -649,6 +692,17 @@ class BatchEvaluator:
         kf.humans, kf.hcount, kf.dyn_c = self.humans.data_ptr(), self.hcount.data_ptr(), r.dyn_c.data_ptr()
         kf.kf_traj, kf.kf_len, kf.kf_P = r.kf_traj.data_ptr(), r.kf_len.data_ptr(), r.kf_P.data_ptr()
         return kf
+
+    def _fleet_args(self, r):
+        """``NmpcFleetArgs`` of a run: the full robot / U / flag arrays, the run's fleet clearance and flag, the blocks."""
+        r.clr_fleet, r.collision_fleet = self._full(self.B, fill=float("inf")), self._full(self.B, dtype=self.torch.uint8, fill=0)
+        r.other_in = None
+        fa = _capi.NmpcFleetArgs()
+        fa.B, fa.R, fa.ts, fa.width = self.B, self.fleet, float(self.ts), float(self.cfg.vehicle_width)
+        fa.robot, fa.alive, fa.collision, fa.complete = self.robot.data_ptr(), r.alive.data_ptr(), r.collision.data_ptr(), r.complete.data_ptr()
+        fa.clr_fleet, fa.collision_fleet = r.clr_fleet.data_ptr(), r.collision_fleet.data_ptr()
+        fa.other_c = self.other_c.data_ptr() if self.fleet_coupling else None
+        return fa
 
     def _mmp_args(self, r, max_steps):
         """The stage's buffers of a run: the hypotheses (pedestrian major as the network returns them, then per scenario as snap
@@ -787,7 +841,7 @@ class BatchEvaluator:
         harvesting hook, the solves."""
         Pa = self.P if nA == self.B else self.P[:nA]
         self.h.assemble_params(self.dt, nA, Pa, r.last_u_c, r.state_c, r.refs_c, r.speed_c, self.tuning, self.stcw, self.dynw,
-                               self.polys, getattr(r, "dyn_in", r.dyn_c)[:nA])
+                               self.polys, getattr(r, "dyn_in", r.dyn_c)[:nA], other_robots=getattr(r, "other_in", None))
         if self.on_params is not None:
             self.on_params(kt, idx, Pa)
         return self._solve_step(kt, idx, nA, Pa, Ua, ya, rec)
@@ -810,6 +864,9 @@ class BatchEvaluator:
         kf = self._kf_args(r, max_steps) if self.predictor == "kfmp" else None
         mm = self._mmp_args(r, max_steps) if self.predictor == "mmp" else None
         dw = self._dwa_args(r) if self.tracker == "dwa" else None
+        fa = self._fleet_args(r) if self.fleet is not None else None       # (after _loop_args: self.robot is the contiguous array)
+        fleet_exchange, exchange_events = self._timed(self.h.fleet_exchange, self.time_fleet)
+        fleet_post, post_events = self._timed(self.h.fleet_post, self.time_fleet)
         kf_predict, kf_events = self._timed(self.h.kf_predict, self.time_predictor)
         mmp_predict, mmp_events = self._timed(self._mmp_predict, self.time_predictor)
         dwa_step, dwa_events = self._timed(self.h.dwa_step_lists if self.tracker == "dwa" and mm is not None else self.h.dwa_step, self.time_tracker)
@@ -821,6 +878,9 @@ class BatchEvaluator:
             idx = torch.nonzero(r.alive, as_tuple=False).squeeze(1).contiguous() if self.compact else None
             nA = int(idx.numel()) if idx is not None else B
             full = nA == B
+            # the robots that run this step, for the fleet epilogue: without compaction loop_post takes all B and skips the stopped
+            # ones by their flag, which it has just cleared for those that stop now
+            ran = idx if (fa is None or self.compact) else torch.nonzero(r.alive, as_tuple=False).squeeze(1).contiguous()
             Ua = self.U if full else self._Ua[:nA]
             ya = self.y if full else r.ya_buf[:nA]
             st = self._draw_stagger()
@@ -839,12 +899,20 @@ class BatchEvaluator:
                 rec.update(dyn=(r.mmp_dyn if full else torch.zeros_like(r.mmp_dyn).index_copy_(0, idx, r.mmp_dyn[:nA])).cpu().numpy(),
                            dyn_count=(r.mmp_counts if full else torch.zeros_like(r.mmp_counts).index_copy_(0, idx, r.mmp_counts[:nA])).cpu().numpy(),
                            n_obs=r.mmp_obs_steps[kt].cpu().numpy(), n_outside=r.mmp_out_steps[kt].cpu().numpy())
+            if fa is not None and self.fleet_coupling:
+                fa.n_run, fa.run, fa.U_prev = nA, a.run, (self.U.data_ptr() if kt > 0 else None)
+                fleet_exchange(self.dt, fa)
+                r.other_in = self.other_c[:nA]
             if dw is not None:
                 dw.n_run, dw.run, dw.U_c = nA, a.run, Ua.data_ptr()
                 hs = self._dwa_step(r, dw, dwa_step, idx, nA, Ua, rec)
             else:
                 hs = self._mpc_step(r, kt, idx, nA, Ua, ya, rec)
             self.h.loop_step(self.dt, a, post=True)
+            if fa is not None:
+                fa.n_run = int(ran.numel())
+                fa.run = None if fa.n_run == B else ran.data_ptr()
+                fleet_post(self.dt, fa)
             if rec is not None:
                 if hs is not None:
                     rec["U"] = self.U.cpu().numpy()
@@ -855,6 +923,9 @@ class BatchEvaluator:
             if events:
                 torch.cuda.synchronize(self.dev)
                 setattr(self, name, [e0.elapsed_time(e1) for e0, e1 in events])
+        if exchange_events or post_events:
+            torch.cuda.synchronize(self.dev)
+            self.fleet_ms = {name: [e0.elapsed_time(e1) for e0, e1 in ev] for name, ev in (("exchange", exchange_events), ("post", post_events)) if ev}
         res = self._finish_run(r, r.traj[:, :n_steps_run + 1], r.acts[:, :n_steps_run], solve_ms)
         if mm is not None:
             res.n_obs, res.n_outside = r.mmp_obs_steps[:n_steps_run].cpu().numpy(), r.mmp_out_steps[:n_steps_run].cpu().numpy()

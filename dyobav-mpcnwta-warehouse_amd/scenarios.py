@@ -337,6 +337,77 @@ def make_reference_scenarios(B: int, seed: int = 13, n_ped: int = 4, n_waypoints
                 map_polygons=np.array(w["map_polygons_world"], dtype=float), scenario_index=sidx)
 
 
+def make_fleet_scenarios(G: int, R: int, seed: int = 13, n_ped: int = 4, n_waypoints: int = 4, scenario: int | None = None,
+                         n_nodes: int = 4, min_separation: float = 1.0, layouts: int = 48) -> dict:
+    """G fleets of R robots on the reference's warehouse for ``BatchEvaluator(fleet=R)``: scenario ``b = g R + i`` is member i of
+    group g.
+
+    * member 0 of group g is the robot ``make_reference_scenarios(G, seed, n_ped, n_waypoints, scenario)`` gives scenario g (start
+      state and node path of ``scenario_{g % 3}``), and the group's ONE pedestrian set is that scenario's -- every member carries
+      a copy (the evaluator steps the pedestrians per member, in lock-step with one stagger draw per group);
+    * members 1 .. R - 1 drive seeded node paths of the same graph, like the extra pedestrians there: a non-backtracking walk of
+      ``n_nodes`` nodes; the robot starts within 0.3 m of a point on the walk's first edge, heading for its second node, and its
+      path is the rest of the walk. A start is redrawn until it is farther than ``min_separation`` (> vehicle_width: no run starts in a collision) from
+      every earlier member's start of its group;
+    * the members' layout of group g is that of group ``g % layouts`` (``layouts`` a multiple of 3, so that it belongs to the same
+      reference scenario): further groups are Monte-Carlo repetitions with other pedestrians, as ``max_num_run`` repeats a scenario
+      in the reference, and the evaluator builds one reference trajectory per distinct robot.
+
+    Deterministic in its arguments. Returns the keyword arguments of ``BatchEvaluator`` (``B = G R`` rows) plus ``scenario_index``
+    [B] and ``group`` [B]."""
+    if R < 1 or G < 1:
+        raise ValueError(f"G = {G}, R = {R}")
+    if layouts < 3 or layouts % 3 != 0:
+        raise ValueError(f"layouts = {layouts} must be a positive multiple of 3")
+    base = make_reference_scenarios(G, seed=seed, n_ped=n_ped, n_waypoints=n_waypoints, scenario=scenario)
+    w = warehouse_world()
+    nodes = {int(k): np.array(v, dtype=float) for k, v in w["nodes_world"].items()}
+    adj: dict = {k: [] for k in nodes}
+    for a, b in w["graph_edges"]:
+        adj[a].append(b)
+        adj[b].append(a)
+    ids = sorted(nodes)
+    drawn = {}
+
+    def layout(l):
+        """Starts [R - 1, 3] and node paths of the members 1 .. R - 1 of layout l (its member 0: base scenario l)."""
+        if l not in drawn:
+            rng = np.random.default_rng(np.random.SeedSequence([seed, 7919, l]))
+            placed = [np.asarray(base["robot_starts"][l][:2], dtype=float)]      # (l = g % layouts <= g < G)
+            starts, paths, tries = [], [], 0
+            while len(starts) < R - 1:
+                walk = [ids[int(rng.integers(len(ids)))]]
+                while len(walk) < n_nodes:
+                    nxt = [n for n in adj[walk[-1]] if len(walk) < 2 or n != walk[-2]] or adj[walk[-1]]
+                    walk.append(nxt[int(rng.integers(len(nxt)))])
+                # somewhere on the walk's first edge (32 nodes alone do not hold 64 robots a metre apart), within 0.3 m of it
+                p0 = nodes[walk[0]] + rng.uniform(0.0, 0.8) * (nodes[walk[1]] - nodes[walk[0]]) + rng.uniform(-0.3, 0.3, 2)
+                tries += 1
+                if tries > 20000:
+                    raise ValueError(f"no room for R = {R} robots {min_separation} m apart on the warehouse graph")
+                if min(np.linalg.norm(p0 - q) for q in placed) <= min_separation:
+                    continue
+                head = nodes[walk[1]] - p0
+                placed.append(p0)
+                starts.append([p0[0], p0[1], float(np.arctan2(head[1], head[0]))])
+                paths.append([tuple(float(v) for v in nodes[n]) for n in walk[1:]])
+            drawn[l] = (np.array(starts, dtype=float).reshape(R - 1, 3), paths)
+        return drawn[l]
+
+    B = G * R
+    starts = np.empty((B, 3))
+    paths = []
+    for g in range(G):
+        starts[g * R] = base["robot_starts"][g]
+        paths.append(base["robot_paths"][g])
+        st, pa = layout(g % layouts)
+        starts[g * R + 1:(g + 1) * R] = st
+        paths.extend(pa)
+    rep = lambda x: np.repeat(np.asarray(x), R, axis=0)
+    return dict(robot_starts=starts, robot_paths=paths, human_starts=rep(base["human_starts"]), human_paths=rep(base["human_paths"]),
+                map_polygons=base["map_polygons"], scenario_index=rep(base["scenario_index"]), group=np.repeat(np.arange(G), R))
+
+
 HUMAN_STAGGER = 0.5     # main_base.py:77
 
 
